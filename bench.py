@@ -1,12 +1,16 @@
 #!/usr/bin/env python
 """Benchmark of the AdvChain adversarial-augmentation inner loop on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2] [--dump-outputs DIR] [--full]
 
 One "step" = one ``solver.adversarial_training(data, model, n_iter=...)`` call on one synthetic batch (all
 ascent steps + the final consistency-loss pass), data already resident in HBM.  Prints ONE JSON line:
-metric / value (whole-job augmented images per second) / roofline of the dominant kernel (HIP events on the
-launch stream, over the timed region) / cpu_baseline (the CPU oracle, bounded sample, rank 0 at N=1 only).
+metric / value (whole-job augmented images per second) / ms_per_step.  A plain run sets up, warms up, times the K
+steps and prints that line, nothing else.  --full adds the roofline of the dominant kernel (HIP events on the
+launch stream, over the timed region), the secondary legs and configs, and cpu_baseline (the CPU oracle, bounded
+sample, rank 0 at N=1 only).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy; the
+inputs are seeded and the timed solver runs in its deterministic mode (solver.deterministic: bit-reproducible run to
+run), so two builds run with the same arguments can be compared output for output.
 
 Multi-GPU (``torch.distributed.run``): one process per GPU, the batch is sharded (weak scaling: the
 per-GPU batch is the workload's batch), RCCL all-reduces carry scalars only.
@@ -235,9 +239,14 @@ class _ModelTimer(object):
         return sum(a.elapsed_time(b) for a, b in self.pairs)
 
 
-def run_gpu(workload, wl, steps, warmup, rank, world, device):
+def run_gpu(workload, wl, steps, warmup, rank, world, device, full=False, dump=False, deterministic=False):
     """K timed steps of one workload.  Returns (max-over-ranks seconds, roofline of the dominant entry, breakdown,
-    extras: model / path split of a step, per-rank step times and collectives per step when sharded)."""
+    extras: model / path split of a step, per-rank step times and collectives per step when sharded; with `dump` also
+    `outputs`: what the last timed step handed its caller, on the host).  Without `full` the steps are warmed up and timed
+    and nothing else runs: no instrumented step, no further leg (roofline and breakdown are None).  `deterministic`: the
+    timed solver runs in its bit-reproducible mode (solver.deterministic), so that the same arguments give the same results
+    in every run -- the default mode's float-atomic flush of the window scatter adds in arrival order, and the ascent steps
+    carry those last-bit differences into every output."""
     import torch.distributed as dist
     from advchain_amd import _lib
     pg = dist.group.WORLD if (world > 1 or FORCE_PG) else None
@@ -246,6 +255,7 @@ def run_gpu(workload, wl, steps, warmup, rank, world, device):
     data = torch.rand(wl["batch"], 1, *wl["dims"], device=device)
     model = make_model(sd).to(device)
     solver = build_solver(wl, device, pg)
+    solver.deterministic = bool(deterministic)
     kw = solver_kwargs(wl, device)
 
     import contextlib
@@ -283,33 +293,37 @@ def run_gpu(workload, wl, steps, warmup, rank, world, device):
         finally:
             solver.hip_graph = graphed
             _ops.COMPOSITE = composite
-    # warm-up; one warm-up step is instrumented on every entry point to find the dominant kernel -- after one cold step of
-    # its own (first launches include code-object loading and would be booked to whichever entry runs first).  With
-    # solver.hip_graph the warm-up also holds the calls that record the launch plan and the capture (at least 5 steps).
-    dominant = None
-    with ordinary():
-        step()
-        torch.cuda.synchronize()
-        lib.records = []
-        with lib.timed():
+    # warm-up.  With solver.hip_graph it also holds the calls that record the launch plan and the capture (at least 5 steps).
+    dominant, breakdown = None, None
+    if full:
+        # one warm-up step is instrumented on every entry point to find the dominant kernel -- after one cold step of its
+        # own (first launches include code-object loading and would be booked to whichever entry runs first)
+        with ordinary():
             step()
-        torch.cuda.synchronize()
-    abi_calls = len(lib.records)           # C-ABI calls of one step on the ordinary path as the product dispatches it
-    with ordinary(separate_entries=True):
-        lib.records = []
-        with lib.timed():
-            step()
-        torch.cuda.synchronize()
-    tot = {}
-    for name, a, e0, e1 in lib.records:
-        if algorithmic_bytes(name, a) is None:
-            continue
-        tot[name] = tot.get(name, 0.0) + e0.elapsed_time(e1)
-    dominant = max(tot, key=tot.get) if tot else None
-    breakdown = {k.replace("advchain_", ""): round(v, 3) for k, v in sorted(tot.items(), key=lambda kv: -kv[1])}
-    for i in range(max(warmup - 1, 5 if graphed else 0)):
+            torch.cuda.synchronize()
+            lib.records = []
+            with lib.timed():
+                step()
+            torch.cuda.synchronize()
+        abi_calls = len(lib.records)           # C-ABI calls of one step on the ordinary path as the product dispatches it
+        with ordinary(separate_entries=True):
+            lib.records = []
+            with lib.timed():
+                step()
+            torch.cuda.synchronize()
+        tot = {}
+        for name, a, e0, e1 in lib.records:
+            if algorithmic_bytes(name, a) is None:
+                continue
+            tot[name] = tot.get(name, 0.0) + e0.elapsed_time(e1)
+        dominant = max(tot, key=tot.get) if tot else None
+        breakdown = {k.replace("advchain_", ""): round(v, 3) for k, v in sorted(tot.items(), key=lambda kv: -kv[1])}
+        n_warm = max(warmup - 1, 5 if graphed else 0)
+    else:
+        n_warm = max(warmup, 5 if graphed else 1)      # (at least one: the first call loads code objects, MIOpen picks its convolutions)
+    for i in range(n_warm):
         step()
-    # timed region: exactly K steps between barrier+sync; only the dominant entry point carries events.  The cyclic
+    # timed region: exactly K steps between barrier+sync; with --full the dominant entry point carries events.  The cyclic
     # garbage collector is parked for it, as timeit does: one generation-2 pass (~40-60 ms with torch loaded) would
     # otherwise land inside a 20-step run at random and move the result by 15 %.
     import gc
@@ -327,54 +341,59 @@ def run_gpu(workload, wl, steps, warmup, rank, world, device):
     stats0 = dict(solver.graph_stats)
     from advchain_amd import ops as _ops_mod
     nsteps0 = dict(_ops_mod.NSTEPS_STATS)
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]      # one event per step boundary (GPU-side span of a step)
+    # --full: one event per step boundary (GPU-side span of a step)
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)] if full else None
     sync()
     t0 = time.perf_counter()
     # ordinary path: one call in five of the dominant entry carries an event pair (every call of a chain entry: it is 8+
     # launches); replayed graphs: nothing can be instrumented inside -- the roofline comes from ordinary steps afterwards
     with lib.timed([dominant] if (dominant and not graphed) else [], every=1 if dominant in CHAIN_ENTRIES else 5):
-        marks[0].record()
+        if full:
+            marks[0].record()
         for i in range(steps):
-            step()
-            marks[i + 1].record()
+            loss = step()
+            if full:
+                marks[i + 1].record()
     sync()
     elapsed = time.perf_counter() - t0
     gc.enable()
-    extras = {}
+    extras = {"outputs": step_outputs(solver, loss)} if dump else {}
     if sd == 3:
         # 3D chains are enqueued with a guessed squaring count (ops._DemonsField: no host read in front of them); a guess
         # that proves wrong enqueues the chain a second time -- how often that happened in the timed region
         extras["step_count_guesses"] = {k: _ops_mod.NSTEPS_STATS[k] - nsteps0[k] for k in ("chains", "respeculated")}
-    # GPU-side span of the timed steps: first to last boundary event on the launch stream.  Host-bound steps show up as
-    # ms_per_step well above it only at the ends of the region; INSIDE it the two agree by construction, so the honest
-    # host-boundness figure is the comparison with the ordinary path below (`ordinary_ms_per_step`) and with rocprof's
-    # kernel-busy time (profiles/)
-    extras["gpu_span_ms_per_step"] = round(marks[0].elapsed_time(marks[-1]) / steps, 3)
-    per = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(steps))
-    extras["gpu_span_ms_by_step"] = {"min": round(per[0], 3), "median": round(per[len(per) // 2], 3), "max": round(per[-1], 3),
-                                     "first": [round(marks[i].elapsed_time(marks[i + 1]), 3) for i in range(min(steps, 6))]}
-    # kernel-busy time and launches per step: the sum of kernel durations of the rocprofv3 kernel trace of THIS command
-    # (tools/profile_bench.sh -> profiles/rNN/per_call_summary.txt, newest round that holds the workload), not an
-    # in-process estimate -- a replayed graph carries no per-kernel events.  host_gap = ms_per_step - gpu_busy
-    # (round 6: measured in this run -- torch.profiler's kernel records over further calls after the timed region; the
-    # committed rocprofv3 summary of the same command only where the profiler is not usable)
-    # (one rank only: a profiler that fails on ONE rank of a sharded run would leave the ranks with different numbers of steps,
-    # i.e. with collectives that no longer pair up)
-    busy = None if (PROFILING_RUN or world > 1) else traced_busy(step, sync)
-    if busy is not None and len(busy) == 1:
-        extras["gpu_busy_trace"] = busy[0]
-        busy = None
-    if busy is None:
-        busy = profiled_busy(workload)
-    if busy is not None:
-        extras["gpu_busy_ms_per_step"], extras["launches_per_step"], extras["gpu_busy_source"] = busy
-        gap = elapsed / steps * 1e3 - busy[0]
-        extras["host_gap_ms_per_step"] = round(max(gap, 0.0), 3)
-        if gap < 0:
-            # kernel-busy time comes from two FURTHER calls under the profiler (kernels traced one by one run ~1 % longer than
-            # in the timed, untraced steps): busy > step means "no measurable idle time", not negative idle time
-            extras["host_gap_raw_ms_per_step"] = round(gap, 3)
-    extras["abi_calls_per_step"] = abi_calls
+    roof = None
+    if full:
+        # GPU-side span of the timed steps: first to last boundary event on the launch stream.  Host-bound steps show up as
+        # ms_per_step well above it only at the ends of the region; INSIDE it the two agree by construction, so the honest
+        # host-boundness figure is the comparison with the ordinary path below (`ordinary_ms_per_step`) and with rocprof's
+        # kernel-busy time (profiles/)
+        extras["gpu_span_ms_per_step"] = round(marks[0].elapsed_time(marks[-1]) / steps, 3)
+        per = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(steps))
+        extras["gpu_span_ms_by_step"] = {"min": round(per[0], 3), "median": round(per[len(per) // 2], 3), "max": round(per[-1], 3),
+                                         "first": [round(marks[i].elapsed_time(marks[i + 1]), 3) for i in range(min(steps, 6))]}
+        # kernel-busy time and launches per step: the sum of kernel durations of the rocprofv3 kernel trace of THIS command
+        # (tools/profile_bench.sh -> profiles/rNN/per_call_summary.txt, newest round that holds the workload), not an
+        # in-process estimate -- a replayed graph carries no per-kernel events.  host_gap = ms_per_step - gpu_busy
+        # (round 6: measured in this run -- torch.profiler's kernel records over further calls after the timed region; the
+        # committed rocprofv3 summary of the same command only where the profiler is not usable)
+        # (one rank only: a profiler that fails on ONE rank of a sharded run would leave the ranks with different numbers of steps,
+        # i.e. with collectives that no longer pair up)
+        busy = None if (PROFILING_RUN or world > 1) else traced_busy(step, sync)
+        if busy is not None and len(busy) == 1:
+            extras["gpu_busy_trace"] = busy[0]
+            busy = None
+        if busy is None:
+            busy = profiled_busy(workload)
+        if busy is not None:
+            extras["gpu_busy_ms_per_step"], extras["launches_per_step"], extras["gpu_busy_source"] = busy
+            gap = elapsed / steps * 1e3 - busy[0]
+            extras["host_gap_ms_per_step"] = round(max(gap, 0.0), 3)
+            if gap < 0:
+                # kernel-busy time comes from two FURTHER calls under the profiler (kernels traced one by one run ~1 % longer than
+                # in the timed, untraced steps): busy > step means "no measurable idle time", not negative idle time
+                extras["host_gap_raw_ms_per_step"] = round(gap, 3)
+        extras["abi_calls_per_step"] = abi_calls
     if graphed:
         st = solver.graph_stats
         extras["hip_graph"] = {"replays": st["replays"] - stats0["replays"], "violations": st["violations"] - stats0["violations"],
@@ -386,152 +405,161 @@ def run_gpu(workload, wl, steps, warmup, rank, world, device):
             extras["hip_graph"]["violated_bounds"] = viol[:8]
         if extras["hip_graph"]["replays"] == 0:
             graphed = False                 # (nothing was replayed -- the anatomy ladder, a capture that failed: the ordinary path was timed)
-    k_ord = 0
-    if graphed and not PROFILING_RUN:
-        # the same steps dispatched launch by launch (what the product does without hip_graph), for comparison
-        k_ord = max(3, min(steps, 10))
-        with ordinary():
-            step()
-            sync()
-            t1 = time.perf_counter()
-            for _ in range(k_ord):
+    if full:
+        k_ord = 0
+        if graphed and not PROFILING_RUN:
+            # the same steps dispatched launch by launch (what the product does without hip_graph), for comparison
+            k_ord = max(3, min(steps, 10))
+            with ordinary():
                 step()
-            sync()
-            extras["ordinary_ms_per_step"] = round((time.perf_counter() - t1) / k_ord * 1e3, 3)
-    if (not graphed) and (sd == 2 or wl.get("anatomy")) and pg is None and REPLAY_LEG and not PROFILING_RUN:
-        # the same workload with the ascent loop of a call replayed from a hipGraph (solver.hip_graph=True: opt-in in the
-        # product).  A solver of its own: recorded calls, capture, then K timed replays
-        rs = build_solver(wl, device, None, hip_graph=True)
-
-        def rstep():
-            with contextlib.redirect_stdout(io.StringIO()):
-                return rs.adversarial_training(data=data, model=model, **kw)
-        for _ in range(int(rs.hip_graph_record_calls) + 3):
-            rstep()
-        k_rep = max(3, min(steps, 20))
-        r0 = dict(rs.graph_stats)
-        sync()
-        t1 = time.perf_counter()
-        for _ in range(k_rep):
-            rstep()
-        sync()
-        extras["replayed_ms_per_step"] = round((time.perf_counter() - t1) / k_rep * 1e3, 3)
-        extras["replayed"] = {"steps": k_rep, "replays": rs.graph_stats["replays"] - r0["replays"],
-                              "violations": rs.graph_stats["violations"] - r0["violations"], "captures": rs.graph_stats["captures"],
-                              "note": "solver.hip_graph=True (opt-in): prediction + ascent steps of a call as ONE hipGraph replay, the "
-                                      "final pass dispatched behind it; `value` / `ms_per_step` are the DEFAULT path (launch by launch)"}
-        viol = [v for rec in rs._graphs.values() for v in rec["plan"].violated]
-        if viol:
-            extras["replayed"]["violated_bounds"] = viol[-8:]
-        del rs
-    if workload in DETERMINISTIC_LEG and world == 1 and pg is None and not PROFILING_RUN:
-        # the same steps with solver.deterministic = True (ordinary path): the window scatter's float-atomic flush replaced by its
-        # 64-bit fixed-point twin (bit-reproducible run to run) -- what the mode costs on the workloads that reach that kernel
-        from advchain_amd import ops as _ops_det
-        ds = build_solver(wl, device, None, hip_graph=False)
-        ds.deterministic = True
-
-        def dstep():
-            with contextlib.redirect_stdout(io.StringIO()):
-                return ds.adversarial_training(data=data, model=model, **kw)
-        try:
-            for _ in range(2):
-                dstep()
-            k_det = max(3, min(steps, 10))
-            sync()
-            t1 = time.perf_counter()
-            for _ in range(k_det):
-                dstep()
-            sync()
-            extras["deterministic_ms_per_step"] = round((time.perf_counter() - t1) / k_det * 1e3, 3)
-        finally:
-            _ops_det.set_deterministic(False)
-        del ds
-    if workload == "cfg2" and world == 1 and pg is None and not PROFILING_RUN:
-        # BASELINE config 2 says "bf16": the USER MODEL under torch.autocast(bfloat16) -- what a mixed-precision training loop
-        # hands the solver -- with the augmentation path in fp32 as the reference's own F.grid_sample is under autocast (it is
-        # on autocast's fp32 list).  A secondary line: the headline stays the fp32 model (the 1e-4 parity contract is fp32)
-        class _Bf16Model(torch.nn.Module):
-            def __init__(self, inner):
-                super().__init__()
-                self.inner = inner
-
-            def forward(self, x):
-                with torch.autocast("cuda", dtype=torch.bfloat16):
-                    y = self.inner(x)
-                return y.float()
-        bm = _Bf16Model(model)
-        bs = build_solver(wl, device, None, hip_graph=False)
-
-        def bstep():
-            with contextlib.redirect_stdout(io.StringIO()):
-                return bs.adversarial_training(data=data, model=bm, **kw)
-        try:
-            for _ in range(3):
-                bstep()
-            k_bf = max(3, min(steps, 10))
-            sync()
-            t1 = time.perf_counter()
-            for _ in range(k_bf):
-                bstep()
-            sync()
-            extras["model_bf16_autocast_ms_per_step"] = round((time.perf_counter() - t1) / k_bf * 1e3, 3)
-        except Exception as exc:        # (a secondary line must not take the headline down with it)
-            extras["model_bf16_autocast_error"] = "%s: %s" % (type(exc).__name__, str(exc)[:200])
-        del bs, bm
-    if not PROFILING_RUN and dominant and not lib.records:
-        # nothing in the timed region could carry the dominant entry's events (a replayed graph makes no C-ABI call; the
-        # composite DemonsCompose entries hold the chain inside one call): the same launches, enqueued entry by entry
-        k_ord = max(3, min(steps, 10))
-        with ordinary(separate_entries=True):
-            step()
-            sync()
-            with lib.timed([dominant], every=1 if dominant in CHAIN_ENTRIES else 5):
+                sync()
+                t1 = time.perf_counter()
                 for _ in range(k_ord):
                     step()
+                sync()
+                extras["ordinary_ms_per_step"] = round((time.perf_counter() - t1) / k_ord * 1e3, 3)
+        if (not graphed) and (sd == 2 or wl.get("anatomy")) and pg is None and REPLAY_LEG and not PROFILING_RUN:
+            # the same workload with the ascent loop of a call replayed from a hipGraph (solver.hip_graph=True: opt-in in the
+            # product).  A solver of its own: recorded calls, capture, then K timed replays
+            rs = build_solver(wl, device, None, hip_graph=True)
+            rs.deterministic = bool(deterministic)
+
+            def rstep():
+                with contextlib.redirect_stdout(io.StringIO()):
+                    return rs.adversarial_training(data=data, model=model, **kw)
+            for _ in range(int(rs.hip_graph_record_calls) + 3):
+                rstep()
+            k_rep = max(3, min(steps, 20))
+            r0 = dict(rs.graph_stats)
             sync()
-        extras["roofline_steps"] = k_ord
+            t1 = time.perf_counter()
+            for _ in range(k_rep):
+                rstep()
+            sync()
+            extras["replayed_ms_per_step"] = round((time.perf_counter() - t1) / k_rep * 1e3, 3)
+            extras["replayed"] = {"steps": k_rep, "replays": rs.graph_stats["replays"] - r0["replays"],
+                                  "violations": rs.graph_stats["violations"] - r0["violations"], "captures": rs.graph_stats["captures"],
+                                  "note": "solver.hip_graph=True (opt-in): prediction + ascent steps of a call as ONE hipGraph replay, the "
+                                          "final pass dispatched behind it; `value` / `ms_per_step` are the DEFAULT path (launch by launch)"}
+            viol = [v for rec in rs._graphs.values() for v in rec["plan"].violated]
+            if viol:
+                extras["replayed"]["violated_bounds"] = viol[-8:]
+            del rs
+        if workload in DETERMINISTIC_LEG and world == 1 and pg is None and not PROFILING_RUN:
+            # the same steps in the other mode (ordinary path): solver.deterministic = True replaces the window scatter's
+            # float-atomic flush by its 64-bit fixed-point twin (bit-reproducible run to run) -- what the mode costs on the
+            # workloads that reach that kernel
+            from advchain_amd import ops as _ops_det
+            ds = build_solver(wl, device, None, hip_graph=False)
+            ds.deterministic = not deterministic
+
+            def dstep():
+                with contextlib.redirect_stdout(io.StringIO()):
+                    return ds.adversarial_training(data=data, model=model, **kw)
+            try:
+                for _ in range(2):
+                    dstep()
+                k_det = max(3, min(steps, 10))
+                sync()
+                t1 = time.perf_counter()
+                for _ in range(k_det):
+                    dstep()
+                sync()
+                other_ms = round((time.perf_counter() - t1) / k_det * 1e3, 3)
+                if deterministic:       # (the timed steps were the deterministic mode: the leg is the float-atomic flush)
+                    extras["deterministic_ms_per_step"] = round(elapsed / steps * 1e3, 3)
+                    extras["float_atomic_ms_per_step"] = other_ms
+                else:
+                    extras["deterministic_ms_per_step"] = other_ms
+            finally:
+                _ops_det.set_deterministic(False)
+            del ds
+        if workload == "cfg2" and world == 1 and pg is None and not PROFILING_RUN:
+            # BASELINE config 2 says "bf16": the USER MODEL under torch.autocast(bfloat16) -- what a mixed-precision training loop
+            # hands the solver -- with the augmentation path in fp32 as the reference's own F.grid_sample is under autocast (it is
+            # on autocast's fp32 list).  A secondary line: the headline stays the fp32 model (the 1e-4 parity contract is fp32)
+            class _Bf16Model(torch.nn.Module):
+                def __init__(self, inner):
+                    super().__init__()
+                    self.inner = inner
+
+                def forward(self, x):
+                    with torch.autocast("cuda", dtype=torch.bfloat16):
+                        y = self.inner(x)
+                    return y.float()
+            bm = _Bf16Model(model)
+            bs = build_solver(wl, device, None, hip_graph=False)
+            bs.deterministic = bool(deterministic)
+
+            def bstep():
+                with contextlib.redirect_stdout(io.StringIO()):
+                    return bs.adversarial_training(data=data, model=bm, **kw)
+            try:
+                for _ in range(3):
+                    bstep()
+                k_bf = max(3, min(steps, 10))
+                sync()
+                t1 = time.perf_counter()
+                for _ in range(k_bf):
+                    bstep()
+                sync()
+                extras["model_bf16_autocast_ms_per_step"] = round((time.perf_counter() - t1) / k_bf * 1e3, 3)
+            except Exception as exc:        # (a secondary line must not take the headline down with it)
+                extras["model_bf16_autocast_error"] = "%s: %s" % (type(exc).__name__, str(exc)[:200])
+            del bs, bm
+        if not PROFILING_RUN and dominant and not lib.records:
+            # nothing in the timed region could carry the dominant entry's events (a replayed graph makes no C-ABI call; the
+            # composite DemonsCompose entries hold the chain inside one call): the same launches, enqueued entry by entry
+            k_ord = max(3, min(steps, 10))
+            with ordinary(separate_entries=True):
+                step()
+                sync()
+                with lib.timed([dominant], every=1 if dominant in CHAIN_ENTRIES else 5):
+                    for _ in range(k_ord):
+                        step()
+                sync()
+            extras["roofline_steps"] = k_ord
     if world > 1 or FORCE_PG:
         dist.all_reduce = orig_all_reduce
         extras["all_reduces_per_step"] = round(n_coll[0] / float(steps), 2)
-    # model / path split: an instrumented pass of a few steps after the timed region (events around the model's forward
-    # and backward calls only; the solver's own kernels carry none)
-    k_split = 0 if PROFILING_RUN else max(1, min(steps, 5))       # (a profiling run holds the timed workload and nothing else)
-    with ordinary(), _ModelTimer(solver) as mt:        # (the timer wraps the Python-side model calls: ordinary steps)
-        for _ in range(k_split):
-            step()
-    model_ms = mt.total_ms() / max(k_split, 1)
+    if full:
+        # model / path split: an instrumented pass of a few steps after the timed region (events around the model's forward
+        # and backward calls only; the solver's own kernels carry none)
+        k_split = 0 if PROFILING_RUN else max(1, min(steps, 5))       # (a profiling run holds the timed workload and nothing else)
+        with ordinary(), _ModelTimer(solver) as mt:        # (the timer wraps the Python-side model calls: ordinary steps)
+            for _ in range(k_split):
+                step()
+        model_ms = mt.total_ms() / max(k_split, 1)
+        if k_split:
+            extras["model_ms_per_step"] = round(model_ms, 3)
+            extras["path_ms_per_step"] = round(elapsed / steps * 1e3 - model_ms, 3)
+        extras["model_split_note"] = ("model = HIP-event time of the user model's forward calls and input-gradient backward calls "
+                                      "(stock MIOpen / rocBLAS kernels) per adversarial_training call, measured over %d further "
+                                      "steps after the timed region; path = ms_per_step - model" % k_split)
+        if dominant and lib.records:
+            durs, bts, nl = [], [], 0
+            for name, a, e0, e1 in lib.records:
+                durs.append(e0.elapsed_time(e1) * 1e-3)
+                bts.append(algorithmic_bytes(name, a))
+                nl += launches_in(name, a)
+            # per LAUNCH of the dominant kernel: a chain entry holds n squarings between its two events
+            avg_t = sum(durs) / nl
+            avg_b = sum(bts) / nl
+            achieved = avg_b / avg_t / 1e9
+            dominant = CHAIN_ENTRIES.get(dominant, (dominant,))[0]
+            traffic, source = profiled_traffic(workload, dominant)
+            durs = [0] * nl
+            roof = {"timed_in": ("%d steps dispatched entry by entry after the timed region (a replayed graph / a composite C entry "
+                                 "cannot carry the events of one entry inside it)" % extras.pop("roofline_steps")) if "roofline_steps" in extras
+                    else "the timed region",
+                    "bound": "hbm", "kernel": dominant.replace("advchain_", ""), "achieved": round(achieved, 1),
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                    "traffic": traffic, "traffic_unit": "bytes/launch", "traffic_source": source,
+                    "launches": len(durs), "avg_launch_us": round(avg_t * 1e6, 2),
+                    "algorithmic_bytes_per_launch": int(avg_b)}
     from advchain_amd import ops as _ops
     if _ops.FUSE_STATS["chains"]:
         extras["fused_chain_refusals"] = "%d of %d" % (_ops.FUSE_STATS["refused"], _ops.FUSE_STATS["chains"])
-    if k_split:
-        extras["model_ms_per_step"] = round(model_ms, 3)
-        extras["path_ms_per_step"] = round(elapsed / steps * 1e3 - model_ms, 3)
-    extras["model_split_note"] = ("model = HIP-event time of the user model's forward calls and input-gradient backward calls "
-                                  "(stock MIOpen / rocBLAS kernels) per adversarial_training call, measured over %d further "
-                                  "steps after the timed region; path = ms_per_step - model" % k_split)
-    roof = None
-    if dominant and lib.records:
-        durs, bts, nl = [], [], 0
-        for name, a, e0, e1 in lib.records:
-            durs.append(e0.elapsed_time(e1) * 1e-3)
-            bts.append(algorithmic_bytes(name, a))
-            nl += launches_in(name, a)
-        # per LAUNCH of the dominant kernel: a chain entry holds n squarings between its two events
-        avg_t = sum(durs) / nl
-        avg_b = sum(bts) / nl
-        achieved = avg_b / avg_t / 1e9
-        dominant = CHAIN_ENTRIES.get(dominant, (dominant,))[0]
-        traffic, source = profiled_traffic(workload, dominant)
-        durs = [0] * nl
-        roof = {"timed_in": ("%d steps dispatched entry by entry after the timed region (a replayed graph / a composite C entry "
-                             "cannot carry the events of one entry inside it)" % extras.pop("roofline_steps")) if "roofline_steps" in extras
-                else "the timed region",
-                "bound": "hbm", "kernel": dominant.replace("advchain_", ""), "achieved": round(achieved, 1),
-                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                "traffic": traffic, "traffic_unit": "bytes/launch", "traffic_source": source,
-                "launches": len(durs), "avg_launch_us": round(avg_t * 1e6, 2),
-                "algorithmic_bytes_per_launch": int(avg_b)}
     extras["solver_calls_in_process"] = n_calls[0]      # (per-call figures of a rocprof summary of this command divide by this)
     if solver.graph_stats["violations"]:              # (each ran its ascent loop a second time, the ordinary way)
         extras["ascent_loops_run_twice"] = solver.graph_stats["violations"]
@@ -541,6 +569,37 @@ def run_gpu(workload, wl, steps, warmup, rank, world, device):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     return elapsed, roof, breakdown, extras
+
+
+DUMP_MAX_ELEMS = 1 << 20     # per array: at most 9 arrays (loss, 4 solver outputs, 4 transforms) stay under 64 MB in all
+
+
+def step_outputs(solver, loss):
+    """What one adversarial_training call hands its caller -- the returned loss (float64), the solver's adversarial data,
+    predictions and the transforms' parameters (float32) -- copied to the host.  An array of more than DUMP_MAX_ELEMS
+    elements is kept as a fixed, seeded sample of its flattened elements (the same positions for the same shape)."""
+    import numpy as np
+    out = {"loss": np.asarray(float(torch.as_tensor(loss).detach()), dtype=np.float64)}
+    named = [(nm, getattr(solver, nm, None)) for nm in ("adv_data", "adv_predict", "warped_back_adv_output", "init_output")]
+    named += [("param_%d_%s" % (i, t.get_name()), t.param) for i, t in enumerate(solver.chain_of_transforms)]
+    for nm, t in named:
+        if not torch.is_tensor(t):
+            continue
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            pick = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_MAX_ELEMS, replace=False))
+            flat = flat[torch.from_numpy(pick).to(flat.device)]
+            out[nm] = flat.float().cpu().numpy()
+        else:
+            out[nm] = t.detach().float().cpu().numpy()
+    return out
+
+
+def write_outputs(outdir, outputs):
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for nm, a in outputs.items():
+        np.save(os.path.join(outdir, nm + ".npy"), a)
 
 
 def traced_busy(step, sync, calls=2):
@@ -885,6 +944,16 @@ def main():
     ap.add_argument("--only-workload", action="store_true",
                     help="profiling runs: the chosen workload and nothing else (no secondary configs, no north-star "
                          "kernel pair, no CPU baseline)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the instrumented warm-up step (roofline, per-entry breakdown), "
+                         "GPU span and busy time, model / path split, the replayed, float-atomic-mode and bf16-model legs, the 3D "
+                         "configs, the north-star kernel pair and the CPU baseline.  Default: set up, warm up, time the steps, "
+                         "print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (the returned loss, the solver's adversarial data and "
+                         "predictions, the transforms' parameters) as DIR/<name>.npy; arrays of more than %d elements as a "
+                         "fixed, seeded sample.  Inputs are seeded and the timed solver runs in its deterministic mode: the "
+                         "same arguments give the same outputs in every run" % DUMP_MAX_ELEMS)
     args = ap.parse_args()
     global PROFILING_RUN, HIP_GRAPH, SHARDED_GRAPH, REPLAY_LEG
     PROFILING_RUN = bool(args.only_workload)
@@ -894,6 +963,10 @@ def main():
     stub = os.environ.get("ADVCHAIN_BENCH_STUB") == "1"
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if stub and args.dump_outputs:
+        raise SystemExit("bench.py: --dump-outputs needs the GPU path (the stub computes nothing)")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_spawn(args, stub))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -934,8 +1007,12 @@ def main():
     if stub:
         elapsed, roof, breakdown, extras = run_stub(args.steps, args.warmup, rank, world)
     else:
-        elapsed, roof, breakdown, extras = run_gpu(args.workload, wl, args.steps, args.warmup, rank, world, device)
+        elapsed, roof, breakdown, extras = run_gpu(args.workload, wl, args.steps, args.warmup, rank, world, device,
+                                                   full=args.full, dump=bool(args.dump_outputs) and rank == 0,
+                                                   deterministic=True)
     if rank == 0:
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, extras.pop("outputs"))
         rec = result_record(args.workload, wl, world, args.steps, args.warmup, elapsed, roof, breakdown, extras)
         out = {
             "metric": "augmented images/sec (N adv steps, chain=noise+bias+morph+affine)",
@@ -947,12 +1024,13 @@ def main():
                        "dispatch": "hipGraph replay of the ascent loop (solver.hip_graph)" if (HIP_GRAPH and (world == 1 or SHARDED_GRAPH) and not stub
                                                                                                   and len(wl["dims"]) == 2)
                        else "launch by launch",
+                       "deterministic": not stub,
                        "segmentation_net": "Conv%dd(1,4,3,1,1) eval (as adv_compose_solver.py:593)" % len(wl["dims"])},
-            "roofline": roof,
-            "kernel_time_ms_first_step": breakdown,
         }
+        if args.full:
+            out.update({"roofline": roof, "kernel_time_ms_first_step": breakdown})
         out.update(extras)      # model_ms_per_step / path_ms_per_step (+ rank_ms_per_step, all_reduces_per_step when sharded)
-        if world == 1 and not stub:
+        if world == 1 and not stub and args.full:
             if not (args.no_secondary or args.only_workload):
                 # the 3D configs of BASELINE.json, timed by the same code on the same device (fewer steps: they are
                 # 2-15x longer); `value` above stays the headline workload's
@@ -962,7 +1040,7 @@ def main():
                         continue
                     w2 = WORKLOADS[name]
                     k2 = max(3, min(args.steps, 5))
-                    e2, r2, b2, x2 = run_gpu(name, w2, k2, 1, 0, 1, device)
+                    e2, r2, b2, x2 = run_gpu(name, w2, k2, 1, 0, 1, device, full=True, deterministic=True)
                     other[name] = result_record(name, w2, 1, k2, 1, e2, r2, b2, x2)
                     other[name].pop("kernel_time_ms_first_step")
                 out["other_workloads"] = other

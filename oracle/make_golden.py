@@ -1009,6 +1009,22 @@ def g9_utils(aug):
     meta["nrrd"]["loaded_sum"] = float(crop.astype(np.float64).sum())
     out["meta"] = meta
     save("g9_utils", out)
+    nrrd_slice0(blob, end, sizes, dt, payload)
+
+
+def nrrd_slice0(blob, end, sizes, dt, payload):
+    """tests/golden/g9_cardiac_slice0.nrrd: the example volume's header with its slowest size set to 1 and a raw encoding, and
+    slice 0 of its decoded payload (the slice load_image_label reads) -- what the G9 test decodes, so that it needs nothing
+    outside the repository."""
+    def line(ln):
+        key = ln.split(":", 1)[0].strip().lower()
+        if key == "sizes":
+            return "sizes: " + " ".join(str(s) for s in sizes[:-1] + [1])
+        return "encoding: raw" if key == "encoding" else ln
+    lines = [line(ln) for ln in blob[:end].decode("ascii").split("\n")]
+    n = int(np.prod(sizes[:-1])) * np.dtype(dt).itemsize
+    with open(os.path.join(OUT, "g9_cardiac_slice0.nrrd"), "wb") as f:
+        f.write("\n".join(lines).encode("ascii") + b"\n\n" + payload[:n])
 
 
 # ----------------------------------------------------------------------------- G10

@@ -102,8 +102,9 @@ def test_nrrd_reader_and_image_loading(tmp_path):
 
 def test_caller_utilities_match_the_reference_golden():
     """G9: random_chain draw for draw under fixed seeds (incl. the in-place shuffle of its
-    arguments), rescale_intensity, and -- when the reference checkout is mounted -- the NRRD reader and load_image_label
-    on the reference's own example volume against an independent decode of that file."""
+    arguments), rescale_intensity, and the NRRD reader and load_image_label on slice 0 of the reference's own example
+    volume (tests/golden/g9_cardiac_slice0.nrrd: its header and the raw payload of the slice load_image_label reads)
+    against an independent decode of that file."""
     import os
     import random
     import hashlib
@@ -126,13 +127,13 @@ def test_caller_utilities_match_the_reference_golden():
         assert a == c["alist_after"]
     out = U.rescale_intensity(fx.t("rescale_in").clone(), new_min=-1, new_max=2)
     assert float((out - fx.t("rescale_out")).abs().max()) < 1e-6
-    path = os.path.join(os.environ.get("ADVCHAIN_REFERENCE_ROOT", "/root/reference"), meta["nrrd"]["relative_path"])
-    if not os.path.exists(path):
-        return                      # the reference's data does not travel to the GPU box
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g9_cardiac_slice0.nrrd")
     vol, header = U.read_nrrd(path)
     m = meta["nrrd"]
-    assert list(vol.shape) == m["shape"] and str(vol.dtype) == m["dtype"]
-    assert hashlib.sha256(np.ascontiguousarray(vol).tobytes()).hexdigest() == m["sha256"]
+    assert list(vol.shape) == [1] + m["shape"][1:] and str(vol.dtype) == m["dtype"]
+    assert header["sizes"].split()[:2] == m["header"]["sizes"].split()[:2]
+    assert hashlib.sha256(np.ascontiguousarray(vol).tobytes()).hexdigest() == \
+        "1f95a54c5f28a080bd44ebc27352f757aa564898bd93746ccdfeb76f4798adce"     # slice 0 of the volume's independent decode
     assert np.array_equal(vol[0, 40:56, 60:76], fx.arr("nrrd_slice0_patch"))
     img = U.load_image_label(path, slice_id=0, crop_size=(192, 192))
     assert img.shape == (192, 192) and abs(float(img.astype(np.float64).sum()) - m["loaded_sum"]) < 1e-6 * m["loaded_sum"]

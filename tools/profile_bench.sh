@@ -17,9 +17,9 @@ run() {  # name, command...
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_$name -o $name -- "$@" > "$out/${name}_under_rocprof.log" 2>&1
   cp "$(find /tmp/rp_$name -name "${name}_kernel_stats.csv" | head -1)" "$out/${name}_kernel_stats.csv"
 }
-run cfg2 python $repo/bench.py --steps 10 --warmup 3 --only-workload
-run cfg3 python $repo/bench.py --workload cfg3 --steps 5 --warmup 2 --only-workload
-run cfg5 python $repo/bench.py --workload cfg5 --steps 3 --warmup 1 --only-workload
+run cfg2 python $repo/bench.py --steps 10 --warmup 3 --only-workload --full
+run cfg3 python $repo/bench.py --workload cfg3 --steps 5 --warmup 2 --only-workload --full
+run cfg5 python $repo/bench.py --workload cfg5 --steps 3 --warmup 1 --only-workload --full
 run kb3d python $repo/tools/kernel_bench.py --shape 3d
 # per-call figures: the number of adversarial_training calls the profiled command made is in ITS OWN json line
 # ("solver_calls_in_process"), not assumed here (round 4 divided cfg-5's 5 calls by 4)

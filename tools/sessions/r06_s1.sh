@@ -11,7 +11,7 @@ export ADVCHAIN_PARITY_LOG=$out/parity_levels.txt
 rm -f $ADVCHAIN_PARITY_LOG
 timeout 1500 python -m pytest tests -m gpu -x -q > "$out/pytest_gpu.log" 2>&1
 tail -15 "$out/pytest_gpu.log"
-timeout 900 python bench.py > "$out/bench_default.json" 2> "$out/bench_default.err"
+timeout 900 python bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err"
 tail -c 3000 "$out/bench_default.json"; tail -5 "$out/bench_default.err"
 bash tools/profile_ns_pair.sh $tag > "$out/ns_pair.log" 2>&1
 ADVCHAIN_WIDE_ROWMAX_PASS=1 bash tools/profile_ns_pair.sh ${tag}_rowmaxpass > "$out/ns_pair_rowmaxpass.log" 2>&1

@@ -7,7 +7,7 @@ mkdir -p "$out"
 cd $repo
 timeout 900 python -m pytest tests/test_graph_gpu.py tests/test_dist_gpu.py -m gpu -q -x > "$out/pytest_graph.log" 2>&1
 tail -15 "$out/pytest_graph.log"
-timeout 900 python bench.py --workload cfg5 --no-secondary --no-cpu-baseline > "$out/bench_cfg5.json" 2> "$out/bench_cfg5.err"
+timeout 900 python bench.py --full --workload cfg5 --no-secondary --no-cpu-baseline > "$out/bench_cfg5.json" 2> "$out/bench_cfg5.err"
 tail -3 "$out/bench_cfg5.err"
 python - "$out/bench_cfg5.json" <<'PY'
 import json, sys

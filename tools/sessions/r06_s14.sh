@@ -6,7 +6,7 @@ out=$repo/gpurun_out/r06lad
 mkdir -p "$out"
 cd $repo
 for m in 1.3 1.6; do
-ADVCHAIN_PLAN_MARGIN=$m timeout 900 python bench.py --workload cfg5 --no-secondary --no-cpu-baseline > "$out/bench_cfg5_m$m.json" 2> "$out/bench_cfg5_m$m.err"
+ADVCHAIN_PLAN_MARGIN=$m timeout 900 python bench.py --full --workload cfg5 --no-secondary --no-cpu-baseline > "$out/bench_cfg5_m$m.json" 2> "$out/bench_cfg5_m$m.err"
 python - "$out/bench_cfg5_m$m.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -8,7 +8,7 @@ cd $repo
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -3
 timeout 1500 python -m pytest tests -x -q -m gpu > "$out/pytest_gpu.log" 2>&1
 tail -2 "$out/pytest_gpu.log"
-( time python bench.py > "$out/bench_default.json" 2> "$out/bench_default.err" ) 2>&1 | grep real
+( time python bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err" ) 2>&1 | grep real
 python - "$out/bench_default.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

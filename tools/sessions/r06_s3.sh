@@ -11,8 +11,8 @@ rm -f $ADVCHAIN_PARITY_LOG
 timeout 1500 python -m pytest tests -m gpu -q > "$out/pytest_gpu.log" 2>&1
 tail -8 "$out/pytest_gpu.log"
 for rep in 1 2; do
-timeout 600 python bench.py --no-secondary --no-cpu-baseline --no-replay-leg > "$out/bench_cfg2_$rep.json" 2> "$out/bench_cfg2.err"
-ADVCHAIN_FUSED_UPDATE_OFF=1 timeout 600 python bench.py --no-secondary --no-cpu-baseline --no-replay-leg > "$out/bench_cfg2_unfused_update_$rep.json" 2>/dev/null
+timeout 600 python bench.py --full --no-secondary --no-cpu-baseline --no-replay-leg > "$out/bench_cfg2_$rep.json" 2> "$out/bench_cfg2.err"
+ADVCHAIN_FUSED_UPDATE_OFF=1 timeout 600 python bench.py --full --no-secondary --no-cpu-baseline --no-replay-leg > "$out/bench_cfg2_unfused_update_$rep.json" 2>/dev/null
 python - "$out/bench_cfg2_$rep.json" "$out/bench_cfg2_unfused_update_$rep.json" <<'PY'
 import json, sys
 for p in sys.argv[1:]:

@@ -29,7 +29,7 @@ d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v $w', d['ms_pe
   done
 done | tee "$out/fwd_join_e2e.txt"
 cp /tmp/lib_keep.so $lib
-timeout 600 python bench.py --no-secondary --no-cpu-baseline --no-replay-leg > "$out/bench_cfg2.json" 2>/dev/null
+timeout 600 python bench.py --full --no-secondary --no-cpu-baseline --no-replay-leg > "$out/bench_cfg2.json" 2>/dev/null
 python - "$out/bench_cfg2.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
