@@ -69,6 +69,12 @@ PROTOTYPES = {
     "advchain_consistency_fused_bwd": (_I, [_P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _I, _L, _L, _I, _P, _I, _P]),
     "advchain_consistency_fused_fwd_bf16": (_I, [_P, _P, _P, _P, _P, _L, _L, _I, _P, _P]),
     "advchain_consistency_fused_bwd_bf16": (_I, [_P, _P, _P, _P, _P, _P, _F, _F, _F, _L, _L, _I, _P, _P]),
+    "advchain_seg_loss_workspace": (_L, [_L, _I, _P]),
+    "advchain_ce2d_fwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _L, _L, _P, _F, _P]),
+    "advchain_ce2d_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _L, _L, _P, _F, _P]),
+    "advchain_contour_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _I, _P]),
+    "advchain_contour_bwd": (_I, [_P, _P, _P, _P, _L, _L, _I, _P, _I, _P]),
+    "advchain_one_hot": (_I, [_P, _P, _L, _L, _L, _P]),
 }
 
 class UpdateDesc(ctypes.Structure):

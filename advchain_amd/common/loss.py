@@ -1,4 +1,5 @@
-"""Segmentation-consistency loss (reference: advchain/common/loss.py:8-249).
+"""Segmentation losses (reference: advchain/common/loss.py): the consistency loss (loss.py:8-249) and the supervised
+``contour_loss`` / ``One_Hot`` / ``cross_entropy_2D`` (loss.py:102-220, 252-326, on csrc/seg_loss.hip).
 
 'mse', 'contour' and 'kl' all run in the fused HIP kernels (:func:`advchain_amd.ops.consistency_sums`:
 softmax + mask + squared error + KL sum + 3^d edge stencils in two launches forward, one backward).
@@ -116,3 +117,70 @@ def calc_segmentation_mse_consistency(input, target):
 def calc_segmentation_kl_consistency(input, target):
     return calc_segmentation_consistency(output=input, reference=target, divergence_types=['kl'],
                                          divergence_weights=[1.0], class_weights=None, mask=None)
+
+
+# ---- supervised losses (reference: advchain/common/loss.py:102-220, 252-271, 274-326) ----------------------------------
+
+def _require_gpu(t, name):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ops._lib.AdvchainHipError("%s must be a CUDA/ROCm tensor: the advchain_amd kernels have no CPU path" % name)
+
+
+def contour_loss(input, target, use_gpu=True, ignore_background=True, one_hot_target=True, mask=None,
+                 device=torch.device("cuda")):
+    """Contour loss across object boundaries (loss.py:102-220), same signature.  `use_gpu` and `device` are accepted and
+    ignored: the kernels run on the input's device.  The reference's filters sum over the class axis, so the
+    loss is the Sobel edge energy of u = sum over the object classes of (input_c - target_c), weighted by the mean of m^2 over
+    the first min(#object classes, mask channels) mask channels (its mask[:, :object_classes] slice)."""
+    _require_gpu(input, "input")
+    if input.dim() not in (4, 5):
+        raise NotImplementedError("contour_loss supports 2D (N,C,H,W) and 3D (N,C,D,H,W) input, got %d-D" % input.dim())
+    K = input.size(1)
+    first = 1 if ignore_background else 0
+    oc = K - first
+    if oc < 1:
+        raise ValueError("contour_loss: no object class left (%d classes, ignore_background=%s)" % (K, ignore_background))
+    if mask is not None:
+        _require_gpu(mask, "mask")
+        if input.dim() == 4 and 1 < mask.shape[1] < oc:     # (3D: the reference's conv output has one channel)
+            raise ValueError("mask with %d channels does not broadcast against %d object classes" % (mask.shape[1], oc))
+        if torch.is_grad_enabled() and mask.requires_grad:
+            warnings.warn('advchain_amd: contour_loss treats the mask as a constant (detach it to silence this warning)',
+                          stacklevel=2)
+    return ops.contour_energy(input, target, mask=mask, first_class=first, one_hot_target=one_hot_target)
+
+
+class One_Hot(torch.nn.Module):
+    """Integer labels (N x dims or N x 1 x dims) -> float32 one-hot maps N x depth x dims (loss.py:252-271).  `use_gpu` and
+    `device` are accepted and ignored: the kernel runs on the labels' device.  Out-of-range labels give NaN channels."""
+
+    def __init__(self, depth, use_gpu=True, device=torch.device("cuda")):
+        super(One_Hot, self).__init__()
+        self.depth = depth
+
+    def forward(self, X_in):
+        _require_gpu(X_in, "X_in")
+        if X_in.dim() < 2:
+            raise IndexError("One_Hot takes labels of shape N x dims, got %s" % (tuple(X_in.shape),))
+        lab = X_in.detach()
+        lab = lab if lab.dtype == torch.int64 else lab.long()
+        out = ops.one_hot(lab.reshape(lab.shape[0], -1), self.depth)
+        # the reference's permute(0, -1, 1, ...).squeeze(dim=2): (N, depth, *X.shape[1:]) without a size-1 third axis
+        shape = [X_in.shape[0], self.depth] + list(X_in.shape[1:])
+        if shape[2] == 1:
+            del shape[2]
+        return out.view(shape)
+
+    def __repr__(self):
+        return self.__class__.__name__ + "({})".format(self.depth)
+
+
+def cross_entropy_2D(input, target, weight=None, size_average=True):
+    """Cross entropy on 2D images (loss.py:274-326), same signature.  input: (N,C,H,W) fp32 or bf16 logits; target: (N,H,W)
+    int64 labels (-100 is ignored but still counted in N*H*W) or (N,C,H,W) soft targets; weight: C class weights (tensor, list
+    or array), used as weight / sum(weight) * C; size_average divides by N*H*W.  Returns an fp32 scalar."""
+    _require_gpu(input, "input")
+    if input.dim() != 4:
+        raise ValueError("cross_entropy_2D expects 4-D input (N,C,H,W), got %d-D" % input.dim())
+    _require_gpu(target, "target")
+    return ops.cross_entropy_2d(input, target, weight=weight, size_average=size_average)

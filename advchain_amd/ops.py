@@ -1627,3 +1627,174 @@ def consistency_sums(pred, ref, mask, coef, ref_is_prob=False, want_edges=True):
     if len(coef) == 3:
         coef = coef + (0.0,)
     return _Consistency.apply(pred, ref, mask, coef, bool(ref_is_prob), bool(want_edges))
+
+
+# ---- supervised segmentation losses (csrc/seg_loss.hip) ---------------------------------------------------------------
+
+def _dev_logits(t, name="input"):
+    """fp32 or bf16 (a model under autocast) logits; the kernels read bf16 natively."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.AdvchainHipError("%s must be a CUDA/ROCm tensor: the advchain_amd kernels have no CPU path" % name)
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.AdvchainHipError("%s must be float32 or bfloat16, got %s" % (name, t.dtype))
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _dev_labels(t, name="target"):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.AdvchainHipError("%s must be a CUDA/ROCm tensor: the advchain_amd kernels have no CPU path" % name)
+    if t.dtype != torch.int64:
+        raise RuntimeError("%s: expected labels of scalar type Long (int64), got %s" % (name, t.dtype))
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _seg_workspace(N, dims, device):
+    n = _lib.load().advchain_seg_loss_workspace(N, len(dims), _lib.dims_array(dims))
+    if n < 0:
+        raise ValueError("bad loss shape: N=%d, dims=%s" % (N, tuple(dims)))
+    return torch.empty(max(int(n), 1), device=device, dtype=torch.float32)
+
+
+class _CrossEntropy2D(torch.autograd.Function):
+    """sum over pixels of -log_softmax(x)_y * w_y (labels) or -sum_c w_c t_c log_softmax(x)_c (soft target), over `denom`
+    (advchain/common/loss.py:274-326).  Differentiable w.r.t. the logits and a soft target."""
+
+    @staticmethod
+    def forward(ctx, x, labels, soft, weight, denom):
+        N, K, H, W = x.shape
+        dims = _lib.dims_array((H, W))
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[2]
+        lse = torch.empty((N, H, W), device=x.device, dtype=torch.float32) if need else None
+        ws = _seg_workspace(N, (H, W), x.device)
+        value = torch.empty((), device=x.device, dtype=torch.float32)
+        _lib.check(_lib.load().advchain_ce2d_fwd(_ptr(x), int(x.dtype == torch.bfloat16), _ptr(labels), _ptr(soft), _ptr(weight),
+                                                 _ptr(lse), _ptr(ws), _ptr(value), N, K, dims, float(denom), _stream()),
+                   "ce2d_fwd")
+        if need:
+            ctx.save_for_backward(x, labels, soft, weight, lse)
+        ctx.denom = float(denom)
+        return value
+
+    @staticmethod
+    def backward(ctx, gloss):
+        x, labels, soft, weight, lse = ctx.saved_tensors
+        N, K, H, W = x.shape
+        gs = _dev(gloss.reshape(1), "grad")
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gt = torch.empty_like(soft) if (soft is not None and ctx.needs_input_grad[2]) else None
+        if gx is None and gt is None:
+            return None, None, None, None, None
+        _lib.check(_lib.load().advchain_ce2d_bwd(_ptr(x), int(x.dtype == torch.bfloat16), _ptr(labels), _ptr(soft), _ptr(weight),
+                                                 _ptr(lse), _ptr(gs), _ptr(gx), _ptr(gt), N, K, _lib.dims_array((H, W)),
+                                                 ctx.denom, _stream()), "ce2d_bwd")
+        return gx, None, gt, None, None
+
+
+@_on_tensor_device
+def cross_entropy_2d(x, target, weight=None, size_average=True):
+    """cross_entropy_2D of advchain/common/loss.py:274-326 on the HIP kernels.  x (N,K,H,W) fp32 / bf16 logits; target (N,H,W)
+    int64 labels (-100 ignored) or (N,K,H,W) soft target; weight: K class weights (tensor, list or array) or None.  Returns an
+    fp32 scalar."""
+    x = _dev_logits(x, "input")
+    if x.dim() != 4:
+        raise ValueError("cross_entropy_2D takes 4-D input (N,C,H,W), got %d-D" % x.dim())
+    N, K, H, W = x.shape
+    labels = soft = None
+    if target.dim() == 3:
+        labels = _dev_labels(target, "target")
+        if tuple(labels.shape) != (N, H, W):
+            raise ValueError("label target must be (N,H,W) = %s, got %s" % ((N, H, W), tuple(labels.shape)))
+    elif target.dim() == 4:
+        if not isinstance(target, torch.Tensor) or not target.is_cuda:
+            raise _lib.AdvchainHipError("target must be a CUDA/ROCm tensor: the advchain_amd kernels have no CPU path")
+        soft = _dev(target if target.dtype == torch.float32 else target.float(), "target")
+        if soft.shape != x.shape:
+            raise ValueError("soft target must have the input's shape %s, got %s" % (tuple(x.shape), tuple(soft.shape)))
+    else:
+        raise NotImplementedError("cross_entropy_2D: target must be (N,H,W) labels or (N,C,H,W) soft targets")
+    if weight is not None:
+        if isinstance(weight, torch.Tensor):
+            weight = weight.detach().to(device=x.device, dtype=torch.float32)
+        else:
+            weight = torch.as_tensor(weight, dtype=torch.float32).to(x.device)
+        weight = weight.reshape(-1).contiguous()
+        if weight.numel() != K:
+            raise ValueError("weight must have %d entries, got %d" % (K, weight.numel()))
+    _same_device(x, labels, soft, weight)
+    denom = float(N * H * W) if size_average else 1.0
+    return _CrossEntropy2D.apply(x, labels, soft, weight, denom)
+
+
+class _Contour(torch.autograd.Function):
+    """Edge energy of u = sum_{c in S}(input_c - T_c) (advchain/common/loss.py:102-220, Q14).  Differentiable w.r.t. the
+    prediction and a soft target; the mask is a constant."""
+
+    @staticmethod
+    def forward(ctx, x, labels, soft, mask, first_class):
+        N, K = x.shape[:2]
+        sp = tuple(x.shape[2:])
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[2]
+        R = torch.empty((N, 2) + sp, device=x.device, dtype=torch.float32) if need else None
+        ws = _seg_workspace(N, sp, x.device)
+        value = torch.empty((), device=x.device, dtype=torch.float32)
+        mch = 1 if mask is None else mask.shape[1]
+        _lib.check(_lib.load().advchain_contour_fwd(_ptr(x), _ptr(labels), _ptr(soft), _ptr(mask), _ptr(R), _ptr(ws), _ptr(value),
+                                                    N, K, len(sp), _lib.dims_array(sp), int(first_class), mch, _stream()),
+                   "contour_fwd")
+        if need:
+            ctx.save_for_backward(R)
+        ctx.cfg = (tuple(x.shape), int(first_class), soft is not None)
+        return value
+
+    @staticmethod
+    def backward(ctx, gloss):
+        R, = ctx.saved_tensors
+        shape, first_class, has_soft = ctx.cfg
+        gs = _dev(gloss.reshape(1), "grad")
+        gx = torch.empty(shape, device=R.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        gt = torch.empty(shape, device=R.device, dtype=torch.float32) if (has_soft and ctx.needs_input_grad[2]) else None
+        if gx is None and gt is None:
+            return None, None, None, None, None
+        _lib.check(_lib.load().advchain_contour_bwd(_ptr(R), _ptr(gs), _ptr(gx), _ptr(gt), shape[0], shape[1], len(shape) - 2,
+                                                    _lib.dims_array(shape[2:]), first_class, _stream()), "contour_bwd")
+        return gx, None, gt, None, None
+
+
+@_on_tensor_device
+def contour_energy(x, target, mask=None, first_class=1, one_hot_target=True):
+    """contour_loss of advchain/common/loss.py:102-220 on the HIP kernels.  x (N,K,dims) fp32; target: labels with N*prod(dims)
+    entries (one_hot_target) or a soft target of x's shape; mask (N, 1 or >= K - first_class channels, dims) or None."""
+    x = _dev(x, "input")
+    N, K = x.shape[:2]
+    sp = tuple(x.shape[2:])
+    labels = soft = None
+    if one_hot_target:
+        if not isinstance(target, torch.Tensor) or not target.is_cuda:
+            raise _lib.AdvchainHipError("target must be a CUDA/ROCm tensor: the advchain_amd kernels have no CPU path")
+        labels = target if target.dtype == torch.int64 else target.long()
+        if labels.numel() != N * (x.numel() // max(N * K, 1)):
+            raise ValueError("label target of shape %s does not match the input %s" % (tuple(target.shape), tuple(x.shape)))
+        labels = labels.reshape(N, -1).contiguous()
+    else:
+        soft = _dev(target if target.dtype == torch.float32 else target.float(), "target")
+        if soft.shape != x.shape:
+            raise ValueError("pred size: %s must match target size: %s" % (tuple(x.shape), tuple(soft.shape)))
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
+            raise _lib.AdvchainHipError("mask must be a CUDA/ROCm tensor: the advchain_amd kernels have no CPU path")
+        mask = _dev(mask.detach() if mask.dtype == torch.float32 else mask.detach().float(), "mask")
+        if mask.dim() != x.dim() or mask.shape[0] != N or tuple(mask.shape[2:]) != sp:
+            raise ValueError("mask must be (N, C', %s), got %s" % (sp, tuple(mask.shape)))
+    _same_device(x, labels, soft, mask)
+    return _Contour.apply(x, labels, soft, mask, int(first_class))
+
+
+@_on_tensor_device
+def one_hot(labels, depth):
+    """(N, V) int64 labels -> (N, depth, V) fp32 planar one-hot (advchain/common/loss.py:252-271); NaN for out-of-range labels."""
+    labels = _dev_labels(labels, "labels")
+    N = labels.shape[0]
+    V = labels.numel() // max(N, 1)
+    out = torch.empty((N, int(depth), V), device=labels.device, dtype=torch.float32)
+    _lib.check(_lib.load().advchain_one_hot(_ptr(labels), _ptr(out), N, int(depth), max(V, 1), _stream()), "one_hot")
+    return out

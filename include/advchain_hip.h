@@ -443,6 +443,45 @@ int advchain_consistency_fused_bwd_bf16(const void* pred, const void* ref, const
                                         const float* grad_scale, void* grad_pred, float c_mse, float c_a, float c_b, int64_t N,
                                         int64_t K, int ndim, const int64_t* dims, void* stream);
 
+/* ---- supervised segmentation losses (seg_loss.hip) ---------------------------------------------------------------------
+ * Caller-provided workspace of every forward below: advchain_seg_loss_workspace(N, ndim, dims) floats (one partial per
+ * workgroup); the value is their fixed-order sum over one more workgroup -- no float atomics, bitwise reproducible.
+ * Labels are int64 and only ever compared with class indices (never used as an address).  Returns -1 for bad sizes.      */
+int64_t advchain_seg_loss_workspace(int64_t N, int ndim, const int64_t* dims); /* floats */
+/* replaces: cross_entropy_2D, advchain/common/loss.py:274-326 (F.log_softmax + F.nll_loss(weight, reduction="none") + sum, or
+ *           the soft-target sum -sum_c w_c t_c log p_c).  logits (N,K,H,W) fp32 (logits_bf16 = 0) or bf16 (1, raw 16-bit words);
+ *           exactly one of labels (N,H,W) int64 -- -100 contributes 0, any other label outside [0,K) gives NaN -- and soft
+ *           (N,K,H,W) fp32; weight (K floats, device) or NULL, used as weight / sum(weight) * K; dims = (H, W).
+ *           value[0] = sum over pixels / denom (N*H*W for size_average, else 1).  lse (N*H*W floats: the log-sum-exp per pixel,
+ *           kept for the backward) may be NULL.                                                                               */
+int advchain_ce2d_fwd(const void* logits, int logits_bf16, const int64_t* labels, const float* soft, const float* weight,
+                      float* lse, float* workspace, float* value, int64_t N, int64_t K, const int64_t* dims, float denom,
+                      void* stream);
+/* replaces: the autograd of the call above.  grad_logits (the logits' dtype) = gs / denom (W p_c - w_c t_c) with W = sum_c w_c t_c;
+ *           grad_soft (fp32, soft targets only) = gs / denom * w_c (lse - x_c); either may be NULL (not both);
+ *           gs = *grad_scale (device scalar, NULL = 1).                                                                        */
+int advchain_ce2d_bwd(const void* logits, int logits_bf16, const int64_t* labels, const float* soft, const float* weight,
+                      const float* lse, const float* grad_scale, void* grad_logits, float* grad_soft, int64_t N, int64_t K,
+                      const int64_t* dims, float denom, void* stream);
+/* replaces: contour_loss, advchain/common/loss.py:102-220 (One_Hot of the labels, the Sobel convolutions of the prediction and
+ *           of the target, mask, MSE).  The reference's filters sum over the class axis (Q14), so the loss is the edge energy of
+ *           u = sum_{c >= first_class} (input_c - T_c):  2D 1/2 [mean(w (Sx*u)^2) + mean(w (Sy*u)^2)],
+ *           3D 1/3 [2 mean(w (A*u)^2) + mean(w (B*u)^2)] (A, B as for advchain_consistency_fwd), means over N * voxels,
+ *           w = mean of m^2 over the first min(K - first_class, mask_channels) channels of mask (N, mask_channels, dims) or 1
+ *           (mask NULL; in 2D mask_channels must be 1 or >= K - first_class).  input (N,K,dims) fp32; exactly one of labels
+ *           (N,dims) int64 (T = one-hot; a label outside [0,K) gives NaN) and soft (N,K,dims) fp32; first_class = 1 when
+ *           ignore_background.  R (N,2,dims) = the edge fields weighted for the backward, NULL when none is needed.          */
+int advchain_contour_fwd(const float* input, const int64_t* labels, const float* soft, const float* mask, float* R,
+                         float* workspace, float* value, int64_t N, int64_t K, int ndim, const int64_t* dims, int first_class,
+                         int mask_channels, void* stream);
+/* replaces: the autograd of the call above: grad_input_c = g_u, grad_soft_c = -g_u for c >= first_class, 0 for the other
+ *           class (both (N,K,dims), either may be NULL, not both), g_u = gs / (N * voxels) * adjoint stencils of R.         */
+int advchain_contour_bwd(const float* R, const float* grad_scale, float* grad_input, float* grad_soft, int64_t N, int64_t K,
+                         int ndim, const int64_t* dims, int first_class, void* stream);
+/* replaces: One_Hot(depth).forward, advchain/common/loss.py:252-271 (eye(depth).index_select + permute): labels (N, V) int64 ->
+ *           out (N, depth, V) fp32, planar; a label outside [0, depth) gives a NaN column.                                   */
+int advchain_one_hot(const int64_t* labels, float* out, int64_t N, int64_t depth, int64_t V, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
