@@ -624,8 +624,7 @@ k_affine_box_gin(const float* __restrict__ gout, const float* __restrict__ theta
 #pragma unroll
   for (int a = 0; a < DIM; ++a) cnt *= floorf(2.f * gn[21 + a]) + 2.f;
   const bool finite = gmax < 3.0e38f;
-  const float scale = (gmax > 0.f && finite) ? 1073741824.f / (cnt * gmax) : 0.f;
-  const float inv = (gmax > 0.f && finite) ? (cnt * gmax) / 1073741824.f : 0.f;
+  const FixScale fs = fix_scale(finite ? cnt * gmax : 0.f, 30);      // 2^30 / (cnt gmax)
   // ---- pass 2: deposits.  GU candidates of the box per thread and round, their grad_out requested together.  The loop is
   // VALU-bound (profiles/r04/sq_issue_summary.txt: 21 % of the wave-cycles at 4 waves a SIMD = the VALU busy 85 % of the
   // time): a position, three taps and the reach test per CANDIDATE, 2.3x as many as samples at 5 degrees.  Positions
@@ -659,7 +658,7 @@ k_affine_box_gin(const float* __restrict__ gout, const float* __restrict__ theta
       // 2^d corners x C deposits per reaching sample (a row-interval compaction of the box, which cut the visited cells
       // 2-3x, changed the time by < 10 % and was dropped).  Per-axis validity and the scaled x weights once per sample; a
       // corner is one product, a channel one product + convert + LDS add.
-      const float wsx[2] = {tx.w0 * scale, tx.w1 * scale};
+      const float wsx[2] = {tx.w0 * fs.mul, tx.w1 * fs.mul};
       const bool okx[2] = {(unsigned)px < (unsigned)G::TX, (unsigned)(px + 1) < (unsigned)G::TX};
       const bool oky[2] = {(unsigned)py < (unsigned)G::TY, (unsigned)(py + 1) < (unsigned)G::TY};
       const bool okz[2] = {(unsigned)pz < (unsigned)G::TZ, DIM == 3 && (unsigned)(pz + 1) < (unsigned)G::TZ};
@@ -676,7 +675,7 @@ k_affine_box_gin(const float* __restrict__ gout, const float* __restrict__ theta
             int* cell = cell0 + (cz * G::TY + cy) * G::TX + cx;
 #pragma unroll
             for (int c = 0; c < CMAX; ++c)
-              if (c < C) atomicAdd(cell + c * TILE, fix_round(ws * go[u][c]));
+              if (c < C) atomicAdd(cell + c * TILE, fix_round(ws * fix_in(go[u][c], fs)));
           }
         }
     }
@@ -694,7 +693,7 @@ k_affine_box_gin(const float* __restrict__ gout, const float* __restrict__ theta
     const int u = (uz * d.s1 + uy) * d.s2 + ux;
 #pragma unroll
     for (int c = 0; c < CMAX; ++c)
-      if (c < C) ginn[(int64_t)c * V + u] = poison ? nanv : (float)acc[c * TILE + cellu] * inv;
+      if (c < C) ginn[(int64_t)c * V + u] = poison ? nanv : fix_out((float)acc[c * TILE + cellu], fs);
   }
 }
 

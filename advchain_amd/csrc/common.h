@@ -179,6 +179,46 @@ __device__ __forceinline__ int fix_round(float x) {
 #endif
 }
 
+// Scale of the fixed-point scatters (every route: march, whole-row, tiled, window, its int64 twin, affine box): a value v of a
+// domain whose largest |value| is gmax enters the accumulator as v * 2^bits / gmax, a cell comes back as cell * gmax / 2^bits.
+// The factor 2^bits / gmax overflows fp32 to +inf once gmax < 2^bits / FLT_MAX (3e-27 at 2^40, 1e-31 at 2^21), so it is
+// kept as mantissa and exponent: gmax = gm 2^e (gm in [0.5, 1)), mul = 1 / gm folds into the weights where the factor stood,
+// and the power of two 2^(bits - e) is applied with v_ldexp_f32 (fix_in), which cannot overflow for a normal gmax.
+// Power-of-two scaling is exact, so the deposits and results are bit for bit those of the plain factor wherever it was
+// finite, and 2^k times the gradient gives exactly 2^k times the result.  gmax == 0: nothing to deposit (mul = 0); a
+// non-finite gmax (the maxima passes turn NaN / inf into +inf): mul = 0 and inv = gmax, every converted cell NaN or inf,
+// as before.
+struct FixScale {
+  int shift;    // bits - e
+  float mul;    // 1 / gm: multiplies the weights (or the value) before fix_in
+  float inv;    // gm (gmax itself when not finite): fix_out
+};
+__device__ __forceinline__ FixScale fix_scale(float gmax, int bits) {
+  FixScale s;
+  const bool ok = gmax <= 3.40282347e38f;                              // false for +inf and NaN
+  const int e = ok ? __builtin_amdgcn_frexp_expf(gmax) : 0;
+  const float gm = ok ? __builtin_amdgcn_frexp_mantf(gmax) : gmax;
+  s.shift = bits - e;
+  s.mul = (gmax > 0.f && ok) ? 1.f / gm : 0.f;
+  s.inv = gm;
+  return s;
+}
+__device__ __forceinline__ float fix_in(float v, const FixScale& s) { return __builtin_amdgcn_ldexpf(v, s.shift); }
+__device__ __forceinline__ float fix_out(float cell, const FixScale& s) { return __builtin_amdgcn_ldexpf(cell * s.inv, -s.shift); }
+// The plain factor 2^bits / gmax and its inverse as floats, for a kernel that can take them: true when both are finite and
+// normal -- every gmax but the extremes -- and then deposits `w * scale * v` and conversions `cell * inv` are one multiply
+// each, as with a single factor; otherwise the kernel uses fix_in / fix_out.
+__device__ __forceinline__ bool fix_plain(const FixScale& s, float& scale, float& inv) {
+  scale = __builtin_amdgcn_ldexpf(s.mul, s.shift);
+  inv = __builtin_amdgcn_ldexpf(s.inv, -s.shift);
+  return scale <= 3.40282347e38f && inv >= 1.17549435e-38f && inv <= 3.40282347e38f;
+}
+// fix_out(cell) + a, rounded ONCE: cell * (gmax / 2^bits) + a was contracted into one fma, and so it stays (the
+// self-compositions add their coordinate path here)
+__device__ __forceinline__ float fix_out_add(float cell, float a, const FixScale& s) {
+  return __builtin_amdgcn_ldexpf(fmaf(cell, s.inv, __builtin_amdgcn_ldexpf(a, s.shift)), -s.shift);
+}
+
 __device__ __forceinline__ void atomic_add_f32(float* p, float v) {
   // hardware global_atomic_add_f32 (no CAS loop); device memory only
   unsafeAtomicAdd(p, v);

@@ -89,7 +89,7 @@ __device__ __forceinline__ void coord_path_values(const float (&vl)[8], float go
 // Fixed-point resolution: a cell can receive a corner of every sample within H+1 voxels of it, (2H+2)^3 at most, each of
 // weight <= 1 and |grad_out| <= the workgroup's max: 2^23 / 2^22 / 2^21 for H = 2 / 3 / 4 keeps any sum below 2^31.
 // (H = 5..8: 18^3 deposits, 2^18.)
-__device__ __forceinline__ float march_fix_scale(int H) { return H <= 2 ? 8388608.f : (H == 3 ? 4194304.f : (H == 4 ? 2097152.f : 262144.f)); }
+__device__ __forceinline__ int march_fix_bits(int H) { return H <= 2 ? 23 : (H == 3 ? 22 : (H == 4 ? 21 : 18)); }   // (fix_scale)
 
 // max |grad_out| of every x row (over its channels) -> rowmax[n][z][y].  The fixed-point scale of a workgroup comes from
 // the rows IT visits, not from the whole batch: gradients are heavy-tailed (edges), and a global scale left the small
@@ -245,8 +245,7 @@ k_scatter_march3d(const float* __restrict__ gout, const float* __restrict__ in, 
   float gmax = wmax[0];
 #pragma unroll
   for (int w = 1; w < NWV; ++w) gmax = fmaxf(gmax, wmax[w]);
-  const float fix = march_fix_scale(H);
-  const float scale = gmax > 0.f ? fix / gmax : 0.f, inv = gmax / fix;
+  const FixScale fs = fix_scale(gmax, march_fix_bits(H));
   if (SELF && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) ws[3] = -1;   // no max|result| from this launch
   const int xs = xbase + lane;
   const bool xin = xs >= 0 && xs < d.s2, xown = xs >= xo0 && xs < xo1;
@@ -364,7 +363,7 @@ k_scatter_march3d(const float* __restrict__ gout, const float* __restrict__ in, 
         float a[C][2];
 #pragma unroll
         for (int c = 0; c < C; ++c) {
-          const float gsc = go[k][c] * scale;
+          const float gsc = fix_in(go[k][c] * fs.mul, fs);
           a[c][0] = wxm[0] * gsc;
           a[c][1] = wxm[1] * gsc;
         }
@@ -450,14 +449,13 @@ k_scatter_march3d(const float* __restrict__ gout, const float* __restrict__ in, 
         float v[C];
 #pragma unroll
         for (int c = 0; c < C; ++c) {
-          v[c] = (float)cell[c * TY * 64] * inv;
+          const float q = (float)cell[c * TY * 64];
+          v[c] = SELF ? fix_out_add(q, SL ? (c0 == 0 ? gg[k][0] : (c0 == 1 ? gg[k][1] : gg[k][2])) : gg[k][c < 3 ? c : 0], fs)
+                      : fix_out(q, fs);
           cell[c * TY * 64] = 0;
         }
         const unsigned s = (unsigned)((zt * d.s1 + uy) * d.s2 + xl) * 4u;
-        if (SELF) {
-#pragma unroll
-          for (int c = 0; c < C; ++c) v[c] += SL ? (c0 == 0 ? gg[k][0] : (c0 == 1 ? gg[k][1] : gg[k][2])) : gg[k][c < 3 ? c : 0];
-        } else if (GG && !EARLY && xown) {
+        if (!SELF && GG && !EARLY && xown) {
           float* gq = ggrid + (int64_t)n * 3 * V;
 #pragma unroll
           for (int a = 0; a < 3; ++a) st_off(gq + (int64_t)a * V, s, gg[k][a]);
@@ -530,8 +528,7 @@ k_scatter_march3d_flat(const float* __restrict__ gout, const float* __restrict__
   float gmax = wmax[0];
 #pragma unroll
   for (int w = 1; w < NWV; ++w) gmax = fmaxf(gmax, wmax[w]);
-  const float fix = march_fix_scale(H);
-  const float scale = gmax > 0.f ? fix / gmax : 0.f, inv = gmax / fix;
+  const FixScale fs = fix_scale(gmax, march_fix_bits(H));
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) ws[3] = -1;   // no max|result| from this launch
   const int yend = min(y0 + TY, d.s1);
   const int nrows = TY + 2 * H;
@@ -640,7 +637,7 @@ k_scatter_march3d_flat(const float* __restrict__ gout, const float* __restrict__
         float a[C][2];
 #pragma unroll
         for (int c = 0; c < C; ++c) {
-          const float gsc = go[k][c] * scale;
+          const float gsc = fix_in(go[k][c] * fs.mul, fs);
           a[c][0] = wxm[0] * gsc;
           a[c][1] = wxm[1] * gsc;
         }
@@ -695,12 +692,12 @@ k_scatter_march3d_flat(const float* __restrict__ gout, const float* __restrict__
           float v[C];
 #pragma unroll
           for (int c = 0; c < C; ++c) {
-            v[c] = (float)cell[c * chan_cells] * inv;
+            v[c] = fix_out_add((float)cell[c * chan_cells], gg[k][c], fs);
             cell[c * chan_cells] = 0;
           }
           if (oval[k]) {
 #pragma unroll
-            for (int c = 0; c < C; ++c) st_off(ginn + (int64_t)c * V, base + ooff[k], v[c] + gg[k][c]);
+            for (int c = 0; c < C; ++c) st_off(ginn + (int64_t)c * V, base + ooff[k], v[c]);
           }
         }
       }
@@ -887,8 +884,7 @@ k_scatter_march3d_wide(const float* __restrict__ gout, const float* __restrict__
   float gmax = wmax[0];
 #pragma unroll
   for (int w = 1; w < NWV; ++w) gmax = fmaxf(gmax, wmax[w]);
-  const float fix = march_fix_scale(H);
-  const float scale = gmax > 0.f ? fix / gmax : 0.f, inv = gmax / fix;
+  const FixScale fs = fix_scale(gmax, march_fix_bits(H));
 
   // Stores never make a wave wait: on gfx9 the source registers of a store stay busy until it is acknowledged (vmcnt), and
   // the compiler puts `s_waitcnt vmcnt(0)` in front of the first instruction that reuses them.  With the grad_grid values
@@ -992,7 +988,7 @@ k_scatter_march3d_wide(const float* __restrict__ gout, const float* __restrict__
             slotz[cz] = slot * (TY * 64);
           }
 #endif
-          const float gsc = go * scale;
+          const float gsc = fix_in(go * fs.mul, fs);
           const float a0 = wxm[0] * gsc, a1 = wxm[1] * gsc;
 #pragma unroll
           for (int cz = 0; cz < 2; ++cz)
@@ -1058,7 +1054,7 @@ k_scatter_march3d_wide(const float* __restrict__ gout, const float* __restrict__
       const int4 c = *cell;
       *cell = make_int4(0, 0, 0, 0);
       if (uy < d.s1 && 4 * q < d.s2) {
-        fprev = make_float4((float)c.x * inv, (float)c.y * inv, (float)c.z * inv, (float)c.w * inv);
+        fprev = make_float4(fix_out((float)c.x, fs), fix_out((float)c.y, fs), fix_out((float)c.z, fs), fix_out((float)c.w, fs));
         fo_prev = (unsigned)((zt * d.s1 + uy) * d.s2 + 4 * q) * 4u;
         *reinterpret_cast<float4*>(reinterpret_cast<char*>(ginn) + fo_prev) = fprev;
       }
@@ -1087,8 +1083,8 @@ k_scatter_march3d_wide(const float* __restrict__ gout, const float* __restrict__
 #ifndef ADVCHAIN_ROWS2D_FLAT
 #define ADVCHAIN_ROWS2D_FLAT 1
 #endif
-__device__ __forceinline__ float rows2d_fix_scale(int H) {   // (2H+2)^2 deposits of weight <= 1 stay below 2^31
-  return H <= 2 ? 33554432.f : (H <= 4 ? 16777216.f : (H <= 8 ? 4194304.f : (H <= 16 ? 1048576.f : 262144.f)));
+__device__ __forceinline__ int rows2d_fix_bits(int H) {   // (2H+2)^2 deposits of weight <= 1 stay below 2^31 (fix_scale)
+  return H <= 2 ? 25 : (H <= 4 ? 24 : (H <= 8 ? 22 : (H <= 16 ? 20 : 18)));
 }
 
 template <int PAD, int C, bool SELF, bool GG>
@@ -1125,8 +1121,14 @@ k_scatter_rows2d(const float* __restrict__ gout, const float* __restrict__ in, c
   float gmax = wmax[0];
 #pragma unroll
   for (int w = 1; w < NWV; ++w) gmax = fmaxf(gmax, wmax[w]);
-  const float fix = rows2d_fix_scale(H);
-  const float scale = gmax > 0.f ? fix / gmax : 0.f, inv = gmax / fix;
+  const FixScale fs = fix_scale(gmax, rows2d_fix_bits(H));
+  // Everything below twice (workgroup-uniform): PLAIN, the float factor 2^b / gmax as one multiply where it stands -- this
+  // kernel is the dominant entry of the 2D chains, and a v_ldexp_f32 per grad_out value costs ~1 % of a cfg-2 step -- and,
+  // for the extreme maxima where that factor or its inverse is not a normal float, the split form of fix_scale.
+  float scale_p, inv_p;
+  const bool plain = fix_plain(fs, scale_p, inv_p);
+  auto body = [&](auto plain_tag) {
+  constexpr bool PLAIN = decltype(plain_tag)::value;
 
   // ---- deposits: (row, 64-pixel segment) items, two per wave and round with their loads issued together.  The OWN rows
   // first: their coordinate path (which needs nothing from the accumulator) is evaluated where the row is visited for its
@@ -1161,6 +1163,9 @@ k_scatter_rows2d(const float* __restrict__ gout, const float* __restrict__ in, c
       for (int c = 0; c < C; ++c) o.load(inn + (int64_t)c * V, vl[c]);
     }
     if (any) {
+      float gs[C];                                  // grad_out times the power-of-two part of the scale (fs.mul is in the weights)
+#pragma unroll
+      for (int c = 0; c < C; ++c) gs[c] = PLAIN ? go[c] : fix_in(go[c], fs);
       if constexpr (ADVCHAIN_ROWS2D_FLAT && SELF) {
       // branch-light deposits for the squarings (round 6; the 3D march scatters do the same since lesson 37 b): per-axis masked weights, and
       // a masked corner adds its zero at the lane's OWN column of an owned row -- never two lanes on one cell -- instead of
@@ -1171,7 +1176,7 @@ k_scatter_rows2d(const float* __restrict__ gout, const float* __restrict__ in, c
 #pragma unroll
       for (int cx = 0; cx < 2; ++cx) {
         const bool ok = xin && (cx ? t.x.v1 : t.x.v0);
-        wxm[cx] = ok ? (cx ? t.x.w1 : t.x.w0) * scale : 0.f;
+        wxm[cx] = ok ? (cx ? t.x.w1 : t.x.w0) * (PLAIN ? scale_p : fs.mul) : 0.f;
         colc[cx] = ok ? t.x.i0 + cx : ownc;
       }
 #pragma unroll
@@ -1188,7 +1193,7 @@ k_scatter_rows2d(const float* __restrict__ gout, const float* __restrict__ in, c
           const float wsc = wxm[cx] * wym[cy];
           int* cell = acc + rowc[cy] + colc[cx];
 #pragma unroll
-          for (int c = 0; c < C; ++c) atomicAdd(cell + c * TY * W, fix_round(wsc * go[c]));
+          for (int c = 0; c < C; ++c) atomicAdd(cell + c * TY * W, fix_round(wsc * gs[c]));
         }
       } else {
       // (the image warps keep the per-corner branches: with four channels the masked form holds 89 VGPRs and measured
@@ -1200,10 +1205,10 @@ k_scatter_rows2d(const float* __restrict__ gout, const float* __restrict__ in, c
 #pragma unroll
         for (int cx = 0; cx < 2; ++cx) {
           if (!(oky && (cx ? t.x.v1 : t.x.v0))) continue;
-          const float wsc = (cx ? t.x.w1 : t.x.w0) * (cy ? t.y.w1 : t.y.w0) * scale;
+          const float wsc = (cx ? t.x.w1 : t.x.w0) * (cy ? t.y.w1 : t.y.w0) * (PLAIN ? scale_p : fs.mul);
           int* cell = acc + (py - y0) * W + t.x.i0 + cx;
 #pragma unroll
-          for (int c = 0; c < C; ++c) atomicAdd(cell + c * TY * W, fix_round(wsc * go[c]));
+          for (int c = 0; c < C; ++c) atomicAdd(cell + c * TY * W, fix_round(wsc * gs[c]));
         }
       }
       }
@@ -1279,11 +1284,12 @@ k_scatter_rows2d(const float* __restrict__ gout, const float* __restrict__ in, c
     const int s = (y0 + r) * W + min(x, W - 1);
     float v[C];
 #pragma unroll
-    for (int c = 0; c < C; ++c) v[c] = (float)acc[(c * TY + r) * W + min(x, W - 1)] * inv;
-    if (SELF) {
-#pragma unroll
-      for (int c = 0; c < C; ++c) v[c] += ggv[k][c < 2 ? c : 0];
-    } else if (GG) {
+    for (int c = 0; c < C; ++c) {
+      const float q = (float)acc[(c * TY + r) * W + min(x, W - 1)];
+      if (PLAIN) v[c] = SELF ? fmaf(q, inv_p, ggv[k][c < 2 ? c : 0]) : q * inv_p;
+      else v[c] = SELF ? fix_out_add(q, ggv[k][c < 2 ? c : 0], fs) : fix_out(q, fs);
+    }
+    if (!SELF && GG) {
       float* gq = ggrid + (int64_t)n * 2 * V + s;
       if (on) { gq[0] = ggv[k][0]; gq[V] = ggv[k][1]; }
     }
@@ -1309,6 +1315,9 @@ k_scatter_rows2d(const float* __restrict__ gout, const float* __restrict__ in, c
     __syncthreads();
     if ((int)threadIdx.x < yend - y0) rowmax_next[(int64_t)n * d.s1 + y0 + threadIdx.x] = __int_as_float(rmax[threadIdx.x]);
   }
+  };
+  if (plain) body(std::true_type{});
+  else body(std::false_type{});
 }
 
 }  // namespace advchain

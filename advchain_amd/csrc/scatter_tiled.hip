@@ -39,7 +39,7 @@ __device__ __forceinline__ bool deposit_handled(int sz, int sy, int sx, int uz, 
   return in_tile_box(sx, ux, tc.t2, tc.h2) && in_tile_box(sy, uy, tc.t1, tc.h1) && in_tile_box(sz, uz, tc.t0, tc.h0);
 }
 
-constexpr float kFixedOne = 1073741824.f;  // 2^30
+constexpr int kFixedBits = 30;  // values scaled by 2^30 / max|grad_out| (fix_scale)
 
 __device__ __forceinline__ void lds_add_fixed(long long* p, float v) {
   const long long q = (long long)__float2int_rn(v);
@@ -125,7 +125,7 @@ k_scatter_rows(const float* __restrict__ gout, const float* __restrict__ in, con
   const int tvox = tc.t0 * tc.t1 * tc.t2;
   for (int i = threadIdx.x; i < C * tvox; i += NT) acc[i] = 0;
   const float amax = absmax_in[0];
-  const float scale = amax > 0.f ? kFixedOne / amax : 0.f;
+  const FixScale fs = fix_scale(amax, kFixedBits);
   __syncthreads();
   // source region = tile + halo, clipped to the volume; lane <-> x
   const int rx0 = max(x0 - tc.h2, 0), rx1 = min(x0 + tc.t2 + tc.h2, d.s2);
@@ -196,9 +196,9 @@ k_scatter_rows(const float* __restrict__ gout, const float* __restrict__ in, con
               const bool mine = (ux >= x0) && (ux < x0 + tc.t2) && (uy >= y0) && (uy < y0 + tc.t1) && (uz >= z0) && (uz < z0 + tc.t0);
               if (mine) {
                 const int lo = ((uz - z0) * tc.t1 + (uy - y0)) * tc.t2 + (ux - x0);
-                const float w = t.w(cz, cy, cx) * scale;
+                const float w = t.w(cz, cy, cx) * fs.mul;
 #pragma unroll
-                for (int c = 0; c < C; ++c) lds_add_fixed(acc + c * tvox + lo, w * cur.go[c]);
+                for (int c = 0; c < C; ++c) lds_add_fixed(acc + c * tvox + lo, w * fix_in(cur.go[c], fs));
               } else if (owned && !deposit_handled(sz, sy, sx, uz, uy, ux, tc)) {
                 overflow = true;
               }
@@ -216,9 +216,9 @@ k_scatter_rows(const float* __restrict__ gout, const float* __restrict__ in, con
         const float ggz = (DIM == 3 && pz) ? t.z.mult * az : 0.f;
         if (SELF) {
           const int lo = ((sz - z0) * tc.t1 + (sy - y0)) * tc.t2 + (sx - x0);
-          if (ggx != 0.f) lds_add_fixed_wide(acc + lo, ggx * scale);
-          if (ggy != 0.f) lds_add_fixed_wide(acc + tvox + lo, ggy * scale);
-          if (DIM == 3 && ggz != 0.f) lds_add_fixed_wide(acc + 2 * tvox + lo, ggz * scale);
+          if (ggx != 0.f) lds_add_fixed_wide(acc + lo, fix_in(ggx * fs.mul, fs));
+          if (ggy != 0.f) lds_add_fixed_wide(acc + tvox + lo, fix_in(ggy * fs.mul, fs));
+          if (DIM == 3 && ggz != 0.f) lds_add_fixed_wide(acc + 2 * tvox + lo, fix_in(ggz * fs.mul, fs));
         } else {
           float* gg = ggrid + (int64_t)n * DIM * V + s;
           gg[0] = ggx;
@@ -236,7 +236,6 @@ k_scatter_rows(const float* __restrict__ gout, const float* __restrict__ in, con
   }
   __syncthreads();
   // flush the tile (plain, coalesced along x) and track max|value| for the next launch of a chain
-  const float inv = amax * (1.f / kFixedOne);
   float* ginn = gin + (int64_t)n * C * V;
   float m = 0.f;
   for (int i = threadIdx.x; i < C * tvox; i += NT) {
@@ -248,7 +247,7 @@ k_scatter_rows(const float* __restrict__ gout, const float* __restrict__ in, con
     const int lz = q / tc.t1;
     const int ux = x0 + lx, uy = y0 + ly, uz = z0 + lz;
     if (ux < d.s2 && uy < d.s1 && uz < d.s0) {
-      const float v = (float)acc[i] * inv;
+      const float v = fix_out((float)acc[i], fs);
       ginn[(int64_t)c * V + (uz * d.s1 + uy) * d.s2 + ux] = v;
       m = fmaxf(m, fabsf(v));
     }

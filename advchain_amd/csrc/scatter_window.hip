@@ -26,17 +26,14 @@ namespace advchain {
 // to run.  The scale comes from a max |grad_out| per batch entry (k_det_absmax; a NaN / inf there turns the entry's
 // outputs into NaN) -- per entry, so that a sample's result does not depend on what else is in the batch.  Resolution
 // 2^-40 of that maximum per addition; 2^22 additions of the maximum itself fit below 2^63.
-constexpr float kDetFix = 1099511627776.f;   // 2^40
+constexpr int kDetBits = 40;   // (fix_scale)
 template <bool DET>
 __device__ __forceinline__ void win_global_add(float* __restrict__ gin, unsigned long long* __restrict__ acc, int64_t idx,
-                                               float v, float sdet) {
-  if (DET) atomicAdd(acc + idx, (unsigned long long)__float2ll_rn(v * sdet));
+                                               float v, const FixScale& sdet) {
+  if (DET) atomicAdd(acc + idx, (unsigned long long)__float2ll_rn(fix_in(v * sdet.mul, sdet)));
   else atomic_add_f32(gin + idx, v);
 }
-__device__ __forceinline__ float det_scale(const float* __restrict__ maxn, int n) {
-  const float m = maxn[n];
-  return (m > 0.f && m <= 3.0e38f) ? kDetFix / m : 0.f;
-}
+__device__ __forceinline__ FixScale det_scale(const float* __restrict__ maxn, int n) { return fix_scale(maxn[n], kDetBits); }
 
 // max |x| per batch entry (over `per_n` floats) -> maxn[n] (zeroed by the caller); non-finite -> +inf
 __global__ void __launch_bounds__(kBlock) k_det_absmax(const float* __restrict__ x, float* __restrict__ maxn, int64_t per_n) {
@@ -70,21 +67,21 @@ __global__ void __launch_bounds__(kBlock) k_det_absmax(const float* __restrict__
   }
 }
 
-// grad_in = int64 image * max / 2^40 (a non-finite maximum: 0 * inf = NaN, as the owner-computes scatters do)
+// grad_in = int64 image * max / 2^40 (fix_out; a non-finite maximum: 0 * inf = NaN, as the owner-computes scatters do)
 __global__ void __launch_bounds__(kBlock) k_det_convert(const long long* __restrict__ acc, const float* __restrict__ maxn,
                                                         float* __restrict__ gin, int64_t per_n) {
   const int n = blockIdx.y;
-  const float inv = maxn[n] * (1.f / kDetFix);
+  const FixScale fs = det_scale(maxn, n);
   const long long* a = acc + (int64_t)n * per_n;
   float* g = gin + (int64_t)n * per_n;
   const int64_t stride = (int64_t)gridDim.x * kBlock * 2;
   for (int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * 2; i < per_n; i += stride) {
     if (i + 2 <= per_n) {
       const longlong2 q = *reinterpret_cast<const longlong2*>(a + i);
-      g[i] = (float)q.x * inv;
-      g[i + 1] = (float)q.y * inv;
+      g[i] = fix_out((float)q.x, fs);
+      g[i + 1] = fix_out((float)q.y, fs);
     } else {
-      g[i] = (float)a[i] * inv;
+      g[i] = fix_out((float)a[i], fs);
     }
   }
 }
@@ -121,7 +118,7 @@ k_scatter_window2d(const float* __restrict__ gout, const float* __restrict__ in,
   const float* inn = in + (int64_t)n * C * V;
   float* ginn = gin + (int64_t)n * C * V;
   unsigned long long* accn = DET ? acc64 + (int64_t)n * C * V : nullptr;
-  const float sdet = DET ? det_scale(maxn, n) : 0.f;
+  const FixScale sdet = DET ? det_scale(maxn, n) : FixScale{0, 0.f, 0.f};
 
   // ---- 1. taps of this thread's samples, bounding box of the valid corners, max |grad_out|
   Taps<DIM, PAD> t[SPT];
@@ -176,7 +173,7 @@ k_scatter_window2d(const float* __restrict__ gout, const float* __restrict__ in,
   if (ww > 0 && wh > cells_per_ch / ww) wh = cells_per_ch / ww;
   const int cells = ww * wh;
   for (int i = threadIdx.x; i < C * cells; i += kBlock) win[i] = 0;
-  const float scale = gmax > 0.f ? 1048576.f / gmax : 0.f;   // 2^20
+  const FixScale fs = fix_scale(gmax, 20);
   __syncthreads();
 
   // ---- coordinate path of all four samples first: 4 x 4 x C corner loads in flight together, no control flow between
@@ -212,10 +209,10 @@ k_scatter_window2d(const float* __restrict__ gout, const float* __restrict__ in,
         if (!t[j].ok(0, cy, cx)) continue;
         const float w = t[j].w(0, cy, cx);
         if (inx[cx] && iny[cy]) {
-          const float ws = w * scale;
+          const float ws = w * fs.mul;
           int* cell = win + cell0 + (cy ? ww : 0) + cx;
 #pragma unroll
-          for (int c = 0; c < C; ++c) atomicAdd(cell + c * cells, fix_round(ws * go[j][c]));
+          for (int c = 0; c < C; ++c) atomicAdd(cell + c * cells, fix_round(ws * fix_in(go[j][c], fs)));
         } else {
           const int64_t dst = vox0 + (cy ? d.s2 : 0) + cx;
 #pragma unroll
@@ -237,13 +234,12 @@ k_scatter_window2d(const float* __restrict__ gout, const float* __restrict__ in,
   __syncthreads();
 
   // ---- 3. flush the non-zero cells (rows of the window are runs of consecutive addresses)
-  const float inv = gmax * (1.f / 1048576.f);
   for (int i = threadIdx.x; i < C * cells; i += kBlock) {
     const int a = win[i];
     if (a == 0) continue;
     const int c = i / cells, r = i - c * cells;
     const int wy = r / ww, wx = r - wy * ww;
-    win_global_add<DET>(ginn, accn, (int64_t)c * V + (by0 + wy) * d.s2 + (bx0 + wx), (float)a * inv, sdet);
+    win_global_add<DET>(ginn, accn, (int64_t)c * V + (by0 + wy) * d.s2 + (bx0 + wx), fix_out((float)a, fs), sdet);
   }
 }
 
@@ -291,7 +287,7 @@ k_scatter_window3d(const float* __restrict__ gout, const float* __restrict__ in,
   const float* inn = in + (int64_t)n * C * V;
   float* ginn = gin + (int64_t)n * C * V;
   unsigned long long* accn = DET ? acc64 + (int64_t)n * C * V : nullptr;
-  const float sdet = DET ? det_scale(maxn, n) : 0.f;
+  const FixScale sdet = DET ? det_scale(maxn, n) : FixScale{0, 0.f, 0.f};
 
   // ---- 1. bounding box of the valid corners, max |grad_out|
   int lo[3] = {1 << 30, 1 << 30, 1 << 30}, hi[3] = {-(1 << 30), -(1 << 30), -(1 << 30)};
@@ -345,7 +341,7 @@ k_scatter_window3d(const float* __restrict__ gout, const float* __restrict__ in,
   if (ww > 0 && wh > cells_per_ch / ww) wh = cells_per_ch / ww;
   if (ww * wh > 0 && wd > cells_per_ch / (ww * wh)) wd = cells_per_ch / (ww * wh);
   const int plane = ww * wh, cells = plane * wd;
-  const float scale = gmax > 0.f ? 1048576.f / gmax : 0.f;   // 2^20
+  const FixScale fs = fix_scale(gmax, 20);
 
   // ---- 2. deposits.  Grid and grad_out of the four samples are requested up front (unconditionally: a dead sample
   // reads voxel 0), so the loop below starts with its operands in flight instead of one memory round trip per sample.
@@ -412,10 +408,10 @@ k_scatter_window3d(const float* __restrict__ gout, const float* __restrict__ in,
           for (int cx = 0; cx < 2; ++cx) {
             const bool okc = t.ok(cz, cy, cx), inw = inx[cx] && iny[cy] && inz[cz] && cells > 0;
             outside = outside || (okc && !inw);
-            const float ws = (okc && inw) ? t.w(cz, cy, cx) * scale : 0.f;
+            const float ws = (okc && inw) ? t.w(cz, cy, cx) * fs.mul : 0.f;
             int* cell = win + ((okc && inw) ? cell0 + (cz ? plane : 0) + (cy ? ww : 0) + cx : own_cell);
 #pragma unroll
-            for (int c = 0; c < CP; ++c) atomicAdd(cell + c * cells, fix_round(ws * go[c0 + c]));
+            for (int c = 0; c < CP; ++c) atomicAdd(cell + c * cells, fix_round(ws * fix_in(go[c0 + c], fs)));
           }
       if (__ballot(outside) != 0) {
 #pragma unroll
@@ -442,10 +438,10 @@ k_scatter_window3d(const float* __restrict__ gout, const float* __restrict__ in,
           if (!t.ok(cz, cy, cx)) continue;
           const float w = t.w(cz, cy, cx);
           if (inx[cx] && iny[cy] && inz[cz]) {
-            const float ws = w * scale;
+            const float ws = w * fs.mul;
             int* cell = win + cell0 + (cz ? plane : 0) + (cy ? ww : 0) + cx;
 #pragma unroll
-            for (int c = 0; c < CP; ++c) atomicAdd(cell + c * cells, fix_round(ws * go[c0 + c]));
+            for (int c = 0; c < CP; ++c) atomicAdd(cell + c * cells, fix_round(ws * fix_in(go[c0 + c], fs)));
           } else {
             const int64_t dst = vox0 + (cz ? planev : 0) + (cy ? rowv : 0) + cx + (int64_t)c0 * V;
 #pragma unroll
@@ -475,7 +471,6 @@ k_scatter_window3d(const float* __restrict__ gout, const float* __restrict__ in,
 
   // ---- 3. flush: thread <-> cell of the window in memory order (runs of consecutive addresses; a wave per window row left
   // the lanes beyond the row's width idle, 18-40 of 64: 13-21 % of the kernel at 8 x . x 160 x 160 x 80)
-  const float inv = gmax * (1.f / 1048576.f);
   {
     const float inv_ww = 1.f / (float)max(ww, 1), inv_wh = 1.f / (float)max(wh, 1), inv_wd = 1.f / (float)max(wd, 1);
     for (int i = threadIdx.x; i < CP * cells; i += kBlock) {
@@ -485,7 +480,7 @@ k_scatter_window3d(const float* __restrict__ gout, const float* __restrict__ in,
       const int rz = (int)(((float)r + 0.5f) * inv_wh), wy = r - rz * wh;
       const int c = (int)(((float)rz + 0.5f) * inv_wd), wz = rz - c * wd;
       win_global_add<DET>(ginn, accn, (int64_t)(c0 + c) * V + ((lo[2] + wz) * d.s1 + (lo[1] + wy)) * d.s2 + (lo[0] + wx),
-                          (float)a * inv, sdet);
+                          fix_out((float)a, fs), sdet);
     }
   }
   if (c0 + CP < C) __syncthreads();          // the window is cleared for the next channel pair
