@@ -75,6 +75,12 @@ PROTOTYPES = {
     "advchain_contour_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _I, _P]),
     "advchain_contour_bwd": (_I, [_P, _P, _P, _P, _L, _L, _I, _P, _I, _P]),
     "advchain_one_hot": (_I, [_P, _P, _L, _L, _L, _P]),
+    "advchain_image_diff2d_fwd": (_I, [_P, _P, _P, _L, _L, _P, _P]),
+    "advchain_image_diff2d_bwd": (_I, [_P, _P, _P, _L, _L, _P, _P]),
+    "advchain_jacobian_det2d_fwd": (_I, [_P, _P, _L, _P, _P]),
+    "advchain_jacobian_det2d_bwd": (_I, [_P, _P, _P, _L, _P, _P]),
+    "advchain_expo_start": (_I, [_P, _P, _F, _L, _I, _P, _P]),
+    "advchain_sumsq_ordered": (_I, [_P, _L, _P, _P, _P]),
 }
 
 class UpdateDesc(ctypes.Structure):

@@ -176,6 +176,21 @@ class AdvAffine(AdvTransformBase):
     def rescale_parameters(self):
         return self.param
 
+    def make_batch_eye_matrix(self, batch_size, device):
+        """B x 3 x 3 (2D) or B x 4 x 4 (3D) float32 identity matrices (adv_affine.py:275-287)."""
+        O = torch.zeros(batch_size, dtype=torch.float32, device=device)
+        I = torch.ones(batch_size, dtype=torch.float32, device=device)
+        if self.spatial_dims == 2:
+            eyeMtrx = torch.stack([torch.stack([I, O, O], dim=-1),
+                                   torch.stack([O, I, O], dim=-1),
+                                   torch.stack([O, O, I], dim=-1)], dim=1)
+        elif self.spatial_dims == 3:
+            eyeMtrx = torch.stack([torch.stack([I, O, O, O], dim=-1),
+                                   torch.stack([O, I, O, O], dim=-1),
+                                   torch.stack([O, O, I, O], dim=-1),
+                                   torch.stack([O, O, O, I], dim=-1)], dim=1)
+        return eyeMtrx
+
     def get_name(self):
         return 'affine'
 

@@ -15,6 +15,26 @@ from .adv_transformation_base import AdvTransformBase
 logger = logging.getLogger(__name__)
 
 
+def bspline_kernel_2d(sigma=[1, 1], order=3, asTensor=False, dtype=torch.float32, device=torch.device("cuda")):
+    """The reference's B-spline window (adv_bias.py:12-35): the outer product of the 1-D factors of bands.bspline_kernel_1d
+    (round i pads by i * s, so the window has zero borders), in float32; a numpy array unless asTensor."""
+    k = np.outer(bands.bspline_kernel_1d(sigma[0], order, '2d'), bands.bspline_kernel_1d(sigma[1], order, '2d'))
+    kernel = torch.from_numpy(k.astype(np.float32))
+    if asTensor:
+        return kernel.to(dtype=dtype, device=device)
+    return kernel.numpy()
+
+
+def bspline_kernel_3d(sigma=[1, 1, 1], order=2, asTensor=False, dtype=torch.float32, device=torch.device("cuda")):
+    """3D window (adv_bias.py:37-48): every round pads by s - 1."""
+    f = [bands.bspline_kernel_1d(s, order, '3d') for s in sigma[:3]]
+    k = f[0][:, None, None] * f[1][None, :, None] * f[2][None, None, :]
+    kernel = torch.from_numpy(k.astype(np.float32))
+    if asTensor:
+        return kernel.to(dtype=dtype, device=device)
+    return kernel.numpy()
+
+
 class AdvBias(AdvTransformBase):
     """Adv Bias."""
 
@@ -197,6 +217,19 @@ class AdvBias(AdvTransformBase):
 
     def predict_backward(self, data, **kwargs):
         return data
+
+    def get_bspline_kernel(self, spacing, order=3):
+        """Sets and returns `_kernel` (1,1,k...) and `_padding` as the reference does (adv_bias.py:358-374).  The field itself is
+        synthesised from the band tables, which this leaves alone."""
+        if self._dim == 2:
+            self._kernel = bspline_kernel_2d(spacing, order=order, asTensor=True, dtype=self._dtype, device=self.device)
+        elif self._dim == 3:
+            self._kernel = bspline_kernel_3d(spacing, order=order, asTensor=True, dtype=self._dtype, device=self.device)
+        self._padding = (np.array(self._kernel.size()) - 1) / 2
+        self._padding = self._padding.astype(dtype=int).tolist()
+        self._kernel.unsqueeze_(0).unsqueeze_(0)
+        self._kernel = self._kernel.to(dtype=self._dtype, device=self.device)
+        return self._kernel
 
     def get_name(self):
         return 'bias'

@@ -25,6 +25,70 @@ def get_base_grid(batch_size, image_height, image_width, image_depth=None, devic
     return torch.cat(chans, dim=1)
 
 
+def calculate_image_diff(images):
+    """(dx, dy) of a (N,C,H,W) batch (adv_morph.py:57-77): central differences inside, one-sided ones at the first and last
+    column / row; x runs along W.  advchain_image_diff2d_fwd / _bwd."""
+    assert len(images.size()) == 4, 'only support 2D version'
+    return ops.image_diff2d(images)
+
+
+def calculate_jacobian_determinant(data, type='displacement'):
+    """(1 + dxx)(1 + dyy) - dxy dyx of a (N,2,H,W) displacement, per pixel (adv_morph.py:80-100) -> (N,1,H,W).
+    advchain_jacobian_det2d_fwd / _bwd."""
+    type_library = ['displacement']
+    assert len(data.size()) == 4 and data.size(1) == 2, 'only support 2D version, and transformation format is NCHW'
+    assert type in type_library, 'only support {} but found: '.format(type_library, type)
+    return ops.jacobian_det2d(data)
+
+
+def integrate_by_add(basegrid, dxy):
+    """basegrid += dxy in place; returns basegrid itself (adv_morph.py:103-113)."""
+    basegrid += dxy
+    return basegrid
+
+
+def vectorFieldExponentiation2D(duv, nb_steps=8, type='ss', device=torch.device("cuda")):
+    """phi_n - phi_0 of the scaling and squaring of a (N,2,H,W) velocity (adv_morph.py:116-146; phi_0 = id + duv / 2^n, the
+    reference's aliased start grid).  Any `type` other than 'ss': n Euler steps phi <- phi_0 o phi.  The result is on duv's
+    GPU; `device` must resolve to it."""
+    return ops.field_exponentiation(duv, nb_steps, type == 'ss', device, 2)
+
+
+def vectorFieldExponentiation3D(duv, nb_steps=8, type='ss', device=torch.device("cuda")):
+    """3D version (adv_morph.py:148-177): n grows while the whole-batch Frobenius norm of duv / 2^n exceeds 0.5.  Euler
+    steps raise the reference's TypeError (range() of a float, adv_morph.py:171)."""
+    if type != 'ss':
+        raise TypeError("'float' object cannot be interpreted as an integer")
+    return ops.field_exponentiation(duv, nb_steps, True, device, 3)
+
+
+def applyComposition2D(flow1, flow2):
+    """flow1 sampled at the absolute positions flow2 (N,2,H',W'), border padding (adv_morph.py:179-190); any channel count and
+    size of flow1, gradients to both."""
+    return ops.grid_sample(flow1, flow2, 'bilinear', 'border')
+
+
+def applyComposition3D(flow1, flow2):
+    """3D version (adv_morph.py:192-202)."""
+    return ops.grid_sample(flow1, flow2, 'bilinear', 'border')
+
+
+class _GaussianFilter(torch.nn.Module):
+    """The depthwise Gaussian of get_gaussian_kernel: `.weight` is the reference's dense (C,1,k,k[,k]) kernel; forward() runs
+    the separable HIP Gaussian with the same zero padding."""
+
+    def __init__(self, weight, sigma, taps, spatial_dims):
+        super(_GaussianFilter, self).__init__()
+        self.weight = torch.nn.Parameter(weight, requires_grad=False)
+        self.sigma, self.taps, self.spatial_dims = float(sigma), int(taps), int(spatial_dims)
+
+    def forward(self, x):
+        if x.dim() != self.spatial_dims + 2 or x.shape[1] != self.weight.shape[0]:
+            raise RuntimeError("Gaussian filter of %d channels (%dD) got an input of shape %s"
+                               % (self.weight.shape[0], self.spatial_dims, tuple(x.shape)))
+        return ops.gauss_smooth(x, self.sigma, self.taps)
+
+
 class AdvMorph(AdvTransformBase):
     """Adv Morph."""
 
@@ -216,6 +280,33 @@ class AdvMorph(AdvTransformBase):
         for _ in range(n):
             phi = ops.grid_sample(phi0, phi, 'bilinear', 'border')                  # applyComposition2D(interval_phi, phi)
         return ops.axpy(ops.axpy(phi, phi0, -1.0), self.base_grid, 1.0)
+
+    def gaussian_smooth(self, inputvector, iter=1, kernel_size=41, sigma=8):
+        """`iter` passes of the zero-padded Gaussian (adv_morph.py:377-389) over a window of max(kernel_size, 2 int(4 sigma
+        + 0.5) + 1) taps; even windows and windows over 129 taps raise NotImplementedError."""
+        taps = bands.gaussian_taps(sigma, kernel_size)
+        ops.gauss9(sigma, taps)      # (raises for a window the kernels do not take)
+        for _ in range(iter):
+            inputvector = ops.gauss_smooth(inputvector, sigma, taps)
+        return inputvector
+
+    def get_gaussian_kernel(self, kernel_size=5, sigma=8, channels=3):
+        """nn.Module with the reference's dense depthwise weight (adv_morph.py:391-452) whose forward is the HIP Gaussian."""
+        if self.spatial_dims not in (2, 3):
+            raise NotImplementedError('only 2D and 3D are supported')
+        k = bands.gaussian_taps(sigma, kernel_size)
+        ops.gauss9(sigma, k)
+        # the dense weight exactly as the reference builds it (host arithmetic, no convolution)
+        x = torch.arange(k)
+        axes = torch.meshgrid([x] * self.spatial_dims, indexing='ij')
+        grid = torch.stack(list(reversed(axes)), dim=-1).float()
+        g = torch.exp(-torch.sum((grid - (k - 1) / 2.) ** 2., dim=-1) / (2 * sigma ** 2.))
+        g = g / torch.sum(g)
+        weight = g.view(1, 1, *([k] * self.spatial_dims)).repeat(channels, *([1] * (self.spatial_dims + 1)))
+        filt = _GaussianFilter(weight, sigma, k, self.spatial_dims)
+        if self.use_gpu:
+            filt = filt.to(self.device)
+        return filt
 
     def get_deformation_displacement_field(self, duv=None):
         # adv_morph.py:339-347

@@ -8,6 +8,7 @@ import ctypes
 import functools
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1798,3 +1799,190 @@ def one_hot(labels, depth):
     out = torch.empty((N, int(depth), V), device=labels.device, dtype=torch.float32)
     _lib.check(_lib.load().advchain_one_hot(_ptr(labels), _ptr(out), N, int(depth), max(V, 1), _stream()), "one_hot")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# deformation helpers of adv_morph.py:57-202 (deform_diff.hip, the squaring chain, the sampler)
+# ------------------------------------------------------------------------------------------------
+def _check_planes(x, what):
+    """H and W of at least 2: the reference indexes column / row 1 (adv_morph.py:70-75) and raises IndexError below that."""
+    for ax in (3, 2):
+        if x.shape[ax] < 2:
+            raise IndexError("%s: index 1 is out of bounds for dimension %d with size %d" % (what, ax, x.shape[ax]))
+
+
+class _ImageDiff2D(torch.autograd.Function):
+    """images (N,C,H,W) -> (dx, dy) of calculate_image_diff (adv_morph.py:57-77)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = _dev(x, "images")
+        N, C, H, W = x.shape
+        dx, dy = torch.empty_like(x), torch.empty_like(x)
+        _lib.check(_lib.load().advchain_image_diff2d_fwd(_ptr(x), _ptr(dx), _ptr(dy), N, C, _lib.dims_array((H, W)), _stream()),
+                   "image_diff2d_fwd")
+        ctx.set_materialize_grads(False)
+        ctx.shape = tuple(x.shape)
+        return dx, dy
+
+    @staticmethod
+    def backward(ctx, gdx, gdy):
+        if gdx is None and gdy is None:
+            return None
+        gdx = None if gdx is None else _dev(gdx, "grad")
+        gdy = None if gdy is None else _dev(gdy, "grad")
+        N, C, H, W = ctx.shape
+        gin = torch.empty(ctx.shape, device=(gdx if gdx is not None else gdy).device, dtype=torch.float32)
+        _lib.check(_lib.load().advchain_image_diff2d_bwd(_ptr(gdx), _ptr(gdy), _ptr(gin), N, C, _lib.dims_array((H, W)),
+                                                         _stream()), "image_diff2d_bwd")
+        return gin
+
+
+@_on_tensor_device
+def image_diff2d(x):
+    """calculate_image_diff (adv_morph.py:57-77) of a (N,C,H,W) fp32 GPU tensor: (dx along W, dy along H)."""
+    _check_planes(x, "calculate_image_diff")
+    return _ImageDiff2D.apply(x)
+
+
+class _JacobianDet2D(torch.autograd.Function):
+    """(N,2,H,W) displacement -> (N,1,H,W) determinant of calculate_jacobian_determinant (adv_morph.py:80-100); the backward
+    recomputes the derivatives from the saved field."""
+
+    @staticmethod
+    def forward(ctx, field):
+        field = _dev(field, "data")
+        N, _, H, W = field.shape
+        det = torch.empty((N, 1, H, W), device=field.device, dtype=torch.float32)
+        _lib.check(_lib.load().advchain_jacobian_det2d_fwd(_ptr(field), _ptr(det), N, _lib.dims_array((H, W)), _stream()),
+                   "jacobian_det2d_fwd")
+        ctx.save_for_backward(field)
+        return det
+
+    @staticmethod
+    def backward(ctx, g):
+        field, = ctx.saved_tensors
+        g = _dev(g, "grad")
+        N, _, H, W = field.shape
+        gfield = torch.empty_like(field)
+        _lib.check(_lib.load().advchain_jacobian_det2d_bwd(_ptr(g), _ptr(field), _ptr(gfield), N, _lib.dims_array((H, W)),
+                                                           _stream()), "jacobian_det2d_bwd")
+        return gfield
+
+
+@_on_tensor_device
+def jacobian_det2d(field):
+    _check_planes(field, "calculate_jacobian_determinant")
+    return _JacobianDet2D.apply(field)
+
+
+def raw_expo_start(duv, inv):
+    """phi0 = identity + duv * inv (the start field of vectorFieldExponentiation{2,3}D, adv_morph.py:126-130,153-163)."""
+    phi0 = torch.empty_like(duv)
+    _lib.check(_lib.load().advchain_expo_start(_ptr(duv), _ptr(phi0), float(inv), duv.shape[0], duv.dim() - 2,
+                                               _lib.dims_array(duv.shape[2:]), _stream()), "expo_start")
+    return phi0
+
+
+def sum_of_squares(x):
+    """sum(x^2) as a 1-element device tensor, reduced in a fixed order (bitwise the same for the same x)."""
+    x = _dev(x, "tensor")
+    partials = torch.empty(1024, device=x.device, dtype=torch.float32)     # ADVCHAIN_SUMSQ_PARTIALS
+    out = torch.empty(1, device=x.device, dtype=torch.float32)
+    _lib.check(_lib.load().advchain_sumsq_ordered(_ptr(x), x.numel(), _ptr(partials), _ptr(out), _stream()), "sumsq_ordered")
+    return out
+
+
+class _ExpoStart(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, duv, inv):
+        ctx.inv = inv
+        return raw_expo_start(_dev(duv, "duv"), inv)
+
+    @staticmethod
+    def backward(ctx, g):
+        return raw_axpy(None, _dev(g, "grad"), ctx.inv), None
+
+
+class _FieldExponential(torch.autograd.Function):
+    """Scaling and squaring of vectorFieldExponentiation{2,3}D (adv_morph.py:116-177) with its aliasing quirk (Q1): returns
+    phi_n - phi_0, phi_0 = id + duv / 2^n, phi_{m+1} = phi_m o phi_m.  The squarings are advchain_compose_self_fwd calls (no
+    hint: the kernel choice does not change the values), the subtraction advchain_axpy.  phi_0 .. phi_{n-1} are kept only when
+    a gradient is wanted.  The backward is advchain_expo_chain_bwd with a FIXED halo per squaring (2D: 0, the window scatter;
+    3D: 2, the same): nothing measured selects the kernels, and in deterministic mode two backward calls are bitwise equal."""
+
+    @staticmethod
+    def forward(ctx, duv, n, keep):
+        N, d = duv.shape[:2]
+        ctx.n, ctx.inv = n, 2.0 ** (-n)
+        phi0 = raw_expo_start(duv, ctx.inv)
+        if n <= 0:          # no squaring: phi - grid_wh of one aliased tensor
+            return raw_axpy(phi0, phi0, -1.0)
+        fields = torch.empty((n - 1,) + tuple(phi0.shape), device=phi0.device, dtype=torch.float32) if keep else None
+        lib, dims = _lib.load(), _lib.dims_array(phi0.shape[2:])
+        phi = phi0
+        for m in range(1, n + 1):
+            nxt = fields[m - 1] if (keep and m < n) else torch.empty_like(phi0)
+            _lib.check(lib.advchain_compose_self_fwd(_ptr(phi), _ptr(nxt), None, N, d, dims, 0, None, _stream()),
+                       "compose_self_fwd")
+            phi = nxt
+        if keep:
+            ctx.save_for_backward(phi0, fields)
+        return raw_axpy(phi, phi0, -1.0)
+
+    @staticmethod
+    def backward(ctx, g):
+        g = _dev(g, "grad")
+        n = ctx.n
+        if n <= 0:
+            return torch.zeros_like(g), None, None
+        phi0, fields = ctx.saved_tensors
+        N, d = phi0.shape[:2]
+        ws = _scatter_workspace(N, phi0.shape[2:], phi0.device)
+        gphi0 = torch.empty_like(phi0)
+        scratch = torch.empty_like(phi0) if n > 1 else None
+        halos = (ctypes.c_int32 * n)(*([0 if d == 2 else 2] * n))
+        _lib.check(_lib.load().advchain_expo_chain_bwd(_ptr(g), _ptr(phi0), _ptr(fields) if n > 1 else None, _ptr(gphi0),
+                                                       _ptr(scratch), _ptr(ws), halos, N, d, _lib.dims_array(phi0.shape[2:]), n,
+                                                       _stream()), "expo_chain_bwd")
+        # phi_0 also enters through '- phi_0' (Q1); d phi_0 / d duv = 2^-n
+        return raw_axpy(None, raw_axpy(gphi0, g, -1.0), ctx.inv), None, None
+
+
+def _resolve_device(device, like):
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if dev != like.device:
+        raise RuntimeError("Expected all tensors to be on the same device, but found at least two devices, %s and %s!"
+                           % (dev, like.device))
+
+
+def field_exponentiation(duv, nb_steps, scaling_squaring, device, nd):
+    """vectorFieldExponentiation{2,3}D (adv_morph.py:116-177) of a (N,nd,...) fp32 velocity on its GPU.  3D: the step count
+    grows while the whole-batch Frobenius norm of duv / 2^n exceeds 0.5 (Q2; one read-back of a fixed-order sum).  Euler steps
+    (2D only; the caller raises for 3D) run through the sampler.  `device` ('cuda' = the CURRENT device, as for the reference's
+    grid) must be duv's."""
+    duv = _dev(duv, "duv")
+    if duv.dim() != nd + 2 or duv.shape[1] != nd:
+        raise RuntimeError("vectorFieldExponentiation%dD: expected a velocity of shape (N, %d, ...), got %s"
+                           % (nd, nd, tuple(duv.shape)))
+    _resolve_device(device, duv)
+    return _field_exponentiation(duv, nb_steps, scaling_squaring, nd)
+
+
+@_on_tensor_device
+def _field_exponentiation(duv, nb_steps, scaling_squaring, nd):
+    n = int(nb_steps)
+    if nd == 3:
+        nrm = float(np.sqrt(np.float32(sum_of_squares(duv).item()), dtype=np.float32))
+        while nrm / (2.0 ** n) > 0.5:
+            n += 1
+    if not scaling_squaring:       # Euler: phi <- phi_0 o phi, n times (adv_morph.py:136-141)
+        phi0 = _ExpoStart.apply(duv, 2.0 ** (-n))
+        phi = phi0
+        for _ in range(n):
+            phi = grid_sample(phi0, phi, "bilinear", "border")
+        return axpy(phi, phi0, -1.0)
+    keep = torch.is_grad_enabled() and duv.requires_grad
+    return _FieldExponential.apply(duv, n, keep)

@@ -482,6 +482,33 @@ int advchain_contour_bwd(const float* R, const float* grad_scale, float* grad_in
  *           out (N, depth, V) fp32, planar; a label outside [0, depth) gives a NaN column.                                   */
 int advchain_one_hot(const int64_t* labels, float* out, int64_t N, int64_t depth, int64_t V, void* stream);
 
+/* ---- deformation helpers (deform_diff.hip) -----------------------------------------------------------------------------
+ * The module-level helpers of adv_morph.py that users call to inspect or regularise a deformation.  H and W at least 2 (the
+ * reference raises IndexError at 1), N < 65536.  Forwards round once per ATen op of the reference, in its order (no
+ * contraction): bit for bit the reference's fp32 values.  Backwards are gathers (no atomics): bitwise reproducible.        */
+/* replaces: calculate_image_diff, adv_morph.py:57-77.  in (N,C,H,W) -> dx (along W), dy (along H), both (N,C,H,W): the central
+ *           difference 0.5 (v[i+1] - v[i-1]) inside, one-sided differences at the first and last column / row.  12 B/px.     */
+int advchain_image_diff2d_fwd(const float* in, float* dx, float* dy, int64_t N, int64_t C, const int64_t* dims, void* stream);
+/* replaces: the autograd of the call above: grad_in = Dx^T grad_dx + Dy^T grad_dy; either gradient may be NULL (zero).  12 B/px. */
+int advchain_image_diff2d_bwd(const float* grad_dx, const float* grad_dy, float* grad_in, int64_t N, int64_t C,
+                              const int64_t* dims, void* stream);
+/* replaces: calculate_jacobian_determinant(data, 'displacement'), adv_morph.py:80-100.  field (N,2,H,W) = (u, v) -> det (N,1,H,W)
+ *           = (1 + dxx)(1 + dyy) - dxy dyx with (dxx, dxy) = diff(u), (dyx, dyy) = diff(v), per pixel (the reference's units).
+ *           12 B/px.                                                                                                          */
+int advchain_jacobian_det2d_fwd(const float* field, float* det, int64_t N, const int64_t* dims, void* stream);
+/* replaces: its autograd: grad_u = Dx^T(g (1 + dyy)) - Dy^T(g dyx), grad_v = Dy^T(g (1 + dxx)) - Dx^T(g dxy), the derivatives
+ *           recomputed from `field` (no saved planes).  grad_field (N,2,H,W).  20 B/px.                                        */
+int advchain_jacobian_det2d_bwd(const float* grad_det, const float* field, float* grad_field, int64_t N, const int64_t* dims,
+                                void* stream);
+/* replaces: get_base_grid + duv / (2.0 ** nb_steps) + integrate_by_add of vectorFieldExponentiation{2,3}D (adv_morph.py:126-130,
+ *           153-163): phi0 = identity + duv * inv, inv = 2^-n (exact).  duv, phi0 (N, ndim, dims).                           */
+int advchain_expo_start(const float* duv, float* phi0, float inv, int64_t N, int ndim, const int64_t* dims, void* stream);
+/* replaces: the torch.norm(duv_interval) of vectorFieldExponentiation3D (adv_morph.py:159), squared and before the 2^-n: out[0] =
+ *           sum of x[i]^2 over n values.  One partial per workgroup into `partials` (ADVCHAIN_SUMSQ_PARTIALS floats), then
+ *           one workgroup adds them in a fixed order: out[0] is a deterministic function of x.                               */
+#define ADVCHAIN_SUMSQ_PARTIALS 1024
+int advchain_sumsq_ordered(const float* x, int64_t n, float* partials, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
