@@ -13,14 +13,14 @@ import torch
 
 from .. import ops
 
-MAX_CLASSES = 16      # kMaxK of csrc/loss.hip: the fused kernels keep one softmax row per voxel in registers
+MAX_CLASSES = 65535   # the C ABI's range (include/advchain_hip.h): up to 16 classes run csrc/loss.hip, more csrc/loss_wide.hip
 
 
 def _check_operands(output, reference):
     """The restrictions of the fused kernels, stated where the user meets them (INTEGRATION.md "Known deviations"): fp32
-    ROCm tensors (no CPU path -- ops raises), at most MAX_CLASSES channels, gradient w.r.t. the prediction only."""
+    ROCm tensors (no CPU path -- ops raises), fewer than 65536 channels, gradient w.r.t. the prediction only."""
     if output.size(1) > MAX_CLASSES:
-        raise NotImplementedError('the fused consistency kernels take at most %d classes, got %d'
+        raise NotImplementedError('the consistency kernels take at most %d classes, got %d'
                                   % (MAX_CLASSES, output.size(1)))
     if torch.is_grad_enabled() and isinstance(reference, torch.Tensor) and reference.requires_grad:
         warnings.warn('advchain_amd: the consistency loss is differentiated w.r.t. the prediction only; the reference '

@@ -1,0 +1,400 @@
+// Segmentation-consistency loss ('mse' + 'contour' + 'kl') for a RUN-TIME class count, gfx950.
+//
+//   advchain_consistency_wide_fwd/bwd <- calc_segmentation_consistency + contour_loss + kl_divergence,
+//                                        advchain/common/loss.py:8-87,102-220,223-249 (Q13, Q14)
+//
+// Same mathematics as loss.hip (see its header); what differs is that nothing here is sized by K.  loss.hip keeps a softmax
+// row per voxel in registers (K <= 16) or materialises P and D; here the class axis is MARCHED:
+//
+//   k_wide_stats   one streaming pass with a running max / sum of exp over the K planes leaves the softmax statistics of
+//                  both operands, 16 bytes per voxel: stats (N, 4, V) = max_pred, 1 / sum_pred, max_ref, 1 / sum_ref.  With
+//                  them every class plane is independent: P_k(v) = exp(pred_k(v) - max(v)) * inv(v), the arithmetic of
+//                  loss.hip's kernels.  A second sweep over k adds up the 'mse' and 'kl' sums.
+//   k_wide_edge    a workgroup owns a spatial tile (2D 64 x 8, 3D 32 x 8 x 4 outputs) and marches over the classes 1..K-1:
+//                  D_k = P_k - T_k on the tile and a one-voxel halo goes into LDS (two buffers, one barrier per class), the
+//                  3^d stencils read it there.  The statistics of a thread's halo voxels stay in its registers over the march.
+//                  Writes R (kept for the backward) and the two edge energies.
+//   k_wide_bwd     the same tile, two sweeps over the classes.  First: g_k = gs (c_mse 2 m^2 D_k + c_a A^T R_A + c_b B^T R_B)
+//                  (R_k tile + halo through LDS) goes into grad_pred, and dot = sum_k g_k P_k, sum_k m_k T'_k stay in
+//                  registers.  Second: grad_k = P_k (g_k - dot) + kl part, in place -- a thread re-reads only what it
+//                  wrote itself.  No atomics on grad_pred: bit-reproducible.
+//
+// Saved per evaluation: stats 16 V N bytes and R 8 (K - 1) V N bytes; P and D (8 K V N bytes) never exist.
+// Streaming + 3^d stencil: memory-bound, no MFMA.
+#include "loss_common.h"
+
+namespace advchain {
+
+template <int VEC>
+__device__ __forceinline__ void wload(const float* __restrict__ p, float (&o)[VEC]) {
+  if (VEC == 4) {
+    const float4 a = *reinterpret_cast<const float4*>(p);
+    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
+  } else {
+    o[0] = p[0];
+  }
+}
+template <int VEC>
+__device__ __forceinline__ void wstore(float* __restrict__ p, const float (&o)[VEC]) {
+  if (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]);
+  else p[0] = o[0];
+}
+
+// running max / sum of exp(x - max): ONE exp per element (the other factor of the usual two is exp(0))
+__device__ __forceinline__ void online_step(float x, float& mx, float& s) {
+  const float d = x - mx;
+  const float e = ADVCHAIN_SM_EXP(-fabsf(d));
+  if (d > 0.f) { s = s * e + 1.f; mx = x; }
+  else s += e;
+}
+
+// VEC voxels per lane (4: 16-byte loads, V % 4 == 0 and 16-byte aligned tensors)
+template <int VEC>
+__global__ void __launch_bounds__(kBlock)
+k_wide_stats(const float* __restrict__ pred, const float* __restrict__ ref, const float* __restrict__ mask,
+             float* __restrict__ stats, float* __restrict__ sums, int K, int V, int mask_ch, int ref_is_prob, int want_kl) {
+  __shared__ float smem[8];
+  const int n = blockIdx.y;
+  const int v = (blockIdx.x * kBlock + threadIdx.x) * VEC;
+  float acc[2] = {0.f, 0.f};
+  if (v < V) {
+    const float* pn = pred + (int64_t)n * K * V + v;
+    const float* rn = ref + (int64_t)n * K * V + v;
+    float mp[VEC], sp[VEC], mr[VEC], sr[VEC];
+    wload<VEC>(pn, mp);
+    wload<VEC>(rn, mr);
+#pragma unroll
+    for (int q = 0; q < VEC; ++q) { sp[q] = 1.f; sr[q] = 1.f; }
+    for (int k = 1; k < K; ++k) {
+      float a[VEC], b[VEC];
+      wload<VEC>(pn + (int64_t)k * V, a);
+      wload<VEC>(rn + (int64_t)k * V, b);
+#pragma unroll
+      for (int q = 0; q < VEC; ++q) {
+        online_step(a[q], mp[q], sp[q]);
+        if (!ref_is_prob) online_step(b[q], mr[q], sr[q]);
+      }
+    }
+    float isp[VEC], isr[VEC], lsp[VEC], lsr[VEC];
+#pragma unroll
+    for (int q = 0; q < VEC; ++q) {
+      isp[q] = 1.f / sp[q];                      // ONE division per voxel and side
+      isr[q] = 1.f / sr[q];
+      lsp[q] = want_kl ? logf(sp[q]) : 0.f;
+      lsr[q] = want_kl ? logf(sr[q]) : 0.f;
+    }
+    float m1[VEC];
+#pragma unroll
+    for (int q = 0; q < VEC; ++q) m1[q] = 1.f;
+    if (mask && mask_ch == 1) wload<VEC>(mask + (int64_t)n * V + v, m1);
+    for (int k = 0; k < K; ++k) {
+      float a[VEC], b[VEC], m[VEC];
+      wload<VEC>(pn + (int64_t)k * V, a);
+      wload<VEC>(rn + (int64_t)k * V, b);
+      if (mask && mask_ch > 1) wload<VEC>(mask + ((int64_t)n * mask_ch + k) * V + v, m);
+#pragma unroll
+      for (int q = 0; q < VEC; ++q) {
+        const float zp = a[q] - mp[q], zr = b[q] - mr[q];
+        const float p = mul_nc(ADVCHAIN_SM_EXP(zp), isp[q]);
+        const float t = ref_is_prob ? b[q] : mul_nc(ADVCHAIN_SM_EXP(zr), isr[q]);
+        const float mm = (mask && mask_ch > 1) ? m[q] : m1[q];
+        const float e = p * mm - t * mm;
+        acc[0] += e * e;
+        if (want_kl) acc[1] += kl_term(t, zr - lsr[q], zp - lsp[q], mm, ref_is_prob);
+      }
+    }
+    float* sn = stats + (int64_t)n * 4 * V + v;
+    wstore<VEC>(sn, mp);
+    wstore<VEC>(sn + V, isp);
+    wstore<VEC>(sn + 2 * (int64_t)V, mr);
+    wstore<VEC>(sn + 3 * (int64_t)V, isr);
+  }
+  block_sum<2>(acc, smem);
+  if (threadIdx.x == 0) {
+    atomic_add_f32(sums + sum_slot(), acc[0]);
+    if (want_kl) atomic_add_f32(sums + 3 * kSumSlots + sum_slot(), acc[1]);
+  }
+}
+
+// The spatial tile of a workgroup and its one-voxel halo.  256 threads: OUTS outputs and SLOTS halo voxels per thread.
+template <int DIM>
+struct WTile {
+  static constexpr int TX = DIM == 2 ? 64 : 32, TY = 8, TZ = DIM == 2 ? 1 : 4;
+  static constexpr int HX = TX + 2, HY = TY + 2, HZ = DIM == 2 ? 1 : TZ + 2;
+  static constexpr int NH = HX * HY * HZ, NO = TX * TY * TZ;
+  static constexpr int SLOTS = (NH + kBlock - 1) / kBlock, OUTS = NO / kBlock;
+  int x0, y0, z0;
+  __device__ __forceinline__ WTile(const Dims& d) {
+    const int tx = (d.s2 + TX - 1) / TX, ty = (d.s1 + TY - 1) / TY;
+    const int b = blockIdx.x;
+    x0 = (b % tx) * TX;
+    y0 = ((b / tx) % ty) * TY;
+    z0 = (b / (tx * ty)) * TZ;
+  }
+  // volume index of halo slot e, or -1 (outside the volume or past the last slot)
+  __device__ __forceinline__ int halo_voxel(int e, const Dims& d) const {
+    const int hx = e % HX, hy = (e / HX) % HY, hz = e / (HX * HY);
+    const int gx = x0 + hx - 1, gy = y0 + hy - 1, gz = DIM == 3 ? z0 + hz - 1 : 0;
+    const bool in = e < NH && gx >= 0 && gx < d.s2 && gy >= 0 && gy < d.s1 && gz >= 0 && gz < d.s0;
+    return in ? (gz * d.s1 + gy) * d.s2 + gx : -1;
+  }
+  // output o of the tile: its volume index (-1 outside) and the LDS index of its (-1,-1,-1) neighbour
+  __device__ __forceinline__ int out_voxel(int o, const Dims& d, int& corner) const {
+    const int ox = o % TX, oy = (o / TX) % TY, oz = o / (TX * TY);
+    corner = (oz * HY + oy) * HX + ox;
+    const int gx = x0 + ox, gy = y0 + oy, gz = z0 + oz;
+    return (gx < d.s2 && gy < d.s1 && gz < d.s0) ? (gz * d.s1 + gy) * d.s2 + gx : -1;
+  }
+  static int64_t count(const Dims& d) {
+    return (int64_t)((d.s2 + TX - 1) / TX) * ((d.s1 + TY - 1) / TY) * ((d.s0 + TZ - 1) / TZ);
+  }
+};
+
+// The two 3^d stencils of one output from an LDS tile (`corner`: index of the output's (-1,-1,-1) neighbour), taps in the
+// order of loss.hip's kernels.  FLIP: the adjoint (tap a reads the voxel at u - (a - 1)).
+// (3D, measured: a thread's four outputs are a column along z, and sharing the in-plane sums of its six planes -- 54 LDS
+// reads per stencil instead of 4 x 27 -- costs 192 VGPRs and was slower in the forward and no faster in the backward than
+// this form at 4 x 20 x 128 x 128 x 64: not kept, LESSONS 79.)
+template <int DIM, bool FLIP>
+__device__ __forceinline__ void tile_stencil(const float* __restrict__ bufa, const float* __restrict__ bufb, int corner,
+                                             float& ga, float& gb) {
+  using T = WTile<DIM>;
+  float sa = 0.f, sb = 0.f;
+#pragma unroll
+  for (int a0 = (DIM == 3 ? 0 : 1); a0 < (DIM == 3 ? 3 : 2); ++a0)
+#pragma unroll
+    for (int a1 = 0; a1 < 3; ++a1)
+#pragma unroll
+      for (int a2 = 0; a2 < 3; ++a2) {
+        float wa, wb;
+        stencil_w<DIM>(a0, a1, a2, wa, wb);
+        const int p0 = DIM == 3 ? (FLIP ? 2 - a0 : a0) : 0;
+        const int q = corner + (p0 * T::HY + (FLIP ? 2 - a1 : a1)) * T::HX + (FLIP ? 2 - a2 : a2);
+        sa += wa * bufa[q];
+        sb += wb * bufb[q];
+      }
+  ga = sa;
+  gb = sb;
+}
+
+template <int DIM>
+__global__ void __launch_bounds__(kBlock)
+k_wide_edge(const float* __restrict__ pred, const float* __restrict__ ref, const float* __restrict__ mask,
+            const float* __restrict__ stats, float* __restrict__ R, float* __restrict__ sums, int K, Dims d, int mask_ch,
+            int ref_is_prob) {
+  using T = WTile<DIM>;
+  __shared__ float lds[2][T::NH];
+  __shared__ float smem[8];
+  const T tile(d);
+  const int n = blockIdx.y;
+  const int V = (int)d.voxels();
+  const float* sn = stats + (int64_t)n * 4 * V;
+  int hv[T::SLOTS];
+  float hmp[T::SLOTS], hip_[T::SLOTS], hmr[T::SLOTS], hir[T::SLOTS];
+#pragma unroll
+  for (int j = 0; j < T::SLOTS; ++j) {
+    hv[j] = tile.halo_voxel(threadIdx.x + j * kBlock, d);
+    const int c = max(hv[j], 0);
+    hmp[j] = sn[c];
+    hip_[j] = sn[(int64_t)V + c];
+    hmr[j] = sn[2 * (int64_t)V + c];
+    hir[j] = sn[3 * (int64_t)V + c];
+  }
+  int ov[T::OUTS], oc[T::OUTS];
+  float om[T::OUTS];
+#pragma unroll
+  for (int j = 0; j < T::OUTS; ++j) {
+    ov[j] = tile.out_voxel(threadIdx.x + j * kBlock, d, oc[j]);
+    om[j] = (mask && ov[j] >= 0) ? mask[(int64_t)n * mask_ch * V + ov[j]] : 1.f;   // the stencil terms read channel 0
+  }
+  float acc[2] = {0.f, 0.f};
+  for (int k = 1; k < K; ++k) {
+    const float* pk = pred + ((int64_t)n * K + k) * V;
+    const float* rk = ref + ((int64_t)n * K + k) * V;
+    float* buf = lds[k & 1];
+#pragma unroll
+    for (int j = 0; j < T::SLOTS; ++j) {
+      const int e = threadIdx.x + j * kBlock;
+      const int c = max(hv[j], 0);
+      const float xp = pk[c], xr = rk[c];          // unconditional loads from a clamped index: all in flight together
+      const float p = mul_nc(ADVCHAIN_SM_EXP(xp - hmp[j]), hip_[j]);
+      const float t = ref_is_prob ? xr : mul_nc(ADVCHAIN_SM_EXP(xr - hmr[j]), hir[j]);
+      if (e < T::NH) buf[e] = hv[j] >= 0 ? p - t : 0.f;      // zero padding of the convolution
+    }
+    __syncthreads();     // (the other buffer is written next: one barrier per class)
+#pragma unroll
+    for (int j = 0; j < T::OUTS; ++j) {
+      float ga, gb;
+      tile_stencil<DIM, false>(buf, buf, oc[j], ga, gb);
+      if (ov[j] >= 0) {
+        const float m = om[j];
+        const float ea = ga * m, eb = gb * m;
+        acc[0] += ea * ea;
+        acc[1] += eb * eb;
+        if (R) {
+          R[((int64_t)n * 2 * (K - 1) + 2 * (k - 1)) * V + ov[j]] = 2.f * m * m * ga;
+          R[((int64_t)n * 2 * (K - 1) + 2 * (k - 1) + 1) * V + ov[j]] = 2.f * m * m * gb;
+        }
+      }
+    }
+  }
+  block_sum<2>(acc, smem);
+  if (threadIdx.x == 0) {
+    atomic_add_f32(sums + kSumSlots + sum_slot(), acc[0]);
+    atomic_add_f32(sums + 2 * kSumSlots + sum_slot(), acc[1]);
+  }
+}
+
+template <int DIM>
+__global__ void __launch_bounds__(kBlock)
+k_wide_bwd(const float* __restrict__ pred, const float* __restrict__ ref, const float* __restrict__ stats,
+           const float* __restrict__ R, const float* __restrict__ mask, const float* __restrict__ gscale, float* gpred,
+           float c_mse, float c_a, float c_b, float c_kl, int ref_is_prob, int K, Dims d, int mask_ch) {
+  using T = WTile<DIM>;
+  __shared__ float lds[2][2][T::NH];
+  const T tile(d);
+  const int n = blockIdx.y;
+  const int V = (int)d.voxels();
+  const float gs = gscale ? gscale[0] : 1.f;
+  const float* sn = stats + (int64_t)n * 4 * V;
+  int hv[T::SLOTS];
+#pragma unroll
+  for (int j = 0; j < T::SLOTS; ++j) hv[j] = tile.halo_voxel(threadIdx.x + j * kBlock, d);
+  int ov[T::OUTS], oc[T::OUTS];
+  float omp[T::OUTS], oip[T::OUTS], omr[T::OUTS], oir[T::OUTS], om[T::OUTS], dot[T::OUTS], klS[T::OUTS];
+#pragma unroll
+  for (int j = 0; j < T::OUTS; ++j) {
+    ov[j] = tile.out_voxel(threadIdx.x + j * kBlock, d, oc[j]);
+    const int c = max(ov[j], 0);
+    omp[j] = sn[c];
+    oip[j] = sn[(int64_t)V + c];
+    omr[j] = sn[2 * (int64_t)V + c];
+    oir[j] = sn[3 * (int64_t)V + c];
+    om[j] = (mask && mask_ch == 1) ? mask[(int64_t)n * V + c] : 1.f;
+    dot[j] = 0.f;
+    klS[j] = 0.f;
+  }
+  const bool edges = R != nullptr;
+  for (int k = 0; k < K; ++k) {
+    const int64_t plane = ((int64_t)n * K + k) * V;
+    float (*buf)[T::NH] = lds[k & 1];
+    if (edges && k >= 1) {
+      const float* Ra = R + ((int64_t)n * 2 * (K - 1) + 2 * (k - 1)) * V;
+      const float* Rb = Ra + V;
+#pragma unroll
+      for (int j = 0; j < T::SLOTS; ++j) {
+        const int e = threadIdx.x + j * kBlock;
+        const int c = max(hv[j], 0);
+        const float ra = Ra[c], rb = Rb[c];
+        if (e < T::NH) {
+          buf[0][e] = hv[j] >= 0 ? ra : 0.f;
+          buf[1][e] = hv[j] >= 0 ? rb : 0.f;
+        }
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < T::OUTS; ++j) {
+      const int c = max(ov[j], 0);
+      const float xp = pred[plane + c], xr = ref[plane + c];
+      const float m = (mask && mask_ch > 1) ? mask[((int64_t)n * mask_ch + k) * V + c] : om[j];
+      const float p = mul_nc(ADVCHAIN_SM_EXP(xp - omp[j]), oip[j]);
+      const float t = ref_is_prob ? xr : mul_nc(ADVCHAIN_SM_EXP(xr - omr[j]), oir[j]);
+      float g = c_mse * 2.f * m * m * (p - t);
+      if (edges && k >= 1) {
+        float ta, tb;                 // A^T R_A, B^T R_B (R is zero outside the volume)
+        tile_stencil<DIM, true>(buf[0], buf[1], oc[j], ta, tb);
+        g += c_a * ta + c_b * tb;
+      }
+      g *= gs;
+      if (ov[j] >= 0) gpred[plane + c] = g;
+      dot[j] += g * p;
+      if (c_kl != 0.f) klS[j] += m * kl_prob(t, ref_is_prob);
+    }
+  }
+  // second sweep: the softmax Jacobian, in place (every thread re-reads only its own stores)
+  for (int k = 0; k < K; ++k) {
+    const int64_t plane = ((int64_t)n * K + k) * V;
+#pragma unroll
+    for (int j = 0; j < T::OUTS; ++j) {
+      if (ov[j] < 0) continue;
+      const int c = ov[j];
+      const float xp = pred[plane + c];
+      const float p = mul_nc(ADVCHAIN_SM_EXP(xp - omp[j]), oip[j]);
+      float g = p * (gpred[plane + c] - dot[j]);
+      if (c_kl != 0.f) {   // 'kl': gs c_kl (P_j sum_k m_k T'_k - m_j T'_j)
+        const float xr = ref[plane + c];
+        const float t = ref_is_prob ? xr : mul_nc(ADVCHAIN_SM_EXP(xr - omr[j]), oir[j]);
+        const float m = (mask && mask_ch > 1) ? mask[((int64_t)n * mask_ch + k) * V + c] : om[j];
+        g += gs * c_kl * (p * klS[j] - m * kl_prob(t, ref_is_prob));
+      }
+      gpred[plane + c] = g;
+    }
+  }
+}
+
+}  // namespace advchain
+
+using namespace advchain;
+
+static inline bool wide_nk_ok(int64_t N, int64_t K) { return N >= 0 && N < 65536 && K >= 1 && K < 65536; }
+
+extern "C" {
+
+int advchain_consistency_wide_fwd(const float* pred, const float* ref, const float* mask, float* stats, float* R, float* sums,
+                                  int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels, int ref_is_prob,
+                                  int want_edges, int want_kl, void* stream) {
+  ADVCHAIN_CHECK_ARG(pred && ref && stats && sums && dims, "consistency_wide_fwd: null pointer");
+  ADVCHAIN_CHECK_ARG(ldims_ok(ndim, dims), "consistency_wide_fwd: bad dims");
+  ADVCHAIN_CHECK_ARG(wide_nk_ok(N, K), "consistency_wide_fwd: bad N/K (N < 65536, 1 <= K < 65536)");
+  ADVCHAIN_CHECK_ARG(!mask || mask_channels == 1 || mask_channels == K, "consistency_wide_fwd: mask must have 1 or K channels");
+  const Dims d = lmake_dims(ndim, dims);
+  ADVCHAIN_CHECK_ARG(d.voxels() < (1ll << 31), "consistency_wide_fwd: volume too large");
+  if (N == 0) return ADVCHAIN_OK;
+  const int V = (int)d.voxels();
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 b(kBlock);
+  const bool al16 = ((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(ref) | reinterpret_cast<uintptr_t>(mask) |
+                      reinterpret_cast<uintptr_t>(stats)) & 15) == 0;
+  if (V % 4 == 0 && al16)
+    hipLaunchKernelGGL(k_wide_stats<4>, dim3(advchain_blocks(V / 4, kBlock), (unsigned)N), b, 0, st, pred, ref, mask, stats,
+                       sums, (int)K, V, mask_channels, ref_is_prob, want_kl);
+  else
+    hipLaunchKernelGGL(k_wide_stats<1>, dim3(advchain_blocks(V, kBlock), (unsigned)N), b, 0, st, pred, ref, mask, stats,
+                       sums, (int)K, V, mask_channels, ref_is_prob, want_kl);
+  if (want_edges && K > 1) {
+    if (ndim == 3)
+      hipLaunchKernelGGL(k_wide_edge<3>, dim3((unsigned)WTile<3>::count(d), (unsigned)N), b, 0, st, pred, ref, mask, stats, R,
+                         sums, (int)K, d, mask_channels, ref_is_prob);
+    else
+      hipLaunchKernelGGL(k_wide_edge<2>, dim3((unsigned)WTile<2>::count(d), (unsigned)N), b, 0, st, pred, ref, mask, stats, R,
+                         sums, (int)K, d, mask_channels, ref_is_prob);
+  }
+  ADVCHAIN_LAUNCH_CHECK();
+  return ADVCHAIN_OK;
+}
+
+int advchain_consistency_wide_bwd(const float* pred, const float* ref, const float* stats, const float* R, const float* mask,
+                                  const float* grad_scale, float* grad_pred, float c_mse, float c_a, float c_b, float c_kl,
+                                  int ref_is_prob, int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels,
+                                  void* stream) {
+  ADVCHAIN_CHECK_ARG(pred && ref && stats && grad_pred && dims, "consistency_wide_bwd: null pointer");
+  ADVCHAIN_CHECK_ARG(ldims_ok(ndim, dims), "consistency_wide_bwd: bad dims");
+  ADVCHAIN_CHECK_ARG(wide_nk_ok(N, K), "consistency_wide_bwd: bad N/K (N < 65536, 1 <= K < 65536)");
+  ADVCHAIN_CHECK_ARG(!mask || mask_channels == 1 || mask_channels == K, "consistency_wide_bwd: mask must have 1 or K channels");
+  const Dims d = lmake_dims(ndim, dims);
+  ADVCHAIN_CHECK_ARG(d.voxels() < (1ll << 31), "consistency_wide_bwd: volume too large");
+  if (N == 0) return ADVCHAIN_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (K == 1) R = nullptr;        // (no object class: nothing was saved)
+  if (ndim == 3)
+    hipLaunchKernelGGL(k_wide_bwd<3>, dim3((unsigned)WTile<3>::count(d), (unsigned)N), dim3(kBlock), 0, st, pred, ref, stats, R,
+                       mask, grad_scale, grad_pred, c_mse, c_a, c_b, c_kl, ref_is_prob, (int)K, d, mask_channels);
+  else
+    hipLaunchKernelGGL(k_wide_bwd<2>, dim3((unsigned)WTile<2>::count(d), (unsigned)N), dim3(kBlock), 0, st, pred, ref, stats, R,
+                       mask, grad_scale, grad_pred, c_mse, c_a, c_b, c_kl, ref_is_prob, (int)K, d, mask_channels);
+  ADVCHAIN_LAUNCH_CHECK();
+  return ADVCHAIN_OK;
+}
+
+}  // extern "C"

@@ -184,6 +184,8 @@ ADAPTIVE_HALO = os.environ.get("ADVCHAIN_NO_ADAPTIVE_HALO") is None   # measure 
 PAIR_FIELDS = os.environ.get("ADVCHAIN_NO_PAIR_FIELDS") is None       # a solver step integrates field(+v) and field(-v) as one batch
 TILED_SCATTER = True  # LDS-tiled owner-computes scatter (False: global-atomic kernels; for A/B tests)
 FUSED_LOSS = True     # the consistency loss straight from the logits (no P / D intermediates); False: A/B tests
+WIDE_LOSS_MIN_K = 17  # class counts from here on take the run-time-K loss kernels (loss_wide.hip: any K < 65536, no P / D); below:
+                      # the K <= 16 kernels of loss.hip, unchanged.  Tests and tools lower it to compare the two implementations
 FUSE_2D = True        # the leading sub-pixel squarings of a 2D chain in one launch (expo_fused2d.hip); False: A/B tests
 COMPOSITE = True      # a paired 2D DemonsCompose direction as ONE C call (demons_compose.cpp: same launches); False: A/B tests
 RIDE_MASK = True      # the solver's validity mask rides through the data's warps (one launch for both); False: A/B tests
@@ -1572,30 +1574,44 @@ class _Consistency(torch.autograd.Function):
         value = torch.empty((), device=pred.device, dtype=torch.float32)
         slots = _persistent_zeros("loss", (4, 64), pred.device)   # per-workgroup partials, 64 slots per sum; zeroed by the finisher
         lib = _lib.load()
+        wide = K >= WIDE_LOSS_MIN_K
+        stats = None
         try:
-            # f2 fused: one marching kernel straight from the logits, nothing saved but R (K = 2..4, rows of 4j <= 256 voxels)
-            rc = lib.advchain_consistency_fused_fwd(_ptr(pred), _ptr(ref), _ptr(mask), _ptr(R), _ptr(slots), N, K, nd, dims, mch,
-                                                    int(ref_is_prob), int(want_edges), int(want_kl), _stream()) if FUSED_LOSS else -2
-            fused = rc != -2
-            if fused:
-                _lib.check(rc, "consistency_fused_fwd")
+            if wide:
+                # run-time K: per-voxel softmax statistics of both operands instead of P and D
+                stats = torch.empty((N, 4) + tuple(pred.shape[2:]), device=pred.device, dtype=torch.float32)
+                _lib.check(lib.advchain_consistency_wide_fwd(_ptr(pred), _ptr(ref), _ptr(mask), _ptr(stats), _ptr(R), _ptr(slots),
+                                                             N, K, nd, dims, mch, int(ref_is_prob), int(want_edges),
+                                                             int(want_kl), _stream()), "consistency_wide_fwd")
+                fused = False
                 P = D = None
             else:
-                P = torch.empty_like(pred)
-                D = torch.empty_like(pred)
-                _lib.check(lib.advchain_consistency_fwd(_ptr(pred), _ptr(ref), _ptr(mask), _ptr(P), _ptr(D), _ptr(R),
-                                                        _ptr(slots), N, K, nd, dims, mch, int(ref_is_prob),
-                                                        int(want_edges), int(want_kl), _stream()), "consistency_fwd")
+                # f2 fused: one marching kernel straight from the logits, nothing saved but R (K = 2..4, rows of 4j <= 256 voxels)
+                rc = lib.advchain_consistency_fused_fwd(_ptr(pred), _ptr(ref), _ptr(mask), _ptr(R), _ptr(slots), N, K, nd, dims, mch,
+                                                        int(ref_is_prob), int(want_edges), int(want_kl), _stream()) if FUSED_LOSS else -2
+                fused = rc != -2
+                if fused:
+                    _lib.check(rc, "consistency_fused_fwd")
+                    P = D = None
+                else:
+                    P = torch.empty_like(pred)
+                    D = torch.empty_like(pred)
+                    _lib.check(lib.advchain_consistency_fwd(_ptr(pred), _ptr(ref), _ptr(mask), _ptr(P), _ptr(D), _ptr(R),
+                                                            _ptr(slots), N, K, nd, dims, mch, int(ref_is_prob),
+                                                            int(want_edges), int(want_kl), _stream()), "consistency_fwd")
             _lib.check(lib.advchain_consistency_finish(_ptr(slots), _lib.float_array(coef), _ptr(sums), _ptr(value), 1,
                                                        _stream()), "consistency_finish")
         except BaseException:
             _forget_persistent(slots)
             raise
         if need_grad:
-            if fused:
+            if wide:
+                ctx.save_for_backward(pred, ref, R, mask, stats)
+            elif fused:
                 ctx.save_for_backward(pred, ref, R, mask)
             else:
                 ctx.save_for_backward(P, D, R, mask)
+        ctx.wide = wide
         ctx.fused = fused
         ctx.cfg = (coef, mch, int(ref_is_prob))
         ctx.mark_non_differentiable(sums)
@@ -1606,8 +1622,18 @@ class _Consistency(torch.autograd.Function):
     def backward(ctx, gloss, _gsums):
         if gloss is None:
             return None, None, None, None, None, None
-        P, D, R, mask = ctx.saved_tensors              # (fused: pred, ref, R, mask)
         coef, mch, is_gt = ctx.cfg
+        if ctx.wide:
+            pred, ref, R, mask, stats = ctx.saved_tensors
+            N, K = pred.shape[:2]
+            gs = _dev(gloss.reshape(1), "grad")
+            gpred = torch.empty_like(pred)
+            _lib.check(_lib.load().advchain_consistency_wide_bwd(
+                _ptr(pred), _ptr(ref), _ptr(stats), _ptr(R), _ptr(mask), _ptr(gs), _ptr(gpred),
+                float(coef[0]), float(coef[1]), float(coef[2]), float(coef[3]), is_gt, N, K, pred.dim() - 2,
+                _lib.dims_array(pred.shape[2:]), mch, _stream()), "consistency_wide_bwd")
+            return gpred, None, None, None, None, None
+        P, D, R, mask = ctx.saved_tensors              # (fused: pred, ref, R, mask)
         N, K = P.shape[:2]
         nd = P.dim() - 2
         gs = _dev(gloss.reshape(1), "grad")

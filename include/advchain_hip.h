@@ -432,6 +432,25 @@ int advchain_consistency_fused_bwd(const float* pred, const float* ref, const fl
                                    int ref_is_prob, int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels,
                                    void* stream);
 
+/* wide (round 8): the same loss for a RUN-TIME class count, 1 <= K < 65536 -- nothing in these kernels is sized by K
+ * (replaces the same reference lines: common/loss.py:8-87,102-220,223-249; same terms, masks, ref_is_prob and slot sums as
+ * advchain_consistency_fwd, finish with advchain_consistency_finish).  wide_fwd: one streaming pass leaves the softmax
+ * statistics of both operands in stats (N, 4, dims) floats = max_pred, 1 / sum_pred, max_ref, 1 / sum_ref (the ref planes are
+ * unspecified when ref_is_prob) and adds the 'mse' and 'kl' sums; with want_edges and K > 1 a tiled kernel marching over the
+ * classes adds the edge energies and writes R (N, 2(K-1), dims) as above (NULL when no backward is needed).  P and D are
+ * never materialised.  wide_bwd: grad_pred (N,K,dims) from pred, ref, stats and R (NULL: no edge terms) by the formula of
+ * advchain_consistency_bwd, gs = *grad_scale (device scalar, NULL = 1); no atomics on grad_pred, so it is bit-reproducible.
+ * pred / ref / grad_pred fp32 contiguous, any alignment (16-byte aligned tensors with a voxel count divisible by 4 take
+ * 16-byte loads); N < 65536 (N == 0: ADVCHAIN_OK, no launch), fewer than 2^31 voxels, mask_channels 1 or K.  Capture-safe:
+ * kernel launches on `stream` only.  Returns ADVCHAIN_OK or a negative code (advchain_last_error names the entry). */
+int advchain_consistency_wide_fwd(const float* pred, const float* ref, const float* mask, float* stats, float* R, float* sums,
+                                  int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels, int ref_is_prob,
+                                  int want_edges, int want_kl, void* stream);
+int advchain_consistency_wide_bwd(const float* pred, const float* ref, const float* stats, const float* R, const float* mask,
+                                  const float* grad_scale, float* grad_pred, float c_mse, float c_a, float c_b, float c_kl,
+                                  int ref_is_prob, int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels,
+                                  void* stream);
+
 /* bf16 STORAGE experiment (round 6; BASELINE config 2 names "bf16"): the 2D K = 4 fused loss above (common/loss.py:8-87,
  * 102-220: mse + contour terms on logits) with pred / ref / R / grad_pred stored as bfloat16 (raw 16-bit words, 8-byte aligned)
  * and all arithmetic in fp32 registers.  NOT used by the product path -- the parity contract is fp32 at 1e-4; the entries exist
