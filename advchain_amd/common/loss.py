@@ -2,7 +2,8 @@
 ``contour_loss`` / ``One_Hot`` / ``cross_entropy_2D`` (loss.py:102-220, 252-326, on csrc/seg_loss.hip).
 
 'mse', 'contour' and 'kl' all run in the fused HIP kernels (:func:`advchain_amd.ops.consistency_sums`:
-softmax + mask + squared error + KL sum + 3^d edge stencils in two launches forward, one backward).
+softmax + mask + squared error + KL sum + 3^d edge stencils in two launches forward, one backward per operand that
+needs a gradient: the prediction and -- csrc/loss_ref.hip -- the reference).
 
 Batch sharding: ``global_batch`` overrides N in every normaliser -- mse ~ 1/(N^2 K V^2),
 contour ~ 1/(N V) -- so that the per-shard values SUM to the whole-batch loss and the mse:contour mix
@@ -18,13 +19,11 @@ MAX_CLASSES = 65535   # the C ABI's range (include/advchain_hip.h): up to 16 cla
 
 def _check_operands(output, reference):
     """The restrictions of the fused kernels, stated where the user meets them (INTEGRATION.md "Known deviations"): fp32
-    ROCm tensors (no CPU path -- ops raises), fewer than 65536 channels, gradient w.r.t. the prediction only."""
+    ROCm tensors (no CPU path -- ops raises), fewer than 65536 channels.  Both operands are differentiated, as by the
+    reference's torch expression."""
     if output.size(1) > MAX_CLASSES:
         raise NotImplementedError('the consistency kernels take at most %d classes, got %d'
                                   % (MAX_CLASSES, output.size(1)))
-    if torch.is_grad_enabled() and isinstance(reference, torch.Tensor) and reference.requires_grad:
-        warnings.warn('advchain_amd: the consistency loss is differentiated w.r.t. the prediction only; the reference '
-                      'is treated as a constant (detach it to silence this warning)', stacklevel=3)
 
 
 def _pooled(x, scale):

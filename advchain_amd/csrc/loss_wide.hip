@@ -40,14 +40,6 @@ __device__ __forceinline__ void wstore(float* __restrict__ p, const float (&o)[V
   else p[0] = o[0];
 }
 
-// running max / sum of exp(x - max): ONE exp per element (the other factor of the usual two is exp(0))
-__device__ __forceinline__ void online_step(float x, float& mx, float& s) {
-  const float d = x - mx;
-  const float e = ADVCHAIN_SM_EXP(-fabsf(d));
-  if (d > 0.f) { s = s * e + 1.f; mx = x; }
-  else s += e;
-}
-
 // VEC voxels per lane (4: 16-byte loads, V % 4 == 0 and 16-byte aligned tensors)
 template <int VEC>
 __global__ void __launch_bounds__(kBlock)
@@ -114,67 +106,6 @@ k_wide_stats(const float* __restrict__ pred, const float* __restrict__ ref, cons
     atomic_add_f32(sums + sum_slot(), acc[0]);
     if (want_kl) atomic_add_f32(sums + 3 * kSumSlots + sum_slot(), acc[1]);
   }
-}
-
-// The spatial tile of a workgroup and its one-voxel halo.  256 threads: OUTS outputs and SLOTS halo voxels per thread.
-template <int DIM>
-struct WTile {
-  static constexpr int TX = DIM == 2 ? 64 : 32, TY = 8, TZ = DIM == 2 ? 1 : 4;
-  static constexpr int HX = TX + 2, HY = TY + 2, HZ = DIM == 2 ? 1 : TZ + 2;
-  static constexpr int NH = HX * HY * HZ, NO = TX * TY * TZ;
-  static constexpr int SLOTS = (NH + kBlock - 1) / kBlock, OUTS = NO / kBlock;
-  int x0, y0, z0;
-  __device__ __forceinline__ WTile(const Dims& d) {
-    const int tx = (d.s2 + TX - 1) / TX, ty = (d.s1 + TY - 1) / TY;
-    const int b = blockIdx.x;
-    x0 = (b % tx) * TX;
-    y0 = ((b / tx) % ty) * TY;
-    z0 = (b / (tx * ty)) * TZ;
-  }
-  // volume index of halo slot e, or -1 (outside the volume or past the last slot)
-  __device__ __forceinline__ int halo_voxel(int e, const Dims& d) const {
-    const int hx = e % HX, hy = (e / HX) % HY, hz = e / (HX * HY);
-    const int gx = x0 + hx - 1, gy = y0 + hy - 1, gz = DIM == 3 ? z0 + hz - 1 : 0;
-    const bool in = e < NH && gx >= 0 && gx < d.s2 && gy >= 0 && gy < d.s1 && gz >= 0 && gz < d.s0;
-    return in ? (gz * d.s1 + gy) * d.s2 + gx : -1;
-  }
-  // output o of the tile: its volume index (-1 outside) and the LDS index of its (-1,-1,-1) neighbour
-  __device__ __forceinline__ int out_voxel(int o, const Dims& d, int& corner) const {
-    const int ox = o % TX, oy = (o / TX) % TY, oz = o / (TX * TY);
-    corner = (oz * HY + oy) * HX + ox;
-    const int gx = x0 + ox, gy = y0 + oy, gz = z0 + oz;
-    return (gx < d.s2 && gy < d.s1 && gz < d.s0) ? (gz * d.s1 + gy) * d.s2 + gx : -1;
-  }
-  static int64_t count(const Dims& d) {
-    return (int64_t)((d.s2 + TX - 1) / TX) * ((d.s1 + TY - 1) / TY) * ((d.s0 + TZ - 1) / TZ);
-  }
-};
-
-// The two 3^d stencils of one output from an LDS tile (`corner`: index of the output's (-1,-1,-1) neighbour), taps in the
-// order of loss.hip's kernels.  FLIP: the adjoint (tap a reads the voxel at u - (a - 1)).
-// (3D, measured: a thread's four outputs are a column along z, and sharing the in-plane sums of its six planes -- 54 LDS
-// reads per stencil instead of 4 x 27 -- costs 192 VGPRs and was slower in the forward and no faster in the backward than
-// this form at 4 x 20 x 128 x 128 x 64: not kept, LESSONS 79.)
-template <int DIM, bool FLIP>
-__device__ __forceinline__ void tile_stencil(const float* __restrict__ bufa, const float* __restrict__ bufb, int corner,
-                                             float& ga, float& gb) {
-  using T = WTile<DIM>;
-  float sa = 0.f, sb = 0.f;
-#pragma unroll
-  for (int a0 = (DIM == 3 ? 0 : 1); a0 < (DIM == 3 ? 3 : 2); ++a0)
-#pragma unroll
-    for (int a1 = 0; a1 < 3; ++a1)
-#pragma unroll
-      for (int a2 = 0; a2 < 3; ++a2) {
-        float wa, wb;
-        stencil_w<DIM>(a0, a1, a2, wa, wb);
-        const int p0 = DIM == 3 ? (FLIP ? 2 - a0 : a0) : 0;
-        const int q = corner + (p0 * T::HY + (FLIP ? 2 - a1 : a1)) * T::HX + (FLIP ? 2 - a2 : a2);
-        sa += wa * bufa[q];
-        sb += wb * bufb[q];
-      }
-  ga = sa;
-  gb = sb;
 }
 
 template <int DIM>

@@ -186,6 +186,8 @@ TILED_SCATTER = True  # LDS-tiled owner-computes scatter (False: global-atomic k
 FUSED_LOSS = True     # the consistency loss straight from the logits (no P / D intermediates); False: A/B tests
 WIDE_LOSS_MIN_K = 17  # class counts from here on take the run-time-K loss kernels (loss_wide.hip: any K < 65536, no P / D); below:
                       # the K <= 16 kernels of loss.hip, unchanged.  Tests and tools lower it to compare the two implementations
+REF_GRAD_REG_MAX_K = 4  # the gradient w.r.t. the reference (loss_ref.hip) keeps K = 2..this many classes in registers (at most 4);
+                      # 0: the run-time-K form for every class count.  Tests and tools lower it to compare the two forms
 FUSE_2D = True        # the leading sub-pixel squarings of a 2D chain in one launch (expo_fused2d.hip); False: A/B tests
 COMPOSITE = True      # a paired 2D DemonsCompose direction as ONE C call (demons_compose.cpp: same launches); False: A/B tests
 RIDE_MASK = True      # the solver's validity mask rides through the data's warps (one launch for both); False: A/B tests
@@ -1553,7 +1555,10 @@ def demons_field_pair(vel, scale, tables, nsteps_rule, reduce_sumsq=None, opts=N
 class _Consistency(torch.autograd.Function):
     """c_mse * S0 + c_a * SA + c_b * SB + c_kl * SKL  with  S0 = sum((P m - T m)^2), SA/SB = masked edge energies,
     SKL = sum m T' (log T' - log P)  (advchain/common/loss.py:55-79,102-220,223-249).  Differentiable w.r.t. the
-    prediction logits only."""
+    prediction logits (one launch of the forward family's own backward entry) and w.r.t. the reference (one launch of
+    advchain_consistency_ref_bwd, csrc/loss_ref.hip, whichever forward family ran); each is launched only when its operand
+    needs a gradient.  A reference given as probabilities (ref_is_prob) enters 'mse' and 'contour' as it is and 'kl' through a
+    where() that cuts the graph: with 'kl' alone its gradient is None and nothing is launched.  The mask is a constant."""
 
     @staticmethod
     def forward(ctx, pred, ref, mask, coef, ref_is_prob, want_edges):
@@ -1563,7 +1568,8 @@ class _Consistency(torch.autograd.Function):
         nd = pred.dim() - 2
         dims = _lib.dims_array(pred.shape[2:])
         mch = 1 if mask is None else mask.shape[1]
-        need_grad = ctx.needs_input_grad[0]
+        need_pred, need_ref = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_grad = need_pred or need_ref
         want_kl = coef[3] != 0.0
         R = None
         if need_grad and want_edges and K > 1:
@@ -1609,8 +1615,13 @@ class _Consistency(torch.autograd.Function):
                 ctx.save_for_backward(pred, ref, R, mask, stats)
             elif fused:
                 ctx.save_for_backward(pred, ref, R, mask)
+            elif need_ref:
+                # the reference side reads the operands themselves (references to the inputs, not copies)
+                ctx.save_for_backward(P if need_pred else None, D if need_pred else None, R, mask, pred, ref)
             else:
                 ctx.save_for_backward(P, D, R, mask)
+        # ref_is_prob: 'kl' sees the reference through a where() -- without 'mse' or 'contour' it has no gradient
+        ctx.ref_grad = need_ref and not (ref_is_prob and coef[0] == 0.0 and not (want_edges and K > 1))
         ctx.wide = wide
         ctx.fused = fused
         ctx.cfg = (coef, mch, int(ref_is_prob))
@@ -1623,27 +1634,40 @@ class _Consistency(torch.autograd.Function):
         if gloss is None:
             return None, None, None, None, None, None
         coef, mch, is_gt = ctx.cfg
+        need_pred, need_ref = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and ctx.ref_grad
+        gs = _dev(gloss.reshape(1), "grad")
+        lib = _lib.load()
+        gpred = gref = stats = None
         if ctx.wide:
             pred, ref, R, mask, stats = ctx.saved_tensors
             N, K = pred.shape[:2]
-            gs = _dev(gloss.reshape(1), "grad")
-            gpred = torch.empty_like(pred)
-            _lib.check(_lib.load().advchain_consistency_wide_bwd(
-                _ptr(pred), _ptr(ref), _ptr(stats), _ptr(R), _ptr(mask), _ptr(gs), _ptr(gpred),
-                float(coef[0]), float(coef[1]), float(coef[2]), float(coef[3]), is_gt, N, K, pred.dim() - 2,
-                _lib.dims_array(pred.shape[2:]), mch, _stream()), "consistency_wide_bwd")
-            return gpred, None, None, None, None, None
-        P, D, R, mask = ctx.saved_tensors              # (fused: pred, ref, R, mask)
-        N, K = P.shape[:2]
-        nd = P.dim() - 2
-        gs = _dev(gloss.reshape(1), "grad")
-        gpred = torch.empty_like(P)
-        entry = _lib.load().advchain_consistency_fused_bwd if ctx.fused else _lib.load().advchain_consistency_bwd
-        _lib.check(entry(_ptr(P), _ptr(D), _ptr(R), _ptr(mask), _ptr(gs), _ptr(gpred),
-                         float(coef[0]), float(coef[1]), float(coef[2]), float(coef[3]),
-                         is_gt, N, K, nd, _lib.dims_array(P.shape[2:]), mch, _stream()),
-                   "consistency_fused_bwd" if ctx.fused else "consistency_bwd")
-        return gpred, None, None, None, None, None
+            if need_pred:
+                gpred = torch.empty_like(pred)
+                _lib.check(lib.advchain_consistency_wide_bwd(
+                    _ptr(pred), _ptr(ref), _ptr(stats), _ptr(R), _ptr(mask), _ptr(gs), _ptr(gpred),
+                    float(coef[0]), float(coef[1]), float(coef[2]), float(coef[3]), is_gt, N, K, pred.dim() - 2,
+                    _lib.dims_array(pred.shape[2:]), mch, _stream()), "consistency_wide_bwd")
+        else:
+            saved = ctx.saved_tensors
+            P, D, R, mask = saved[:4]                      # (fused: pred, ref, R, mask)
+            pred, ref = (P, D) if ctx.fused else (saved[4:6] if len(saved) > 4 else (None, None))
+            if need_pred:
+                N, K = P.shape[:2]
+                gpred = torch.empty_like(P)
+                entry = lib.advchain_consistency_fused_bwd if ctx.fused else lib.advchain_consistency_bwd
+                _lib.check(entry(_ptr(P), _ptr(D), _ptr(R), _ptr(mask), _ptr(gs), _ptr(gpred),
+                                 float(coef[0]), float(coef[1]), float(coef[2]), float(coef[3]),
+                                 is_gt, N, K, P.dim() - 2, _lib.dims_array(P.shape[2:]), mch, _stream()),
+                           "consistency_fused_bwd" if ctx.fused else "consistency_bwd")
+        if need_ref:
+            N, K = ref.shape[:2]
+            gref = torch.empty_like(ref)
+            lib.advchain_set_ref_grad_reg_max_k(int(REF_GRAD_REG_MAX_K))      # (process-wide in the library: the knob of this module)
+            _lib.check(lib.advchain_consistency_ref_bwd(
+                _ptr(pred), _ptr(ref), _ptr(stats), _ptr(R), _ptr(mask), _ptr(gs), _ptr(gref),
+                float(coef[0]), float(coef[1]), float(coef[2]), float(coef[3]), is_gt, N, K, ref.dim() - 2,
+                _lib.dims_array(ref.shape[2:]), mch, _stream()), "consistency_ref_bwd")
+        return gpred, gref, None, None, None, None
 
 
 @_on_tensor_device

@@ -451,6 +451,30 @@ int advchain_consistency_wide_bwd(const float* pred, const float* ref, const flo
                                   int ref_is_prob, int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels,
                                   void* stream);
 
+/* reference side (round 9): grad_ref (N,K,dims) = what autograd gives `reference` in the same expression (call site
+ * common/loss.py:8-87,223-249: calc_segmentation_consistency / kl_divergence with a reference that requires grad -- mutual
+ * consistency of two branches, a symmetric KL term, a teacher trained through the term, a soft is_gt target).  With
+ *   g_k = gs (c_mse 2 m_k^2 (P_k - T_k) + [k >= 1] (c_a A^T R_A,k + c_b B^T R_B,k))      (the probability-space gradient of
+ *                                                                                         advchain_consistency_bwd)
+ *   h_k = -g_k + gs c_kl m_k (log T_k + 1 - log P_k)
+ * ref_is_prob == 0: grad_ref_k = T_k (h_k - sum_j T_j h_j) (softmax Jacobian of the reference; log T_k - log P_k is taken from
+ * the logits and the softmax statistics); ref_is_prob != 0: grad_ref_k = -g_k -- the reference's where() cuts the graph of
+ * 'kl', c_kl is ignored and the reference's softmax is never evaluated (with 'kl' alone the gradient is zero: do not call).
+ * Independent of the forward family: pred, ref, mask as given to the forward, R (N, 2(K-1), dims) as any forward entry wrote
+ * it (NULL: no edge terms or K == 1), stats (N, 4, dims) as advchain_consistency_wide_fwd wrote it or NULL (the kernel then
+ * takes the softmax statistics of its own output voxels in a sweep over the classes; it never touches the slot sums).
+ * gs = *grad_scale (device scalar, NULL = 1).  K = 2..4 keep a thread's logits in registers and read every operand once;
+ * other K (or all K after advchain_set_ref_grad_reg_max_k(0): PROCESS-WIDE, 0..4, default 4; for tests and A/B) march over
+ * the classes twice with grad_ref as the only scratch.  No atomics: bit-reproducible in either form.  pred / ref / grad_ref
+ * fp32 contiguous, any alignment; N < 65536 (N == 0: ADVCHAIN_OK, no launch), 1 <= K < 65536, fewer than 2^31 voxels,
+ * mask_channels 1 or K.  Capture-safe: one kernel launch on `stream`.  Returns ADVCHAIN_OK or a negative code. */
+int advchain_consistency_ref_bwd(const float* pred, const float* ref, const float* stats /*nullable*/,
+                                 const float* R /*nullable*/, const float* mask, const float* grad_scale,
+                                 float* grad_ref, float c_mse, float c_a, float c_b, float c_kl, int ref_is_prob,
+                                 int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels, void* stream);
+void advchain_set_ref_grad_reg_max_k(int k);
+int advchain_get_ref_grad_reg_max_k(void);
+
 /* bf16 STORAGE experiment (round 6; BASELINE config 2 names "bf16"): the 2D K = 4 fused loss above (common/loss.py:8-87,
  * 102-220: mse + contour terms on logits) with pred / ref / R / grad_pred stored as bfloat16 (raw 16-bit words, 8-byte aligned)
  * and all arithmetic in fp32 registers.  NOT used by the product path -- the parity contract is fp32 at 1e-4; the entries exist
