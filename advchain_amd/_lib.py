@@ -72,6 +72,9 @@ PROTOTYPES = {
     "advchain_consistency_ref_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _I, _L, _L, _I, _P, _I, _P]),
     "advchain_set_ref_grad_reg_max_k": (None, [_I]),
     "advchain_get_ref_grad_reg_max_k": (_I, []),
+    "advchain_consistency_lp_fwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _L, _L, _I, _P, _I, _I, _I, _I, _P]),
+    "advchain_consistency_lp_bwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _I, _L, _L, _I, _P, _I, _P]),
+    "advchain_consistency_lp_ref_bwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _I, _L, _L, _I, _P, _I, _P]),
     "advchain_consistency_fused_fwd_bf16": (_I, [_P, _P, _P, _P, _P, _L, _L, _I, _P, _P]),
     "advchain_consistency_fused_bwd_bf16": (_I, [_P, _P, _P, _P, _P, _P, _F, _F, _F, _L, _L, _I, _P, _P]),
     "advchain_seg_loss_workspace": (_L, [_L, _I, _P]),

@@ -535,11 +535,20 @@ class ComposeAdversarialTransformSolver(object):
             t_data = torch.clamp(t_data, lo, hi)
         return t_data
 
+    @staticmethod
+    def _fp32_for_warp(data, chain):
+        """A bf16 model output (autocast) is upcast once, differentiably, before a geometric warp -- what autocast does for
+        grid_sample in the reference; the warps are fp32 kernels.  Chains without a geometric transform leave it as it is."""
+        if isinstance(data, torch.Tensor) and data.dtype == torch.bfloat16 and any(t.is_geometric() for t in chain):
+            return data.float()
+        return data
+
     def predict_forward(self, data, chain_of_transforms=None, interp=None, padding_mode=None):
         # adv_compose_solver.py:184-197
         if chain_of_transforms is None:
             chain_of_transforms = self.chain_of_transforms
         self._last_chain = list(chain_of_transforms)
+        data = self._fp32_for_warp(data, chain_of_transforms)
         for transform in chain_of_transforms:
             data = transform.predict_forward(data, interp=interp, padding_mode=padding_mode)
         return data
@@ -556,6 +565,7 @@ class ComposeAdversarialTransformSolver(object):
         # adv_compose_solver.py:210-219
         if chain_of_transforms is None:
             chain_of_transforms = self.chain_of_transforms
+        data = self._fp32_for_warp(data, chain_of_transforms)
         for transform in reversed(chain_of_transforms):
             data = transform.predict_backward(data, interp=interp, padding_mode=padding_mode)
         return data
@@ -572,6 +582,7 @@ class ComposeAdversarialTransformSolver(object):
     def _predict_backward_with_mask(self, data, chain, init_output):
         """predict_backward(data) and the validity mask in the same launches (self._ride: the mask after forward())."""
         ride, self._ride = self._ride, None
+        data = self._fp32_for_warp(data, chain)
         geo = [t for t in chain if t.is_geometric()]
         for transform in reversed(chain):
             if transform.is_geometric():        # (the mask is a second, non-differentiable output of the warp)
@@ -611,7 +622,9 @@ class ComposeAdversarialTransformSolver(object):
                 fb = self.predict_backward(self.predict_forward(ones, chain), chain)
                 m = ops.nonzero_mask(fb) if fb is not ones else ones       # one launch for `!= 0` and the cast
             return m.expand(init_output.shape)
-        masks = torch.ones_like(init_output, dtype=init_output.dtype, device=init_output.device, requires_grad=False)
+        # (the mask is fp32 also beside a bf16 init_output: the warps and the loss read an fp32 mask)
+        mask_dtype = torch.float32 if init_output.dtype == torch.bfloat16 else init_output.dtype
+        masks = torch.ones_like(init_output, dtype=mask_dtype, device=init_output.device, requires_grad=False)
         fb = self.predict_backward(self.predict_forward(masks, chain), chain)
         fb[fb != 0] = 1
         return fb

@@ -15,12 +15,13 @@ import torch
 from .. import ops
 
 MAX_CLASSES = 65535   # the C ABI's range (include/advchain_hip.h): up to 16 classes run csrc/loss.hip, more csrc/loss_wide.hip
+                      # (a bf16 operand: csrc/loss_lp.hip for every class count)
 
 
 def _check_operands(output, reference):
     """The restrictions of the fused kernels, stated where the user meets them (INTEGRATION.md "Known deviations"): fp32
-    ROCm tensors (no CPU path -- ops raises), fewer than 65536 channels.  Both operands are differentiated, as by the
-    reference's torch expression."""
+    or bf16 ROCm tensors, each operand on its own (no CPU path and no float16 -- ops raises), fewer than 65536 channels.
+    Both operands are differentiated, as by the reference's torch expression; a gradient has its operand's dtype."""
     if output.size(1) > MAX_CLASSES:
         raise NotImplementedError('the consistency kernels take at most %d classes, got %d'
                                   % (MAX_CLASSES, output.size(1)))
@@ -46,7 +47,10 @@ def _single_channel_mask(mask, K):
 def calc_segmentation_consistency(output, reference, divergence_types=['kl', 'contour'],
                                   divergence_weights=[1.0, 0.5], class_weights=None, scales=[0],
                                   mask=None, is_gt=False, global_batch=None):
-    """Difference between two predictions (logits), same signature as the reference (loss.py:8-87)."""
+    """Difference between two predictions (logits), same signature as the reference (loss.py:8-87).  `output` and
+    `reference` are fp32 or bf16 (a model under autocast), independently: a bf16 operand is read as it is (csrc/loss_lp.hip),
+    all arithmetic is fp32 -- the value is the fp32 loss of the upcast operands, an fp32 scalar -- and the gradient of an
+    operand has that operand's dtype (computed in fp32, rounded once).  float16 is refused."""
     if class_weights is not None:
         raise NotImplementedError
     spatial_dims = output.dim() - 2
@@ -54,6 +58,11 @@ def calc_segmentation_consistency(output, reference, divergence_types=['kl', 'co
     assert output.dim() == reference.dim(), 'output and reference must have the same rank'
     K = reference.size(1)
     _check_operands(output, reference)
+    if any(scale != 0 for scale in scales):
+        # a bf16 operand is upcast ONCE, differentiably, in front of the AvgPool: the pool runs in fp32 (the value stays the
+        # fp32 loss of the upcast operands), and the gradients of the scales add up in fp32 and are rounded once, by the cast
+        output = output.float() if output.dtype == torch.bfloat16 else output
+        reference = reference.float() if reference.dtype == torch.bfloat16 else reference
     dist = 0.
     for scale in scales:
         out_s, ref_s = (output, reference) if scale == 0 else (_pooled(output, scale), _pooled(reference, scale))
@@ -96,7 +105,8 @@ def calc_segmentation_consistency(output, reference, divergence_types=['kl', 'co
 
 
 def kl_divergence(reference, pred, mask=None, is_gt=False, global_batch=None):
-    """KL(P||Q) of two logit maps (loss.py:223-249): the 'kl' term of the fused kernels on its own."""
+    """KL(P||Q) of two logit maps (loss.py:223-249): the 'kl' term of the fused kernels on its own.  fp32 or bf16 operands,
+    as in :func:`calc_segmentation_consistency`."""
     K = pred.size(1)
     _check_operands(pred, reference)
     V = 1

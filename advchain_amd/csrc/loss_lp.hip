@@ -1,0 +1,537 @@
+// Segmentation-consistency loss ('mse' + 'contour' + 'kl') for logits stored in bf16 (a model under autocast), run-time class
+// count, gfx950.
+//
+//   advchain_consistency_lp_fwd / lp_bwd / lp_ref_bwd <- calc_segmentation_consistency + contour_loss + kl_divergence,
+//                                                        advchain/common/loss.py:8-87,102-220,223-249 (Q13, Q14) and what
+//                                                        autograd gives both operands
+//
+// The mathematics and the arithmetic are those of loss_wide.hip (forward, prediction side) and loss_ref.hip (reference side);
+// see their headers for the notation.  What differs is the STORAGE: each logit operand is read as fp32 or as bf16 (raw 16-bit
+// words), independently -- bf16 -> fp32 is exact, so the forward is the fp32 loss of the upcast operands -- and each gradient
+// is written in its operand's type, computed in fp32 and rounded once (to nearest even) at the store.  stats, R, the slot sums
+// and the mask stay fp32.  Every K >= 1 runs here: with a bf16 operand the K <= 16 register kernels of loss.hip are not used.
+//
+//   k_lp_stats     k_wide_stats with typed loads.  A lane owns 4 consecutive voxels in either access form -- 16-byte fp32 /
+//                  8-byte bf16 loads when V % 4 == 0 and every pointer allows it, else scalar loads of the same 4 voxels -- so
+//                  the order of every sum, and with it the value, does not depend on the alignment of a tensor.
+//   k_lp_edge      k_wide_edge with typed loads.
+//   k_lp_bwd       the tile of k_wide_bwd.  k_wide_bwd parks the probability-space gradient g_k in grad_pred between its two
+//                  sweeps; a bf16 grad_pred would round g_k before p_k (g_k - dot) cancels.  CHOSEN HERE: the second sweep
+//                  RECOMPUTES g_k (same code, same operands: the same bits) instead of re-reading it, so the only store of an
+//                  element is the final, rounded one and no scratch exists.  Cost against k_wide_bwd, per element: one more
+//                  adjoint stencil pair (12 LDS reads in 2D, 36 in 3D), one more read of R through the halo (8 bytes x
+//                  halo / tile = 1.29 in 2D, 1.99 in 3D) and one more barrier per class; saved: the 4-byte store and the 4-byte
+//                  re-read of the parked g_k.  An fp32 scratch from the caller would have cost 4 K V N bytes of memory, 8 bytes
+//                  of traffic per element and a workspace entry in the C ABI.  Measured at 32 x 20 x 256 x 256: 349 us with a bf16
+//                  output, 420 us with an fp32 one, against 418 us of k_wide_bwd (profiles/r10/bf16_loss/summary.md).
+//   k_lp_ref_grad  the run-time form of k_loss_ref_grad (statistics always from `stats`: the lp forward saves them for every
+//                  K), with the same recomputing second sweep for h_k.  ref_is_prob: one sweep, -g_k is the gradient.
+//
+// The tile kernels read one value per lane and plane (a wave reads 64 consecutive values of a tile row: 128 contiguous bytes
+// in bf16) at any alignment; only k_lp_stats has a vector form.  The adjoint stencils skip the zero-weight taps (as
+// loss_ref.hip does).  No atomics on the gradients and no shared accumulator: bit-reproducible.  Streaming + 3^d stencil:
+// memory-bound, no MFMA.
+#include "loss_common.h"
+
+namespace advchain {
+namespace {
+
+typedef unsigned short bf16_t;     // raw bf16 words
+
+__device__ __forceinline__ bf16_t lp_to_bf16(float x) {     // round to nearest even; NaN stays NaN
+  const unsigned u = __float_as_uint(x);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)((u >> 16) | 0x40u);
+  return (bf16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
+template <typename ST>
+__device__ __forceinline__ float ld1(const ST* __restrict__ p) {
+  if constexpr (sizeof(ST) == 4) return p[0];
+  else return __uint_as_float((unsigned)p[0] << 16);
+}
+template <typename ST>
+__device__ __forceinline__ void st1(ST* __restrict__ p, float x) {
+  if constexpr (sizeof(ST) == 4) p[0] = x;
+  else p[0] = lp_to_bf16(x);
+}
+
+// 4 consecutive values of one plane: WIDE one 16-byte (fp32) / 8-byte (bf16) access, else `cnt` (1..4) scalar ones
+template <typename ST, bool WIDE>
+__device__ __forceinline__ void ld4(const ST* __restrict__ p, int cnt, float (&x)[4]) {
+  if constexpr (WIDE) {
+    if constexpr (sizeof(ST) == 4) {
+      const float4 a = *reinterpret_cast<const float4*>(p);
+      x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w;
+    } else {
+      const uint2 a = *reinterpret_cast<const uint2*>(p);
+      x[0] = __uint_as_float(a.x << 16); x[1] = __uint_as_float(a.x & 0xffff0000u);
+      x[2] = __uint_as_float(a.y << 16); x[3] = __uint_as_float(a.y & 0xffff0000u);
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) x[q] = q < cnt ? ld1<ST>(p + q) : 0.f;
+  }
+}
+template <bool WIDE>
+__device__ __forceinline__ void st4(float* __restrict__ p, int cnt, const float (&x)[4]) {
+  if constexpr (WIDE) {
+    *reinterpret_cast<float4*>(p) = make_float4(x[0], x[1], x[2], x[3]);
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (q < cnt) p[q] = x[q];
+  }
+}
+
+// tile_stencil<DIM, true> without the taps whose weight is zero (the [1, 0, -1] factor: 3 of 9 taps in 2D, 9 of 27 in 3D)
+template <int DIM>
+__device__ __forceinline__ void lp_adjoint_stencil(const float* __restrict__ bufa, const float* __restrict__ bufb, int corner,
+                                                   float& ga, float& gb) {
+  using T = WTile<DIM>;
+  float sa = 0.f, sb = 0.f;
+#pragma unroll
+  for (int a0 = (DIM == 3 ? 0 : 1); a0 < (DIM == 3 ? 3 : 2); ++a0)
+#pragma unroll
+    for (int a1 = 0; a1 < 3; ++a1)
+#pragma unroll
+      for (int a2 = 0; a2 < 3; ++a2) {
+        float wa, wb;
+        stencil_w<DIM>(a0, a1, a2, wa, wb);
+        const int q = corner + ((DIM == 3 ? 2 - a0 : 0) * T::HY + (2 - a1)) * T::HX + (2 - a2);
+        if (wa != 0.f) sa += wa * bufa[q];
+        if (wb != 0.f) sb += wb * bufb[q];
+      }
+  ga = sa;
+  gb = sb;
+}
+
+// the R_k tile and its halo into one pair of LDS buffers (zero outside the volume: R is zero there)
+template <int DIM>
+__device__ __forceinline__ void lp_stage_R(float (*buf)[WTile<DIM>::NH], const float* __restrict__ Ra,
+                                           const float* __restrict__ Rb, const int (&hv)[WTile<DIM>::SLOTS]) {
+  using T = WTile<DIM>;
+#pragma unroll
+  for (int j = 0; j < T::SLOTS; ++j) {
+    const int e = threadIdx.x + j * kBlock;
+    const int c = max(hv[j], 0);
+    const float ra = Ra[c], rb = Rb[c];          // unconditional loads from a clamped index: all in flight together
+    if (e < T::NH) {
+      buf[0][e] = hv[j] >= 0 ? ra : 0.f;
+      buf[1][e] = hv[j] >= 0 ? rb : 0.f;
+    }
+  }
+}
+
+// A lane owns the voxels 4 i .. 4 i + 3 of a batch entry (i its index in the grid), WIDE or not.
+template <typename PT, typename RT, bool WIDE>
+__global__ void __launch_bounds__(kBlock)
+k_lp_stats(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* __restrict__ mask, float* __restrict__ stats,
+           float* __restrict__ sums, int K, int V, int mask_ch, int ref_is_prob, int want_kl) {
+  __shared__ float smem[8];
+  const int n = blockIdx.y;
+  const int64_t v64 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * 4;
+  float acc[2] = {0.f, 0.f};
+  if (v64 < V) {
+    const int v = (int)v64;
+    const int cnt = min(4, V - v);
+    const PT* pn = pred + (int64_t)n * K * V + v;
+    const RT* rn = ref + (int64_t)n * K * V + v;
+    float mp[4], sp[4], mr[4], sr[4];
+    ld4<PT, WIDE>(pn, cnt, mp);
+    ld4<RT, WIDE>(rn, cnt, mr);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { sp[q] = 1.f; sr[q] = 1.f; }
+    for (int k = 1; k < K; ++k) {
+      float a[4], b[4];
+      ld4<PT, WIDE>(pn + (int64_t)k * V, cnt, a);
+      ld4<RT, WIDE>(rn + (int64_t)k * V, cnt, b);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        online_step(a[q], mp[q], sp[q]);
+        if (!ref_is_prob) online_step(b[q], mr[q], sr[q]);
+      }
+    }
+    float isp[4], isr[4], lsp[4], lsr[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      isp[q] = 1.f / sp[q];                      // ONE division per voxel and side
+      isr[q] = 1.f / sr[q];
+      lsp[q] = want_kl ? logf(sp[q]) : 0.f;
+      lsr[q] = want_kl ? logf(sr[q]) : 0.f;
+    }
+    float m1[4] = {1.f, 1.f, 1.f, 1.f};
+    if (mask && mask_ch == 1) ld4<float, WIDE>(mask + (int64_t)n * V + v, cnt, m1);
+    for (int k = 0; k < K; ++k) {
+      float a[4], b[4], m[4];
+      ld4<PT, WIDE>(pn + (int64_t)k * V, cnt, a);
+      ld4<RT, WIDE>(rn + (int64_t)k * V, cnt, b);
+      if (mask && mask_ch > 1) ld4<float, WIDE>(mask + ((int64_t)n * mask_ch + k) * V + v, cnt, m);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float zp = a[q] - mp[q], zr = b[q] - mr[q];
+        const float p = mul_nc(ADVCHAIN_SM_EXP(zp), isp[q]);
+        const float t = ref_is_prob ? b[q] : mul_nc(ADVCHAIN_SM_EXP(zr), isr[q]);
+        const float mm = (mask && mask_ch > 1) ? m[q] : m1[q];
+        const float e = p * mm - t * mm;
+        if (q < cnt) {
+          acc[0] += e * e;
+          if (want_kl) acc[1] += kl_term(t, zr - lsr[q], zp - lsp[q], mm, ref_is_prob);
+        }
+      }
+    }
+    float* sn = stats + (int64_t)n * 4 * V + v;
+    st4<WIDE>(sn, cnt, mp);
+    st4<WIDE>(sn + V, cnt, isp);
+    st4<WIDE>(sn + 2 * (int64_t)V, cnt, mr);
+    st4<WIDE>(sn + 3 * (int64_t)V, cnt, isr);
+  }
+  block_sum<2>(acc, smem);
+  if (threadIdx.x == 0) {
+    atomic_add_f32(sums + sum_slot(), acc[0]);
+    if (want_kl) atomic_add_f32(sums + 3 * kSumSlots + sum_slot(), acc[1]);
+  }
+}
+
+template <typename PT, typename RT, int DIM>
+__global__ void __launch_bounds__(kBlock)
+k_lp_edge(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* __restrict__ mask,
+          const float* __restrict__ stats, float* __restrict__ R, float* __restrict__ sums, int K, Dims d, int mask_ch,
+          int ref_is_prob) {
+  using T = WTile<DIM>;
+  __shared__ float lds[2][T::NH];
+  __shared__ float smem[8];
+  const T tile(d);
+  const int n = blockIdx.y;
+  const int V = (int)d.voxels();
+  const float* sn = stats + (int64_t)n * 4 * V;
+  int hv[T::SLOTS];
+  float hmp[T::SLOTS], hip_[T::SLOTS], hmr[T::SLOTS], hir[T::SLOTS];
+#pragma unroll
+  for (int j = 0; j < T::SLOTS; ++j) {
+    hv[j] = tile.halo_voxel(threadIdx.x + j * kBlock, d);
+    const int c = max(hv[j], 0);
+    hmp[j] = sn[c];
+    hip_[j] = sn[(int64_t)V + c];
+    hmr[j] = sn[2 * (int64_t)V + c];
+    hir[j] = sn[3 * (int64_t)V + c];
+  }
+  int ov[T::OUTS], oc[T::OUTS];
+  float om[T::OUTS];
+#pragma unroll
+  for (int j = 0; j < T::OUTS; ++j) {
+    ov[j] = tile.out_voxel(threadIdx.x + j * kBlock, d, oc[j]);
+    om[j] = (mask && ov[j] >= 0) ? mask[(int64_t)n * mask_ch * V + ov[j]] : 1.f;   // the stencil terms read channel 0
+  }
+  float acc[2] = {0.f, 0.f};
+  for (int k = 1; k < K; ++k) {
+    const PT* pk = pred + ((int64_t)n * K + k) * V;
+    const RT* rk = ref + ((int64_t)n * K + k) * V;
+    float* buf = lds[k & 1];
+#pragma unroll
+    for (int j = 0; j < T::SLOTS; ++j) {
+      const int e = threadIdx.x + j * kBlock;
+      const int c = max(hv[j], 0);
+      const float xp = ld1<PT>(pk + c), xr = ld1<RT>(rk + c);     // unconditional loads from a clamped index
+      const float p = mul_nc(ADVCHAIN_SM_EXP(xp - hmp[j]), hip_[j]);
+      const float t = ref_is_prob ? xr : mul_nc(ADVCHAIN_SM_EXP(xr - hmr[j]), hir[j]);
+      if (e < T::NH) buf[e] = hv[j] >= 0 ? p - t : 0.f;      // zero padding of the convolution
+    }
+    __syncthreads();     // (the other buffer is written next: one barrier per class)
+#pragma unroll
+    for (int j = 0; j < T::OUTS; ++j) {
+      float ga, gb;
+      tile_stencil<DIM, false>(buf, buf, oc[j], ga, gb);
+      if (ov[j] >= 0) {
+        const float m = om[j];
+        const float ea = ga * m, eb = gb * m;
+        acc[0] += ea * ea;
+        acc[1] += eb * eb;
+        if (R) {
+          R[((int64_t)n * 2 * (K - 1) + 2 * (k - 1)) * V + ov[j]] = 2.f * m * m * ga;
+          R[((int64_t)n * 2 * (K - 1) + 2 * (k - 1) + 1) * V + ov[j]] = 2.f * m * m * gb;
+        }
+      }
+    }
+  }
+  block_sum<2>(acc, smem);
+  if (threadIdx.x == 0) {
+    atomic_add_f32(sums + kSumSlots + sum_slot(), acc[0]);
+    atomic_add_f32(sums + 2 * kSumSlots + sum_slot(), acc[1]);
+  }
+}
+
+// grad_pred.  Sweep 0 leaves dot = sum_k g_k P_k and sum_k m_k T'_k in registers and stores nothing; sweep 1 recomputes g_k and
+// stores P_k (g_k - dot) + the 'kl' part, rounded once.  The barrier between the sweeps: with an even K the last class of
+// sweep 0 and the first staged class of sweep 1 use the same LDS buffer.
+template <typename PT, typename RT, int DIM>
+__global__ void __launch_bounds__(kBlock)
+k_lp_bwd(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* __restrict__ stats, const float* __restrict__ R,
+         const float* __restrict__ mask, const float* __restrict__ gscale, PT* __restrict__ gpred, float c_mse, float c_a,
+         float c_b, float c_kl, int ref_is_prob, int K, Dims d, int mask_ch) {
+  using T = WTile<DIM>;
+  __shared__ float lds[2][2][T::NH];
+  const T tile(d);
+  const int n = blockIdx.y;
+  const int V = (int)d.voxels();
+  const float gs = gscale ? gscale[0] : 1.f;
+  const float* sn = stats + (int64_t)n * 4 * V;
+  int hv[T::SLOTS];
+#pragma unroll
+  for (int j = 0; j < T::SLOTS; ++j) hv[j] = tile.halo_voxel(threadIdx.x + j * kBlock, d);
+  int ov[T::OUTS], oc[T::OUTS];
+  float omp[T::OUTS], oip[T::OUTS], omr[T::OUTS], oir[T::OUTS], om[T::OUTS], dot[T::OUTS], klS[T::OUTS];
+#pragma unroll
+  for (int j = 0; j < T::OUTS; ++j) {
+    ov[j] = tile.out_voxel(threadIdx.x + j * kBlock, d, oc[j]);
+    const int c = max(ov[j], 0);
+    omp[j] = sn[c];
+    oip[j] = sn[(int64_t)V + c];
+    omr[j] = sn[2 * (int64_t)V + c];
+    oir[j] = sn[3 * (int64_t)V + c];
+    om[j] = (mask && mask_ch == 1) ? mask[(int64_t)n * V + c] : 1.f;
+    dot[j] = 0.f;
+    klS[j] = 0.f;
+  }
+  const bool edges = R != nullptr;
+  for (int sweep = 0; sweep < 2; ++sweep) {
+    if (sweep) __syncthreads();
+    for (int k = 0; k < K; ++k) {
+      const int64_t plane = ((int64_t)n * K + k) * V;
+      float (*buf)[T::NH] = lds[k & 1];
+      if (edges && k >= 1) {
+        const float* Ra = R + ((int64_t)n * 2 * (K - 1) + 2 * (k - 1)) * V;
+        lp_stage_R<DIM>(buf, Ra, Ra + V, hv);
+        __syncthreads();     // (the other buffer is written next: one barrier per class)
+      }
+#pragma unroll
+      for (int j = 0; j < T::OUTS; ++j) {
+        const int c = max(ov[j], 0);
+        const float xp = ld1<PT>(pred + plane + c), xr = ld1<RT>(ref + plane + c);
+        const float m = (mask && mask_ch > 1) ? mask[((int64_t)n * mask_ch + k) * V + c] : om[j];
+        const float p = mul_nc(ADVCHAIN_SM_EXP(xp - omp[j]), oip[j]);
+        const float t = ref_is_prob ? xr : mul_nc(ADVCHAIN_SM_EXP(xr - omr[j]), oir[j]);
+        float g = c_mse * 2.f * m * m * (p - t);
+        if (edges && k >= 1) {
+          float ta, tb;                 // A^T R_A, B^T R_B (R is zero outside the volume)
+          lp_adjoint_stencil<DIM>(buf[0], buf[1], oc[j], ta, tb);
+          g += c_a * ta + c_b * tb;
+        }
+        g *= gs;
+        if (sweep == 0) {
+          dot[j] += g * p;
+          if (c_kl != 0.f) klS[j] += m * kl_prob(t, ref_is_prob);
+        } else if (ov[j] >= 0) {
+          float o = p * (g - dot[j]);     // the softmax Jacobian
+          if (c_kl != 0.f) o += gs * c_kl * (p * klS[j] - m * kl_prob(t, ref_is_prob));   // 'kl': gs c_kl (P_j sum_k m_k T'_k - m_j T'_j)
+          st1<PT>(gpred + plane + c, o);
+        }
+      }
+    }
+  }
+}
+
+// grad_ref.  h_k = -g_k + gs c_kl m_k (log T_k + 1 - log P_k); ref_is_prob: h_k is the gradient (one sweep); logits: sweep 0
+// leaves sum_j T_j h_j in registers, sweep 1 recomputes h_k and stores T_k (h_k - sum), rounded once.
+template <typename PT, typename RT, int DIM>
+__global__ void __launch_bounds__(kBlock)
+k_lp_ref_grad(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* __restrict__ stats,
+              const float* __restrict__ R, const float* __restrict__ mask, const float* __restrict__ gscale,
+              RT* __restrict__ gref, float c_mse, float c_a, float c_b, float c_kl, int ref_is_prob, int K, Dims d,
+              int mask_ch) {
+  using T = WTile<DIM>;
+  __shared__ float lds[2][2][T::NH];
+  const T tile(d);
+  const int n = blockIdx.y;
+  const int V = (int)d.voxels();
+  const float gs = gscale ? gscale[0] : 1.f;
+  const bool edges = R != nullptr;
+  const bool kl = c_kl != 0.f && !ref_is_prob;
+  const float ckl = gs * c_kl;
+  const float* sn = stats + (int64_t)n * 4 * V;
+  int hv[T::SLOTS];
+#pragma unroll
+  for (int j = 0; j < T::SLOTS; ++j) hv[j] = tile.halo_voxel(threadIdx.x + j * kBlock, d);
+  int ov[T::OUTS], oc[T::OUTS];
+  float om[T::OUTS], dot[T::OUTS], omp[T::OUTS], oip[T::OUTS], omr[T::OUTS], oir[T::OUTS], lgd[T::OUTS];
+#pragma unroll
+  for (int j = 0; j < T::OUTS; ++j) {
+    ov[j] = tile.out_voxel(threadIdx.x + j * kBlock, d, oc[j]);
+    const int c = max(ov[j], 0);
+    om[j] = (mask && mask_ch == 1) ? mask[(int64_t)n * V + c] : 1.f;
+    dot[j] = 0.f;
+    omp[j] = sn[c];
+    oip[j] = sn[(int64_t)V + c];
+    omr[j] = ref_is_prob ? 0.f : sn[2 * (int64_t)V + c];      // (the ref planes are unspecified when ref_is_prob)
+    oir[j] = ref_is_prob ? 1.f : sn[3 * (int64_t)V + c];
+    lgd[j] = kl ? logf(oir[j]) - logf(oip[j]) : 0.f;          // log inv_r - log inv_p
+  }
+  const int64_t batch = (int64_t)n * K * V;
+  const int sweeps = ref_is_prob ? 1 : 2;
+  for (int sweep = 0; sweep < sweeps; ++sweep) {
+    if (sweep) __syncthreads();
+    for (int k = 0; k < K; ++k) {
+      const int64_t plane = batch + (int64_t)k * V;
+      float (*buf)[T::NH] = lds[k & 1];
+      if (edges && k >= 1) {
+        const float* Ra = R + ((int64_t)n * 2 * (K - 1) + 2 * (k - 1)) * V;
+        lp_stage_R<DIM>(buf, Ra, Ra + V, hv);
+        __syncthreads();     // (the other buffer is written next: one barrier per class)
+      }
+#pragma unroll
+      for (int j = 0; j < T::OUTS; ++j) {
+        const int c = max(ov[j], 0);
+        const float xp = ld1<PT>(pred + plane + c), xr = ld1<RT>(ref + plane + c);
+        const float m = (mask && mask_ch > 1) ? mask[((int64_t)n * mask_ch + k) * V + c] : om[j];
+        const float zp = xp - omp[j], zr = xr - omr[j];
+        const float p = mul_nc(ADVCHAIN_SM_EXP(zp), oip[j]);
+        const float t = ref_is_prob ? xr : mul_nc(ADVCHAIN_SM_EXP(zr), oir[j]);
+        float g = c_mse * 2.f * m * m * (p - t);
+        if (edges && k >= 1) {
+          float ta, tb;                 // A^T R_A, B^T R_B
+          lp_adjoint_stencil<DIM>(buf[0], buf[1], oc[j], ta, tb);
+          g += c_a * ta + c_b * tb;
+        }
+        float hk = -(g * gs);
+        if (kl) hk += ckl * m * ((zr - zp) + lgd[j] + 1.f);
+        if (sweep == 0) {
+          dot[j] += t * hk;
+          if (ref_is_prob && ov[j] >= 0) st1<RT>(gref + plane + c, hk);     // already the gradient
+        } else if (ov[j] >= 0) {
+          st1<RT>(gref + plane + c, t * (hk - dot[j]));     // the softmax Jacobian of the reference
+        }
+      }
+    }
+  }
+}
+
+inline bool lp_nk_ok(int64_t N, int64_t K) { return N >= 0 && N < 65536 && K >= 1 && K < 65536; }
+inline bool lp_flag_ok(int f) { return f == 0 || f == 1; }
+inline bool lp_aligned(const void* p, int bytes) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % bytes) == 0; }
+
+template <typename PT, typename RT>
+void lp_launch_fwd(hipStream_t st, const void* pred, const void* ref, const float* mask, float* stats, float* R, float* sums,
+                   int N, int K, int ndim, Dims d, int mask_ch, int ref_is_prob, int want_edges, int want_kl) {
+  const int V = (int)d.voxels();
+  const PT* p = (const PT*)pred;
+  const RT* r = (const RT*)ref;
+  const dim3 b(kBlock);
+  const dim3 g((unsigned)advchain_blocks(((int64_t)V + 3) / 4, kBlock), (unsigned)N);
+  const bool wide = V % 4 == 0 && lp_aligned(pred, 4 * (int)sizeof(PT)) && lp_aligned(ref, 4 * (int)sizeof(RT)) &&
+                    lp_aligned(mask, 16) && lp_aligned(stats, 16);
+  if (wide)
+    hipLaunchKernelGGL((k_lp_stats<PT, RT, true>), g, b, 0, st, p, r, mask, stats, sums, K, V, mask_ch, ref_is_prob, want_kl);
+  else
+    hipLaunchKernelGGL((k_lp_stats<PT, RT, false>), g, b, 0, st, p, r, mask, stats, sums, K, V, mask_ch, ref_is_prob, want_kl);
+  if (want_edges && K > 1) {
+    if (ndim == 3)
+      hipLaunchKernelGGL((k_lp_edge<PT, RT, 3>), dim3((unsigned)WTile<3>::count(d), (unsigned)N), b, 0, st, p, r, mask, stats, R,
+                         sums, K, d, mask_ch, ref_is_prob);
+    else
+      hipLaunchKernelGGL((k_lp_edge<PT, RT, 2>), dim3((unsigned)WTile<2>::count(d), (unsigned)N), b, 0, st, p, r, mask, stats, R,
+                         sums, K, d, mask_ch, ref_is_prob);
+  }
+}
+
+template <typename PT, typename RT>
+void lp_launch_bwd(hipStream_t st, const void* pred, const void* ref, const float* stats, const float* R, const float* mask,
+                   const float* gs, void* gpred, float c_mse, float c_a, float c_b, float c_kl, int ref_is_prob, int N, int K,
+                   int ndim, Dims d, int mask_ch) {
+  if (ndim == 3)
+    hipLaunchKernelGGL((k_lp_bwd<PT, RT, 3>), dim3((unsigned)WTile<3>::count(d), (unsigned)N), dim3(kBlock), 0, st,
+                       (const PT*)pred, (const RT*)ref, stats, R, mask, gs, (PT*)gpred, c_mse, c_a, c_b, c_kl, ref_is_prob, K, d,
+                       mask_ch);
+  else
+    hipLaunchKernelGGL((k_lp_bwd<PT, RT, 2>), dim3((unsigned)WTile<2>::count(d), (unsigned)N), dim3(kBlock), 0, st,
+                       (const PT*)pred, (const RT*)ref, stats, R, mask, gs, (PT*)gpred, c_mse, c_a, c_b, c_kl, ref_is_prob, K, d,
+                       mask_ch);
+}
+
+template <typename PT, typename RT>
+void lp_launch_ref(hipStream_t st, const void* pred, const void* ref, const float* stats, const float* R, const float* mask,
+                   const float* gs, void* gref, float c_mse, float c_a, float c_b, float c_kl, int ref_is_prob, int N, int K,
+                   int ndim, Dims d, int mask_ch) {
+  if (ndim == 3)
+    hipLaunchKernelGGL((k_lp_ref_grad<PT, RT, 3>), dim3((unsigned)WTile<3>::count(d), (unsigned)N), dim3(kBlock), 0, st,
+                       (const PT*)pred, (const RT*)ref, stats, R, mask, gs, (RT*)gref, c_mse, c_a, c_b, c_kl, ref_is_prob, K, d,
+                       mask_ch);
+  else
+    hipLaunchKernelGGL((k_lp_ref_grad<PT, RT, 2>), dim3((unsigned)WTile<2>::count(d), (unsigned)N), dim3(kBlock), 0, st,
+                       (const PT*)pred, (const RT*)ref, stats, R, mask, gs, (RT*)gref, c_mse, c_a, c_b, c_kl, ref_is_prob, K, d,
+                       mask_ch);
+}
+
+// one of the four storage pairs
+#define ADVCHAIN_LP_DISPATCH(fn, pb, rb, ...)                  \
+  do {                                                         \
+    if (pb) {                                                  \
+      if (rb) fn<bf16_t, bf16_t>(__VA_ARGS__);                 \
+      else fn<bf16_t, float>(__VA_ARGS__);                     \
+    } else {                                                   \
+      if (rb) fn<float, bf16_t>(__VA_ARGS__);                  \
+      else fn<float, float>(__VA_ARGS__);                      \
+    }                                                          \
+  } while (0)
+
+}  // namespace
+}  // namespace advchain
+
+using namespace advchain;
+
+extern "C" {
+
+int advchain_consistency_lp_fwd(const void* pred, int pred_bf16, const void* ref, int ref_bf16, const float* mask, float* stats,
+                                float* R, float* sums, int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels,
+                                int ref_is_prob, int want_edges, int want_kl, void* stream) {
+  ADVCHAIN_CHECK_ARG(pred && ref && stats && sums && dims, "consistency_lp_fwd: null pointer");
+  ADVCHAIN_CHECK_ARG(lp_flag_ok(pred_bf16) && lp_flag_ok(ref_bf16), "consistency_lp_fwd: an operand is fp32 (0) or bf16 (1)");
+  ADVCHAIN_CHECK_ARG(ldims_ok(ndim, dims), "consistency_lp_fwd: bad dims");
+  ADVCHAIN_CHECK_ARG(lp_nk_ok(N, K), "consistency_lp_fwd: bad N/K (N < 65536, 1 <= K < 65536)");
+  ADVCHAIN_CHECK_ARG(!mask || mask_channels == 1 || mask_channels == K, "consistency_lp_fwd: mask must have 1 or K channels");
+  const Dims d = lmake_dims(ndim, dims);
+  ADVCHAIN_CHECK_ARG(d.voxels() < (1ll << 31), "consistency_lp_fwd: volume too large");
+  if (N == 0) return ADVCHAIN_OK;
+  ADVCHAIN_LP_DISPATCH(lp_launch_fwd, pred_bf16, ref_bf16, (hipStream_t)stream, pred, ref, mask, stats, R, sums, (int)N, (int)K,
+                       ndim, d, mask_channels, ref_is_prob, want_edges, want_kl);
+  ADVCHAIN_LAUNCH_CHECK();
+  return ADVCHAIN_OK;
+}
+
+int advchain_consistency_lp_bwd(const void* pred, int pred_bf16, const void* ref, int ref_bf16, const float* stats,
+                                const float* R, const float* mask, const float* grad_scale, void* grad_pred, float c_mse,
+                                float c_a, float c_b, float c_kl, int ref_is_prob, int64_t N, int64_t K, int ndim,
+                                const int64_t* dims, int mask_channels, void* stream) {
+  ADVCHAIN_CHECK_ARG(pred && ref && stats && grad_pred && dims, "consistency_lp_bwd: null pointer");
+  ADVCHAIN_CHECK_ARG(lp_flag_ok(pred_bf16) && lp_flag_ok(ref_bf16), "consistency_lp_bwd: an operand is fp32 (0) or bf16 (1)");
+  ADVCHAIN_CHECK_ARG(ldims_ok(ndim, dims), "consistency_lp_bwd: bad dims");
+  ADVCHAIN_CHECK_ARG(lp_nk_ok(N, K), "consistency_lp_bwd: bad N/K (N < 65536, 1 <= K < 65536)");
+  ADVCHAIN_CHECK_ARG(!mask || mask_channels == 1 || mask_channels == K, "consistency_lp_bwd: mask must have 1 or K channels");
+  const Dims d = lmake_dims(ndim, dims);
+  ADVCHAIN_CHECK_ARG(d.voxels() < (1ll << 31), "consistency_lp_bwd: volume too large");
+  if (N == 0) return ADVCHAIN_OK;
+  if (K == 1) R = nullptr;        // (no object class: nothing was saved)
+  ADVCHAIN_LP_DISPATCH(lp_launch_bwd, pred_bf16, ref_bf16, (hipStream_t)stream, pred, ref, stats, R, mask, grad_scale, grad_pred,
+                       c_mse, c_a, c_b, c_kl, ref_is_prob, (int)N, (int)K, ndim, d, mask_channels);
+  ADVCHAIN_LAUNCH_CHECK();
+  return ADVCHAIN_OK;
+}
+
+int advchain_consistency_lp_ref_bwd(const void* pred, int pred_bf16, const void* ref, int ref_bf16, const float* stats,
+                                    const float* R, const float* mask, const float* grad_scale, void* grad_ref, float c_mse,
+                                    float c_a, float c_b, float c_kl, int ref_is_prob, int64_t N, int64_t K, int ndim,
+                                    const int64_t* dims, int mask_channels, void* stream) {
+  ADVCHAIN_CHECK_ARG(pred && ref && stats && grad_ref && dims, "consistency_lp_ref_bwd: null pointer");
+  ADVCHAIN_CHECK_ARG(lp_flag_ok(pred_bf16) && lp_flag_ok(ref_bf16), "consistency_lp_ref_bwd: an operand is fp32 (0) or bf16 (1)");
+  ADVCHAIN_CHECK_ARG(ldims_ok(ndim, dims), "consistency_lp_ref_bwd: bad dims");
+  ADVCHAIN_CHECK_ARG(lp_nk_ok(N, K), "consistency_lp_ref_bwd: bad N/K (N < 65536, 1 <= K < 65536)");
+  ADVCHAIN_CHECK_ARG(!mask || mask_channels == 1 || mask_channels == K, "consistency_lp_ref_bwd: mask must have 1 or K channels");
+  const Dims d = lmake_dims(ndim, dims);
+  ADVCHAIN_CHECK_ARG(d.voxels() < (1ll << 31), "consistency_lp_ref_bwd: volume too large");
+  if (N == 0) return ADVCHAIN_OK;
+  if (K == 1) R = nullptr;        // (no object class: nothing was saved)
+  ADVCHAIN_LP_DISPATCH(lp_launch_ref, pred_bf16, ref_bf16, (hipStream_t)stream, pred, ref, stats, R, mask, grad_scale, grad_ref,
+                       c_mse, c_a, c_b, c_kl, ref_is_prob, (int)N, (int)K, ndim, d, mask_channels);
+  ADVCHAIN_LAUNCH_CHECK();
+  return ADVCHAIN_OK;
+}
+
+}  // extern "C"

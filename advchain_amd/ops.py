@@ -1562,7 +1562,12 @@ class _Consistency(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, ref, mask, coef, ref_is_prob, want_edges):
-        pred, ref = _dev(pred, "pred"), _dev(ref, "reference")
+        pred, ref = _dev_logits(pred, "pred"), _dev_logits(ref, "reference")
+        if pred.dtype != torch.float32 or ref.dtype != torch.float32:
+            if isinstance(mask, torch.Tensor) and mask.dtype in (torch.bfloat16, torch.float16, torch.float64):
+                mask = mask.float()           # (small: the kernels read an fp32 mask)
+            mask = None if mask is None else _dev(mask, "mask")
+            return _Consistency._forward_lp(ctx, pred, ref, mask, coef, ref_is_prob, want_edges)
         mask = None if mask is None else _dev(mask, "mask")
         N, K = pred.shape[:2]
         nd = pred.dim() - 2
@@ -1630,9 +1635,72 @@ class _Consistency(torch.autograd.Function):
         return value, sums
 
     @staticmethod
+    def _forward_lp(ctx, pred, ref, mask, coef, ref_is_prob, want_edges):
+        """At least one operand stored in bf16 (csrc/loss_lp.hip): the run-time-K scheme for every K, read natively."""
+        N, K = pred.shape[:2]
+        nd = pred.dim() - 2
+        dims = _lib.dims_array(pred.shape[2:])
+        mch = 1 if mask is None else mask.shape[1]
+        need_pred, need_ref = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_grad = need_pred or need_ref
+        want_kl = coef[3] != 0.0
+        R = None
+        if need_grad and want_edges and K > 1:
+            R = torch.empty((N, 2 * (K - 1)) + tuple(pred.shape[2:]), device=pred.device, dtype=torch.float32)
+        sums = torch.empty(4, device=pred.device, dtype=torch.float32)
+        value = torch.empty((), device=pred.device, dtype=torch.float32)
+        slots = _persistent_zeros("loss", (4, 64), pred.device)
+        stats = torch.empty((N, 4) + tuple(pred.shape[2:]), device=pred.device, dtype=torch.float32)
+        lib = _lib.load()
+        try:
+            _lib.check(lib.advchain_consistency_lp_fwd(
+                _ptr(pred), int(pred.dtype == torch.bfloat16), _ptr(ref), int(ref.dtype == torch.bfloat16), _ptr(mask),
+                _ptr(stats), _ptr(R), _ptr(slots), N, K, nd, dims, mch, int(ref_is_prob), int(want_edges), int(want_kl),
+                _stream()), "consistency_lp_fwd")
+            _lib.check(lib.advchain_consistency_finish(_ptr(slots), _lib.float_array(coef), _ptr(sums), _ptr(value), 1,
+                                                       _stream()), "consistency_finish")
+        except BaseException:
+            _forget_persistent(slots)
+            raise
+        if need_grad:
+            ctx.save_for_backward(pred, ref, R, mask, stats)
+        ctx.ref_grad = need_ref and not (ref_is_prob and coef[0] == 0.0 and not (want_edges and K > 1))
+        ctx.lp = True
+        ctx.cfg = (coef, mch, int(ref_is_prob))
+        ctx.mark_non_differentiable(sums)
+        ctx.set_materialize_grads(False)
+        return value, sums
+
+    @staticmethod
+    def _backward_lp(ctx, gloss):
+        coef, mch, is_gt = ctx.cfg
+        need_pred, need_ref = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and ctx.ref_grad
+        gs = _dev(gloss.reshape(1), "grad")
+        lib = _lib.load()
+        pred, ref, R, mask, stats = ctx.saved_tensors
+        N, K = pred.shape[:2]
+        gpred = gref = None
+        for need, entry, name in ((need_pred, lib.advchain_consistency_lp_bwd, "consistency_lp_bwd"),
+                                  (need_ref, lib.advchain_consistency_lp_ref_bwd, "consistency_lp_ref_bwd")):
+            if not need:
+                continue
+            out = torch.empty_like(pred if name == "consistency_lp_bwd" else ref)     # (the operand's dtype)
+            _lib.check(entry(_ptr(pred), int(pred.dtype == torch.bfloat16), _ptr(ref), int(ref.dtype == torch.bfloat16),
+                             _ptr(stats), _ptr(R), _ptr(mask), _ptr(gs), _ptr(out), float(coef[0]), float(coef[1]),
+                             float(coef[2]), float(coef[3]), is_gt, N, K, pred.dim() - 2, _lib.dims_array(pred.shape[2:]), mch,
+                             _stream()), name)
+            if name == "consistency_lp_bwd":
+                gpred = out
+            else:
+                gref = out
+        return gpred, gref, None, None, None, None
+
+    @staticmethod
     def backward(ctx, gloss, _gsums):
         if gloss is None:
             return None, None, None, None, None, None
+        if getattr(ctx, "lp", False):
+            return _Consistency._backward_lp(ctx, gloss)
         coef, mch, is_gt = ctx.cfg
         need_pred, need_ref = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and ctx.ref_grad
         gs = _dev(gloss.reshape(1), "grad")

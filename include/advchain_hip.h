@@ -475,6 +475,32 @@ int advchain_consistency_ref_bwd(const float* pred, const float* ref, const floa
 void advchain_set_ref_grad_reg_max_k(int k);
 int advchain_get_ref_grad_reg_max_k(void);
 
+/* low-precision storage (round 10, loss_lp.hip): the same loss and both of its gradients for logits stored in bf16 (a model
+ * under autocast), every K from 1 to 65535, 2D and 3D.  pred / ref are read as fp32 (flag 0) or as raw bf16 words (flag 1),
+ * independently; bf16 -> fp32 is exact and all arithmetic is the fp32 arithmetic of the wide entries, so lp_fwd computes the
+ * fp32 loss of the upcast operands.  mask, stats (N, 4, dims), R (N, 2(K-1), dims; NULL when no backward is needed) and the
+ * slot sums are fp32 and have the layouts of advchain_consistency_wide_fwd (finish with advchain_consistency_finish); a
+ * reference given as probabilities (ref_is_prob) is read in its own storage type as it is.  lp_bwd writes grad_pred in pred's
+ * type, lp_ref_bwd writes grad_ref in ref's type (formulas of advchain_consistency_wide_bwd / advchain_consistency_ref_bwd;
+ * stats must be what lp_fwd wrote, R NULL: no edge terms): computed in fp32 and rounded once, to nearest even, at the store.
+ * The probability-space gradient between the two sweeps of a backward never passes through the output: the second sweep
+ * recomputes it, so there is no scratch and no workspace.  No atomics on the gradients: bit-reproducible.  Tensors are
+ * contiguous at any alignment (lp_fwd's streaming pass takes 16-byte fp32 / 8-byte bf16 accesses when the voxel count is
+ * divisible by 4 and every pointer allows it; the value does not depend on which form ran).  N < 65536 (N == 0: ADVCHAIN_OK,
+ * no launch), fewer than 2^31 voxels, mask_channels 1 or K, flags 0 or 1.  Capture-safe: kernel launches on `stream` only.
+ * Returns ADVCHAIN_OK or a negative code (advchain_last_error names the entry). */
+int advchain_consistency_lp_fwd(const void* pred, int pred_bf16, const void* ref, int ref_bf16, const float* mask, float* stats,
+                                float* R /*nullable*/, float* sums, int64_t N, int64_t K, int ndim, const int64_t* dims,
+                                int mask_channels, int ref_is_prob, int want_edges, int want_kl, void* stream);
+int advchain_consistency_lp_bwd(const void* pred, int pred_bf16, const void* ref, int ref_bf16, const float* stats,
+                                const float* R /*nullable*/, const float* mask, const float* grad_scale, void* grad_pred,
+                                float c_mse, float c_a, float c_b, float c_kl, int ref_is_prob, int64_t N, int64_t K, int ndim,
+                                const int64_t* dims, int mask_channels, void* stream);
+int advchain_consistency_lp_ref_bwd(const void* pred, int pred_bf16, const void* ref, int ref_bf16, const float* stats,
+                                    const float* R /*nullable*/, const float* mask, const float* grad_scale, void* grad_ref,
+                                    float c_mse, float c_a, float c_b, float c_kl, int ref_is_prob, int64_t N, int64_t K,
+                                    int ndim, const int64_t* dims, int mask_channels, void* stream);
+
 /* bf16 STORAGE experiment (round 6; BASELINE config 2 names "bf16"): the 2D K = 4 fused loss above (common/loss.py:8-87,
  * 102-220: mse + contour terms on logits) with pred / ref / R / grad_pred stored as bfloat16 (raw 16-bit words, 8-byte aligned)
  * and all arithmetic in fp32 registers.  NOT used by the product path -- the parity contract is fp32 at 1e-4; the entries exist
