@@ -75,6 +75,10 @@ PROTOTYPES = {
     "advchain_consistency_lp_fwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _L, _L, _I, _P, _I, _I, _I, _I, _P]),
     "advchain_consistency_lp_bwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _I, _L, _L, _I, _P, _I, _P]),
     "advchain_consistency_lp_ref_bwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _I, _L, _L, _I, _P, _I, _P]),
+    # (the lp lists with `const float* class_w` in front of the stream)
+    "advchain_consistency_cw_fwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _L, _L, _I, _P, _I, _I, _I, _I, _P, _P]),
+    "advchain_consistency_cw_bwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _I, _L, _L, _I, _P, _I, _P, _P]),
+    "advchain_consistency_cw_ref_bwd": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _I, _L, _L, _I, _P, _I, _P, _P]),
     "advchain_consistency_fused_fwd_bf16": (_I, [_P, _P, _P, _P, _P, _L, _L, _I, _P, _P]),
     "advchain_consistency_fused_bwd_bf16": (_I, [_P, _P, _P, _P, _P, _P, _F, _F, _F, _L, _L, _I, _P, _P]),
     "advchain_seg_loss_workspace": (_L, [_L, _I, _P]),

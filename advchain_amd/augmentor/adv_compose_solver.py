@@ -17,7 +17,7 @@ import math
 import torch
 
 from .. import ops
-from ..common.loss import calc_segmentation_consistency
+from ..common.loss import calc_segmentation_consistency, class_weights_tuple
 from ..common.utils import _disable_tracking_bn_stats, _fix_dropout
 from .adv_affine import AdvAffine
 from .adv_bias import AdvBias
@@ -40,7 +40,7 @@ class ComposeAdversarialTransformSolver(object):
     def __init__(self, chain_of_transforms=[], divergence_types=['mse', 'contour'],
                  divergence_weights=[1.0, 0.5], use_gpu=True, debug=False, if_norm_image=False,
                  min_intensity=None, max_intensity=None, is_gt=False, process_group=None, hip_graph=False,
-                 deterministic=None):
+                 deterministic=None, class_weights=None):
         self.chain_of_transforms = chain_of_transforms
         self.use_gpu = use_gpu
         self.debug = debug
@@ -51,7 +51,7 @@ class ComposeAdversarialTransformSolver(object):
         self.min_intensity = min_intensity
         self.max_intensity = max_intensity
         self.is_gt = is_gt
-        self.class_weights = None
+        self.class_weights = class_weights     # (a property: kept as a tuple of floats)
         self.process_group = process_group     # extension: batch-sharded replicas
         # extension: the whole-batch size when sharded (the sum of the ranks' batches).  None: asked of the group at the start
         # of every call (one all-reduce and one host read-back per call); set it when every call has the same global batch
@@ -70,6 +70,18 @@ class ComposeAdversarialTransformSolver(object):
         self.graph_stats = {"recorded": 0, "captures": 0, "replays": 0, "violations": 0, "refused": 0}
         self._global_batch = None
         self._local_steps = None
+
+    @property
+    def class_weights(self):
+        """Class weights of the consistency loss (calc_segmentation_consistency), for the ascent loop and the returned loss;
+        None: unweighted.  Whatever is assigned -- list, tuple, ndarray, tensor -- is validated and read to the host once, here,
+        and kept as a tuple of floats: a plain attribute, hence part of the hip_graph key (new weights record a new graph), and
+        nothing to read back inside a capture.  The same on every rank of a sharded run."""
+        return self._class_weights
+
+    @class_weights.setter
+    def class_weights(self, value):
+        self._class_weights = class_weights_tuple(value)
 
     # ------------------------------------------------------------------------------- sharding helpers
     def _dist(self):

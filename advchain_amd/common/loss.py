@@ -8,6 +8,7 @@ needs a gradient: the prediction and -- csrc/loss_ref.hip -- the reference).
 Batch sharding: ``global_batch`` overrides N in every normaliser -- mse ~ 1/(N^2 K V^2),
 contour ~ 1/(N V) -- so that the per-shard values SUM to the whole-batch loss and the mse:contour mix
 (hence the ascent direction) does not depend on the shard size."""
+import math
 import warnings
 
 import torch
@@ -25,6 +26,37 @@ def _check_operands(output, reference):
     if output.size(1) > MAX_CLASSES:
         raise NotImplementedError('the consistency kernels take at most %d classes, got %d'
                                   % (MAX_CLASSES, output.size(1)))
+
+
+def class_weights_tuple(class_weights, K=None):
+    """`class_weights` (a list, tuple, ndarray or tensor of K numbers; a device tensor is read to the host, once) as a tuple
+    of floats, or None.  ValueError for anything but one finite, non-negative number per class -- raised before any device
+    work, so a CPU caller sees the same errors.  K=None leaves the length to a later call."""
+    if class_weights is None:
+        return None
+    if isinstance(class_weights, torch.Tensor):
+        class_weights = class_weights.detach().cpu()
+    if hasattr(class_weights, 'tolist'):          # tensor, ndarray
+        class_weights = class_weights.tolist()
+    if not isinstance(class_weights, (list, tuple)) or any(isinstance(w, (list, tuple)) for w in class_weights):
+        raise ValueError('class_weights must be a flat sequence with one number per class')
+    w = tuple(float(x) for x in class_weights)
+    if K is not None and len(w) != K:
+        raise ValueError('class_weights has the wrong length: %d entries for %d classes' % (len(w), K))
+    for i, x in enumerate(w):
+        if math.isnan(x):
+            raise ValueError('class_weights[%d] is NaN' % i)
+        if math.isinf(x):
+            raise ValueError('class_weights[%d] is infinite (%r)' % (i, x))
+        if x < 0:
+            raise ValueError('class_weights[%d] is negative (%r)' % (i, x))
+    return w
+
+
+def _weighted(class_weights, K):
+    """The keyword that hands validated weights to ops.consistency_sums; without weights the call is today's, argument for
+    argument."""
+    return {} if class_weights is None else {'class_w': class_weights_tuple(class_weights, K)}
 
 
 def _pooled(x, scale):
@@ -50,13 +82,18 @@ def calc_segmentation_consistency(output, reference, divergence_types=['kl', 'co
     """Difference between two predictions (logits), same signature as the reference (loss.py:8-87).  `output` and
     `reference` are fp32 or bf16 (a model under autocast), independently: a bf16 operand is read as it is (csrc/loss_lp.hip),
     all arithmetic is fp32 -- the value is the fp32 loss of the upcast operands, an fp32 scalar -- and the gradient of an
-    operand has that operand's dtype (computed in fp32, rounded once).  float16 is refused."""
-    if class_weights is not None:
-        raise NotImplementedError
+    operand has that operand's dtype (computed in fp32, rounded once).  float16 is refused.
+
+    class_weights (the reference documents the parameter and raises): K finite, non-negative numbers w_k -- list, tuple, ndarray
+    or tensor -- used as given, without normalisation; constants (no gradient).  With D = P - T' masked,
+    'mse' sums w_k (m_k D_k)^2, 'kl' sums w_k m_k T'_k (log T'_k - log P_k), 'contour' multiplies the edge energy of object
+    class i by w_i (w_0 does not enter); every normaliser stays as it is, so w = 1 is the unweighted loss.  Weights run the
+    run-time-K kernels (the cw entries of csrc/loss_lp.hip) for every K and dtype pair; None runs the unweighted paths."""
     spatial_dims = output.dim() - 2
     assert spatial_dims == 2 or spatial_dims == 3, 'only support 2d or 3d segmentation'
     assert output.dim() == reference.dim(), 'output and reference must have the same rank'
     K = reference.size(1)
+    weighted = _weighted(class_weights, K)
     _check_operands(output, reference)
     if any(scale != 0 for scale in scales):
         # a bf16 operand is upcast ONCE, differentiably, in front of the AvgPool: the pool runs in fp32 (the value stays the
@@ -98,23 +135,24 @@ def calc_segmentation_consistency(output, reference, divergence_types=['kl', 'co
             w_kl = sum(w for t, w in zip(divergence_types, divergence_weights) if t == 'kl')
             c_kl = (w_kl / (float(Ng) * V)) if has_kl else 0.0
             coef = [(2 ** scale) * c for c in (c_mse, c_a, c_b, c_kl)]
-            val, _ = ops.consistency_sums(out_s, ref_s, m, coef, ref_is_prob=is_gt, want_edges=has_cnt)
+            val, _ = ops.consistency_sums(out_s, ref_s, m, coef, ref_is_prob=is_gt, want_edges=has_cnt, **weighted)
             dist = val if isinstance(dist, float) and dist == 0. else dist + val     # (0. + x is x: no launch for it)
     # (x / 1.0 is x: the reference's division by the number of scales is skipped for its only call, scales = [0])
     return dist if len(scales) == 1 else dist / (1.0 * len(scales))
 
 
-def kl_divergence(reference, pred, mask=None, is_gt=False, global_batch=None):
-    """KL(P||Q) of two logit maps (loss.py:223-249): the 'kl' term of the fused kernels on its own.  fp32 or bf16 operands,
-    as in :func:`calc_segmentation_consistency`."""
+def kl_divergence(reference, pred, mask=None, is_gt=False, global_batch=None, class_weights=None):
+    """KL(P||Q) of two logit maps (loss.py:223-249): the 'kl' term of the fused kernels on its own.  fp32 or bf16 operands
+    and class_weights (an extension: class k enters w_k times) as in :func:`calc_segmentation_consistency`."""
     K = pred.size(1)
+    weighted = _weighted(class_weights, K)
     _check_operands(pred, reference)
     V = 1
     for s in pred.shape[2:]:
         V *= s
     Ng = pred.shape[0] if global_batch is None else int(global_batch)
     val, _ = ops.consistency_sums(pred, reference, _single_channel_mask(mask, K), [0.0, 0.0, 0.0, 1.0 / (float(Ng) * V)],
-                                  ref_is_prob=is_gt, want_edges=False)
+                                  ref_is_prob=is_gt, want_edges=False, **weighted)
     return val
 
 

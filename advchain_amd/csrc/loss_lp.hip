@@ -5,6 +5,9 @@
 //                                                        advchain/common/loss.py:8-87,102-220,223-249 (Q13, Q14) and what
 //                                                        autograd gives both operands
 //
+//   advchain_consistency_cw_fwd / cw_bwd / cw_ref_bwd <- the same with class weights w_k (a parameter the reference documents
+//                                                        and raises on): the same kernels with a trailing weight argument
+//
 // The mathematics and the arithmetic are those of loss_wide.hip (forward, prediction side) and loss_ref.hip (reference side);
 // see their headers for the notation.  What differs is the STORAGE: each logit operand is read as fp32 or as bf16 (raw 16-bit
 // words), independently -- bf16 -> fp32 is exact, so the forward is the fp32 loss of the upcast operands -- and each gradient
@@ -31,6 +34,8 @@
 // in bf16) at any alignment; only k_lp_stats has a vector form.  The adjoint stencils skip the zero-weight taps (as
 // loss_ref.hip does).  No atomics on the gradients and no shared accumulator: bit-reproducible.  Streaming + 3^d stencil:
 // memory-bound, no MFMA.
+#include <stdio.h>
+
 #include "loss_common.h"
 
 namespace advchain {
@@ -53,6 +58,17 @@ template <typename ST>
 __device__ __forceinline__ void st1(ST* __restrict__ p, float x) {
   if constexpr (sizeof(ST) == 4) p[0] = x;
   else p[0] = lp_to_bf16(x);
+}
+
+// Class weights.  Each kernel ends in a parameter pack W... that is EMPTY (the lp entries: the unweighted loss, the very
+// kernel arguments and instructions it had without the pack) or ONE `const float*` (the cw entries: K device floats, w_k read
+// with a uniform load once per class and workgroup; no per-voxel traffic).  The weights do not change while a kernel runs, so
+// they are read through the constant address space: there a uniform load is a scalar one (s_load_dword) whatever the kernel
+// stores between two classes -- as a plain global load the compiler keeps it on the vector unit in the loops that store R or
+// a gradient.
+__device__ __forceinline__ float lp_cw(int) { return 1.f; }
+__device__ __forceinline__ float lp_cw(int k, const float* cw) {
+  return ((const __attribute__((address_space(4))) float*)cw)[k];
 }
 
 // 4 consecutive values of one plane: WIDE one 16-byte (fp32) / 8-byte (bf16) access, else `cnt` (1..4) scalar ones
@@ -123,10 +139,11 @@ __device__ __forceinline__ void lp_stage_R(float (*buf)[WTile<DIM>::NH], const f
 }
 
 // A lane owns the voxels 4 i .. 4 i + 3 of a batch entry (i its index in the grid), WIDE or not.
-template <typename PT, typename RT, bool WIDE>
+template <typename PT, typename RT, bool WIDE, typename... W>
 __global__ void __launch_bounds__(kBlock)
 k_lp_stats(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* __restrict__ mask, float* __restrict__ stats,
-           float* __restrict__ sums, int K, int V, int mask_ch, int ref_is_prob, int want_kl) {
+           float* __restrict__ sums, int K, int V, int mask_ch, int ref_is_prob, int want_kl, W... cw) {
+  constexpr bool CW = sizeof...(W) != 0;
   __shared__ float smem[8];
   const int n = blockIdx.y;
   const int64_t v64 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * 4;
@@ -166,6 +183,7 @@ k_lp_stats(const PT* __restrict__ pred, const RT* __restrict__ ref, const float*
       ld4<PT, WIDE>(pn + (int64_t)k * V, cnt, a);
       ld4<RT, WIDE>(rn + (int64_t)k * V, cnt, b);
       if (mask && mask_ch > 1) ld4<float, WIDE>(mask + ((int64_t)n * mask_ch + k) * V + v, cnt, m);
+      const float wk = lp_cw(k, cw...);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const float zp = a[q] - mp[q], zr = b[q] - mr[q];
@@ -174,8 +192,13 @@ k_lp_stats(const PT* __restrict__ pred, const RT* __restrict__ ref, const float*
         const float mm = (mask && mask_ch > 1) ? m[q] : m1[q];
         const float e = p * mm - t * mm;
         if (q < cnt) {
-          acc[0] += e * e;
-          if (want_kl) acc[1] += kl_term(t, zr - lsr[q], zp - lsp[q], mm, ref_is_prob);
+          if constexpr (CW) {
+            acc[0] += wk * (e * e);
+            if (want_kl) acc[1] += wk * kl_term(t, zr - lsr[q], zp - lsp[q], mm, ref_is_prob);
+          } else {
+            acc[0] += e * e;
+            if (want_kl) acc[1] += kl_term(t, zr - lsr[q], zp - lsp[q], mm, ref_is_prob);
+          }
         }
       }
     }
@@ -192,11 +215,12 @@ k_lp_stats(const PT* __restrict__ pred, const RT* __restrict__ ref, const float*
   }
 }
 
-template <typename PT, typename RT, int DIM>
+template <typename PT, typename RT, int DIM, typename... W>
 __global__ void __launch_bounds__(kBlock)
 k_lp_edge(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* __restrict__ mask,
           const float* __restrict__ stats, float* __restrict__ R, float* __restrict__ sums, int K, Dims d, int mask_ch,
-          int ref_is_prob) {
+          int ref_is_prob, W... cw) {
+  constexpr bool CW = sizeof...(W) != 0;
   using T = WTile<DIM>;
   __shared__ float lds[2][T::NH];
   __shared__ float smem[8];
@@ -227,6 +251,7 @@ k_lp_edge(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* 
     const PT* pk = pred + ((int64_t)n * K + k) * V;
     const RT* rk = ref + ((int64_t)n * K + k) * V;
     float* buf = lds[k & 1];
+    const float wk = lp_cw(k, cw...);
 #pragma unroll
     for (int j = 0; j < T::SLOTS; ++j) {
       const int e = threadIdx.x + j * kBlock;
@@ -244,9 +269,14 @@ k_lp_edge(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* 
       if (ov[j] >= 0) {
         const float m = om[j];
         const float ea = ga * m, eb = gb * m;
-        acc[0] += ea * ea;
-        acc[1] += eb * eb;
-        if (R) {
+        if constexpr (CW) {
+          acc[0] += wk * (ea * ea);
+          acc[1] += wk * (eb * eb);
+        } else {
+          acc[0] += ea * ea;
+          acc[1] += eb * eb;
+        }
+        if (R) {                // (R_k is saved unweighted: the backward scales g_k)
           R[((int64_t)n * 2 * (K - 1) + 2 * (k - 1)) * V + ov[j]] = 2.f * m * m * ga;
           R[((int64_t)n * 2 * (K - 1) + 2 * (k - 1) + 1) * V + ov[j]] = 2.f * m * m * gb;
         }
@@ -263,11 +293,12 @@ k_lp_edge(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* 
 // grad_pred.  Sweep 0 leaves dot = sum_k g_k P_k and sum_k m_k T'_k in registers and stores nothing; sweep 1 recomputes g_k and
 // stores P_k (g_k - dot) + the 'kl' part, rounded once.  The barrier between the sweeps: with an even K the last class of
 // sweep 0 and the first staged class of sweep 1 use the same LDS buffer.
-template <typename PT, typename RT, int DIM>
+template <typename PT, typename RT, int DIM, typename... W>
 __global__ void __launch_bounds__(kBlock)
 k_lp_bwd(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* __restrict__ stats, const float* __restrict__ R,
          const float* __restrict__ mask, const float* __restrict__ gscale, PT* __restrict__ gpred, float c_mse, float c_a,
-         float c_b, float c_kl, int ref_is_prob, int K, Dims d, int mask_ch) {
+         float c_b, float c_kl, int ref_is_prob, int K, Dims d, int mask_ch, W... cw) {
+  constexpr bool CW = sizeof...(W) != 0;
   using T = WTile<DIM>;
   __shared__ float lds[2][2][T::NH];
   const T tile(d);
@@ -297,6 +328,7 @@ k_lp_bwd(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* _
     if (sweep) __syncthreads();
     for (int k = 0; k < K; ++k) {
       const int64_t plane = ((int64_t)n * K + k) * V;
+      const float wk = lp_cw(k, cw...);
       float (*buf)[T::NH] = lds[k & 1];
       if (edges && k >= 1) {
         const float* Ra = R + ((int64_t)n * 2 * (K - 1) + 2 * (k - 1)) * V;
@@ -316,13 +348,15 @@ k_lp_bwd(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* _
           lp_adjoint_stencil<DIM>(buf[0], buf[1], oc[j], ta, tb);
           g += c_a * ta + c_b * tb;
         }
+        if constexpr (CW) g *= wk;
         g *= gs;
+        const float wm = CW ? wk * m : m;     // 'kl' takes w_k m_k where the unweighted loss takes m_k
         if (sweep == 0) {
           dot[j] += g * p;
-          if (c_kl != 0.f) klS[j] += m * kl_prob(t, ref_is_prob);
+          if (c_kl != 0.f) klS[j] += wm * kl_prob(t, ref_is_prob);
         } else if (ov[j] >= 0) {
           float o = p * (g - dot[j]);     // the softmax Jacobian
-          if (c_kl != 0.f) o += gs * c_kl * (p * klS[j] - m * kl_prob(t, ref_is_prob));   // 'kl': gs c_kl (P_j sum_k m_k T'_k - m_j T'_j)
+          if (c_kl != 0.f) o += gs * c_kl * (p * klS[j] - wm * kl_prob(t, ref_is_prob));   // 'kl': gs c_kl (P_j sum_k m_k T'_k - m_j T'_j)
           st1<PT>(gpred + plane + c, o);
         }
       }
@@ -332,12 +366,13 @@ k_lp_bwd(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* _
 
 // grad_ref.  h_k = -g_k + gs c_kl m_k (log T_k + 1 - log P_k); ref_is_prob: h_k is the gradient (one sweep); logits: sweep 0
 // leaves sum_j T_j h_j in registers, sweep 1 recomputes h_k and stores T_k (h_k - sum), rounded once.
-template <typename PT, typename RT, int DIM>
+template <typename PT, typename RT, int DIM, typename... W>
 __global__ void __launch_bounds__(kBlock)
 k_lp_ref_grad(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* __restrict__ stats,
               const float* __restrict__ R, const float* __restrict__ mask, const float* __restrict__ gscale,
               RT* __restrict__ gref, float c_mse, float c_a, float c_b, float c_kl, int ref_is_prob, int K, Dims d,
-              int mask_ch) {
+              int mask_ch, W... cw) {
+  constexpr bool CW = sizeof...(W) != 0;
   using T = WTile<DIM>;
   __shared__ float lds[2][2][T::NH];
   const T tile(d);
@@ -371,6 +406,7 @@ k_lp_ref_grad(const PT* __restrict__ pred, const RT* __restrict__ ref, const flo
     if (sweep) __syncthreads();
     for (int k = 0; k < K; ++k) {
       const int64_t plane = batch + (int64_t)k * V;
+      const float wk = lp_cw(k, cw...);
       float (*buf)[T::NH] = lds[k & 1];
       if (edges && k >= 1) {
         const float* Ra = R + ((int64_t)n * 2 * (K - 1) + 2 * (k - 1)) * V;
@@ -391,8 +427,9 @@ k_lp_ref_grad(const PT* __restrict__ pred, const RT* __restrict__ ref, const flo
           lp_adjoint_stencil<DIM>(buf[0], buf[1], oc[j], ta, tb);
           g += c_a * ta + c_b * tb;
         }
+        if constexpr (CW) g *= wk;
         float hk = -(g * gs);
-        if (kl) hk += ckl * m * ((zr - zp) + lgd[j] + 1.f);
+        if (kl) hk += ckl * (CW ? wk * m : m) * ((zr - zp) + lgd[j] + 1.f);
         if (sweep == 0) {
           dot[j] += t * hk;
           if (ref_is_prob && ov[j] >= 0) st1<RT>(gref + plane + c, hk);     // already the gradient
@@ -408,9 +445,10 @@ inline bool lp_nk_ok(int64_t N, int64_t K) { return N >= 0 && N < 65536 && K >= 
 inline bool lp_flag_ok(int f) { return f == 0 || f == 1; }
 inline bool lp_aligned(const void* p, int bytes) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % bytes) == 0; }
 
-template <typename PT, typename RT>
+// w: nothing (the lp entries) or the K class weights in device memory (the cw entries); it selects the kernels' pack
+template <typename PT, typename RT, typename... W>
 void lp_launch_fwd(hipStream_t st, const void* pred, const void* ref, const float* mask, float* stats, float* R, float* sums,
-                   int N, int K, int ndim, Dims d, int mask_ch, int ref_is_prob, int want_edges, int want_kl) {
+                   int N, int K, int ndim, Dims d, int mask_ch, int ref_is_prob, int want_edges, int want_kl, W... w) {
   const int V = (int)d.voxels();
   const PT* p = (const PT*)pred;
   const RT* r = (const RT*)ref;
@@ -419,45 +457,47 @@ void lp_launch_fwd(hipStream_t st, const void* pred, const void* ref, const floa
   const bool wide = V % 4 == 0 && lp_aligned(pred, 4 * (int)sizeof(PT)) && lp_aligned(ref, 4 * (int)sizeof(RT)) &&
                     lp_aligned(mask, 16) && lp_aligned(stats, 16);
   if (wide)
-    hipLaunchKernelGGL((k_lp_stats<PT, RT, true>), g, b, 0, st, p, r, mask, stats, sums, K, V, mask_ch, ref_is_prob, want_kl);
+    hipLaunchKernelGGL((k_lp_stats<PT, RT, true>), g, b, 0, st, p, r, mask, stats, sums, K, V, mask_ch, ref_is_prob, want_kl,
+                       w...);
   else
-    hipLaunchKernelGGL((k_lp_stats<PT, RT, false>), g, b, 0, st, p, r, mask, stats, sums, K, V, mask_ch, ref_is_prob, want_kl);
+    hipLaunchKernelGGL((k_lp_stats<PT, RT, false>), g, b, 0, st, p, r, mask, stats, sums, K, V, mask_ch, ref_is_prob, want_kl,
+                       w...);
   if (want_edges && K > 1) {
     if (ndim == 3)
       hipLaunchKernelGGL((k_lp_edge<PT, RT, 3>), dim3((unsigned)WTile<3>::count(d), (unsigned)N), b, 0, st, p, r, mask, stats, R,
-                         sums, K, d, mask_ch, ref_is_prob);
+                         sums, K, d, mask_ch, ref_is_prob, w...);
     else
       hipLaunchKernelGGL((k_lp_edge<PT, RT, 2>), dim3((unsigned)WTile<2>::count(d), (unsigned)N), b, 0, st, p, r, mask, stats, R,
-                         sums, K, d, mask_ch, ref_is_prob);
+                         sums, K, d, mask_ch, ref_is_prob, w...);
   }
 }
 
-template <typename PT, typename RT>
+template <typename PT, typename RT, typename... W>
 void lp_launch_bwd(hipStream_t st, const void* pred, const void* ref, const float* stats, const float* R, const float* mask,
                    const float* gs, void* gpred, float c_mse, float c_a, float c_b, float c_kl, int ref_is_prob, int N, int K,
-                   int ndim, Dims d, int mask_ch) {
+                   int ndim, Dims d, int mask_ch, W... w) {
   if (ndim == 3)
     hipLaunchKernelGGL((k_lp_bwd<PT, RT, 3>), dim3((unsigned)WTile<3>::count(d), (unsigned)N), dim3(kBlock), 0, st,
                        (const PT*)pred, (const RT*)ref, stats, R, mask, gs, (PT*)gpred, c_mse, c_a, c_b, c_kl, ref_is_prob, K, d,
-                       mask_ch);
+                       mask_ch, w...);
   else
     hipLaunchKernelGGL((k_lp_bwd<PT, RT, 2>), dim3((unsigned)WTile<2>::count(d), (unsigned)N), dim3(kBlock), 0, st,
                        (const PT*)pred, (const RT*)ref, stats, R, mask, gs, (PT*)gpred, c_mse, c_a, c_b, c_kl, ref_is_prob, K, d,
-                       mask_ch);
+                       mask_ch, w...);
 }
 
-template <typename PT, typename RT>
+template <typename PT, typename RT, typename... W>
 void lp_launch_ref(hipStream_t st, const void* pred, const void* ref, const float* stats, const float* R, const float* mask,
                    const float* gs, void* gref, float c_mse, float c_a, float c_b, float c_kl, int ref_is_prob, int N, int K,
-                   int ndim, Dims d, int mask_ch) {
+                   int ndim, Dims d, int mask_ch, W... w) {
   if (ndim == 3)
     hipLaunchKernelGGL((k_lp_ref_grad<PT, RT, 3>), dim3((unsigned)WTile<3>::count(d), (unsigned)N), dim3(kBlock), 0, st,
                        (const PT*)pred, (const RT*)ref, stats, R, mask, gs, (RT*)gref, c_mse, c_a, c_b, c_kl, ref_is_prob, K, d,
-                       mask_ch);
+                       mask_ch, w...);
   else
     hipLaunchKernelGGL((k_lp_ref_grad<PT, RT, 2>), dim3((unsigned)WTile<2>::count(d), (unsigned)N), dim3(kBlock), 0, st,
                        (const PT*)pred, (const RT*)ref, stats, R, mask, gs, (RT*)gref, c_mse, c_a, c_b, c_kl, ref_is_prob, K, d,
-                       mask_ch);
+                       mask_ch, w...);
 }
 
 // one of the four storage pairs
@@ -472,6 +512,65 @@ void lp_launch_ref(hipStream_t st, const void* pred, const void* ref, const floa
     }                                                          \
   } while (0)
 
+// an argument error of entry `who` (the lp and the cw entries share their bodies)
+#define ADVCHAIN_LP_CHECK(cond, text)                          \
+  do {                                                         \
+    if (!(cond)) {                                             \
+      char msg_[160];                                          \
+      snprintf(msg_, sizeof(msg_), "%s: %s", who, text);       \
+      advchain_set_error_(msg_);                               \
+      return ADVCHAIN_ERR_ARG;                                 \
+    }                                                          \
+  } while (0)
+
+// the checks every entry makes; `out` is the tensor it writes besides stats
+#define ADVCHAIN_LP_CHECK_COMMON(out)                                                                          \
+  ADVCHAIN_LP_CHECK(pred && ref && stats && out && dims, "null pointer");                                      \
+  ADVCHAIN_LP_CHECK(!weighted || class_w, "null pointer (class_w)");                                           \
+  ADVCHAIN_LP_CHECK(lp_flag_ok(pred_bf16) && lp_flag_ok(ref_bf16), "an operand is fp32 (0) or bf16 (1)");      \
+  ADVCHAIN_LP_CHECK(ldims_ok(ndim, dims), "bad dims");                                                         \
+  ADVCHAIN_LP_CHECK(lp_nk_ok(N, K), "bad N/K (N < 65536, 1 <= K < 65536)");                                    \
+  ADVCHAIN_LP_CHECK(!mask || mask_channels == 1 || mask_channels == K, "mask must have 1 or K channels");      \
+  const Dims d = lmake_dims(ndim, dims);                                                                       \
+  ADVCHAIN_LP_CHECK(d.voxels() < (1ll << 31), "volume too large")
+
+int lp_fwd(const char* who, bool weighted, const void* pred, int pred_bf16, const void* ref, int ref_bf16, const float* mask,
+           float* stats, float* R, float* sums, int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels,
+           int ref_is_prob, int want_edges, int want_kl, const float* class_w, void* stream) {
+  ADVCHAIN_LP_CHECK_COMMON(sums);
+  if (N == 0) return ADVCHAIN_OK;
+  if (weighted)
+    ADVCHAIN_LP_DISPATCH(lp_launch_fwd, pred_bf16, ref_bf16, (hipStream_t)stream, pred, ref, mask, stats, R, sums, (int)N, (int)K,
+                         ndim, d, mask_channels, ref_is_prob, want_edges, want_kl, class_w);
+  else
+    ADVCHAIN_LP_DISPATCH(lp_launch_fwd, pred_bf16, ref_bf16, (hipStream_t)stream, pred, ref, mask, stats, R, sums, (int)N, (int)K,
+                         ndim, d, mask_channels, ref_is_prob, want_edges, want_kl);
+  ADVCHAIN_LAUNCH_CHECK();
+  return ADVCHAIN_OK;
+}
+
+int lp_bwd(const char* who, bool weighted, bool ref_side, const void* pred, int pred_bf16, const void* ref, int ref_bf16,
+           const float* stats, const float* R, const float* mask, const float* grad_scale, void* grad, float c_mse, float c_a,
+           float c_b, float c_kl, int ref_is_prob, int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels,
+           const float* class_w, void* stream) {
+  ADVCHAIN_LP_CHECK_COMMON(grad);
+  if (N == 0) return ADVCHAIN_OK;
+  if (K == 1) R = nullptr;        // (no object class: nothing was saved)
+#define ADVCHAIN_LP_BWD_ARGS                                                                                              \
+  (hipStream_t) stream, pred, ref, stats, R, mask, grad_scale, grad, c_mse, c_a, c_b, c_kl, ref_is_prob, (int)N, (int)K, ndim, d, \
+      mask_channels
+  if (ref_side) {
+    if (weighted) ADVCHAIN_LP_DISPATCH(lp_launch_ref, pred_bf16, ref_bf16, ADVCHAIN_LP_BWD_ARGS, class_w);
+    else ADVCHAIN_LP_DISPATCH(lp_launch_ref, pred_bf16, ref_bf16, ADVCHAIN_LP_BWD_ARGS);
+  } else {
+    if (weighted) ADVCHAIN_LP_DISPATCH(lp_launch_bwd, pred_bf16, ref_bf16, ADVCHAIN_LP_BWD_ARGS, class_w);
+    else ADVCHAIN_LP_DISPATCH(lp_launch_bwd, pred_bf16, ref_bf16, ADVCHAIN_LP_BWD_ARGS);
+  }
+#undef ADVCHAIN_LP_BWD_ARGS
+  ADVCHAIN_LAUNCH_CHECK();
+  return ADVCHAIN_OK;
+}
+
 }  // namespace
 }  // namespace advchain
 
@@ -482,56 +581,48 @@ extern "C" {
 int advchain_consistency_lp_fwd(const void* pred, int pred_bf16, const void* ref, int ref_bf16, const float* mask, float* stats,
                                 float* R, float* sums, int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels,
                                 int ref_is_prob, int want_edges, int want_kl, void* stream) {
-  ADVCHAIN_CHECK_ARG(pred && ref && stats && sums && dims, "consistency_lp_fwd: null pointer");
-  ADVCHAIN_CHECK_ARG(lp_flag_ok(pred_bf16) && lp_flag_ok(ref_bf16), "consistency_lp_fwd: an operand is fp32 (0) or bf16 (1)");
-  ADVCHAIN_CHECK_ARG(ldims_ok(ndim, dims), "consistency_lp_fwd: bad dims");
-  ADVCHAIN_CHECK_ARG(lp_nk_ok(N, K), "consistency_lp_fwd: bad N/K (N < 65536, 1 <= K < 65536)");
-  ADVCHAIN_CHECK_ARG(!mask || mask_channels == 1 || mask_channels == K, "consistency_lp_fwd: mask must have 1 or K channels");
-  const Dims d = lmake_dims(ndim, dims);
-  ADVCHAIN_CHECK_ARG(d.voxels() < (1ll << 31), "consistency_lp_fwd: volume too large");
-  if (N == 0) return ADVCHAIN_OK;
-  ADVCHAIN_LP_DISPATCH(lp_launch_fwd, pred_bf16, ref_bf16, (hipStream_t)stream, pred, ref, mask, stats, R, sums, (int)N, (int)K,
-                       ndim, d, mask_channels, ref_is_prob, want_edges, want_kl);
-  ADVCHAIN_LAUNCH_CHECK();
-  return ADVCHAIN_OK;
+  return lp_fwd("consistency_lp_fwd", false, pred, pred_bf16, ref, ref_bf16, mask, stats, R, sums, N, K, ndim, dims,
+                mask_channels, ref_is_prob, want_edges, want_kl, nullptr, stream);
 }
 
 int advchain_consistency_lp_bwd(const void* pred, int pred_bf16, const void* ref, int ref_bf16, const float* stats,
                                 const float* R, const float* mask, const float* grad_scale, void* grad_pred, float c_mse,
                                 float c_a, float c_b, float c_kl, int ref_is_prob, int64_t N, int64_t K, int ndim,
                                 const int64_t* dims, int mask_channels, void* stream) {
-  ADVCHAIN_CHECK_ARG(pred && ref && stats && grad_pred && dims, "consistency_lp_bwd: null pointer");
-  ADVCHAIN_CHECK_ARG(lp_flag_ok(pred_bf16) && lp_flag_ok(ref_bf16), "consistency_lp_bwd: an operand is fp32 (0) or bf16 (1)");
-  ADVCHAIN_CHECK_ARG(ldims_ok(ndim, dims), "consistency_lp_bwd: bad dims");
-  ADVCHAIN_CHECK_ARG(lp_nk_ok(N, K), "consistency_lp_bwd: bad N/K (N < 65536, 1 <= K < 65536)");
-  ADVCHAIN_CHECK_ARG(!mask || mask_channels == 1 || mask_channels == K, "consistency_lp_bwd: mask must have 1 or K channels");
-  const Dims d = lmake_dims(ndim, dims);
-  ADVCHAIN_CHECK_ARG(d.voxels() < (1ll << 31), "consistency_lp_bwd: volume too large");
-  if (N == 0) return ADVCHAIN_OK;
-  if (K == 1) R = nullptr;        // (no object class: nothing was saved)
-  ADVCHAIN_LP_DISPATCH(lp_launch_bwd, pred_bf16, ref_bf16, (hipStream_t)stream, pred, ref, stats, R, mask, grad_scale, grad_pred,
-                       c_mse, c_a, c_b, c_kl, ref_is_prob, (int)N, (int)K, ndim, d, mask_channels);
-  ADVCHAIN_LAUNCH_CHECK();
-  return ADVCHAIN_OK;
+  return lp_bwd("consistency_lp_bwd", false, false, pred, pred_bf16, ref, ref_bf16, stats, R, mask, grad_scale, grad_pred, c_mse,
+                c_a, c_b, c_kl, ref_is_prob, N, K, ndim, dims, mask_channels, nullptr, stream);
 }
 
 int advchain_consistency_lp_ref_bwd(const void* pred, int pred_bf16, const void* ref, int ref_bf16, const float* stats,
                                     const float* R, const float* mask, const float* grad_scale, void* grad_ref, float c_mse,
                                     float c_a, float c_b, float c_kl, int ref_is_prob, int64_t N, int64_t K, int ndim,
                                     const int64_t* dims, int mask_channels, void* stream) {
-  ADVCHAIN_CHECK_ARG(pred && ref && stats && grad_ref && dims, "consistency_lp_ref_bwd: null pointer");
-  ADVCHAIN_CHECK_ARG(lp_flag_ok(pred_bf16) && lp_flag_ok(ref_bf16), "consistency_lp_ref_bwd: an operand is fp32 (0) or bf16 (1)");
-  ADVCHAIN_CHECK_ARG(ldims_ok(ndim, dims), "consistency_lp_ref_bwd: bad dims");
-  ADVCHAIN_CHECK_ARG(lp_nk_ok(N, K), "consistency_lp_ref_bwd: bad N/K (N < 65536, 1 <= K < 65536)");
-  ADVCHAIN_CHECK_ARG(!mask || mask_channels == 1 || mask_channels == K, "consistency_lp_ref_bwd: mask must have 1 or K channels");
-  const Dims d = lmake_dims(ndim, dims);
-  ADVCHAIN_CHECK_ARG(d.voxels() < (1ll << 31), "consistency_lp_ref_bwd: volume too large");
-  if (N == 0) return ADVCHAIN_OK;
-  if (K == 1) R = nullptr;        // (no object class: nothing was saved)
-  ADVCHAIN_LP_DISPATCH(lp_launch_ref, pred_bf16, ref_bf16, (hipStream_t)stream, pred, ref, stats, R, mask, grad_scale, grad_ref,
-                       c_mse, c_a, c_b, c_kl, ref_is_prob, (int)N, (int)K, ndim, d, mask_channels);
-  ADVCHAIN_LAUNCH_CHECK();
-  return ADVCHAIN_OK;
+  return lp_bwd("consistency_lp_ref_bwd", false, true, pred, pred_bf16, ref, ref_bf16, stats, R, mask, grad_scale, grad_ref,
+                c_mse, c_a, c_b, c_kl, ref_is_prob, N, K, ndim, dims, mask_channels, nullptr, stream);
+}
+
+// the class-weighted entries: the same kernels with CW = true, for all four storage pairs (fp32-fp32 included)
+int advchain_consistency_cw_fwd(const void* pred, int pred_bf16, const void* ref, int ref_bf16, const float* mask, float* stats,
+                                float* R, float* sums, int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels,
+                                int ref_is_prob, int want_edges, int want_kl, const float* class_w, void* stream) {
+  return lp_fwd("consistency_cw_fwd", true, pred, pred_bf16, ref, ref_bf16, mask, stats, R, sums, N, K, ndim, dims,
+                mask_channels, ref_is_prob, want_edges, want_kl, class_w, stream);
+}
+
+int advchain_consistency_cw_bwd(const void* pred, int pred_bf16, const void* ref, int ref_bf16, const float* stats,
+                                const float* R, const float* mask, const float* grad_scale, void* grad_pred, float c_mse,
+                                float c_a, float c_b, float c_kl, int ref_is_prob, int64_t N, int64_t K, int ndim,
+                                const int64_t* dims, int mask_channels, const float* class_w, void* stream) {
+  return lp_bwd("consistency_cw_bwd", true, false, pred, pred_bf16, ref, ref_bf16, stats, R, mask, grad_scale, grad_pred, c_mse,
+                c_a, c_b, c_kl, ref_is_prob, N, K, ndim, dims, mask_channels, class_w, stream);
+}
+
+int advchain_consistency_cw_ref_bwd(const void* pred, int pred_bf16, const void* ref, int ref_bf16, const float* stats,
+                                    const float* R, const float* mask, const float* grad_scale, void* grad_ref, float c_mse,
+                                    float c_a, float c_b, float c_kl, int ref_is_prob, int64_t N, int64_t K, int ndim,
+                                    const int64_t* dims, int mask_channels, const float* class_w, void* stream) {
+  return lp_bwd("consistency_cw_ref_bwd", true, true, pred, pred_bf16, ref, ref_bf16, stats, R, mask, grad_scale, grad_ref,
+                c_mse, c_a, c_b, c_kl, ref_is_prob, N, K, ndim, dims, mask_channels, class_w, stream);
 }
 
 }  // extern "C"

@@ -377,6 +377,25 @@ def cached_ones(shape, device):
     return t
 
 
+_CLASS_W = {}
+
+
+def class_weights_device(values, device):
+    """The class weights `values` (a tuple of floats) as K device floats, cached per (device, values): one host-device copy at
+    the first use of a weight vector, none -- and no synchronisation -- after it.  Read-only.  A capture keeps the tensor it
+    read alive with its plan, so that dropping old entries here cannot free what a graph replays."""
+    key = (str(device), values)
+    t = _CLASS_W.get(key)
+    if t is None:
+        if len(_CLASS_W) > 64:
+            _CLASS_W.clear()
+        t = _CLASS_W[key] = torch.tensor(values, dtype=torch.float32, device=device)
+    plan = _PLAN
+    if plan is not None and plan.is_frozen:
+        plan.persistent.setdefault(("class_w",) + key, t)
+    return t
+
+
 def squaring_halo(disp, d):
     """Displacement bound for the backward of one squaring from the MEASURED displacement of its input (voxels).
     Negative = exact (the gather-form adjoint then needs no overflow list): the measurement uses the kernels' own
@@ -1558,16 +1577,20 @@ class _Consistency(torch.autograd.Function):
     prediction logits (one launch of the forward family's own backward entry) and w.r.t. the reference (one launch of
     advchain_consistency_ref_bwd, csrc/loss_ref.hip, whichever forward family ran); each is launched only when its operand
     needs a gradient.  A reference given as probabilities (ref_is_prob) enters 'mse' and 'contour' as it is and 'kl' through a
-    where() that cuts the graph: with 'kl' alone its gradient is None and nothing is launched.  The mask is a constant."""
+    where() that cuts the graph: with 'kl' alone its gradient is None and nothing is launched.  The mask is a constant.
+    class_w (a tuple of K floats, or None): constant class weights inside S0, SA/SB (object classes) and SKL -- the cw entries
+    of csrc/loss_lp.hip for every K and either storage type; None runs the unweighted families."""
 
     @staticmethod
-    def forward(ctx, pred, ref, mask, coef, ref_is_prob, want_edges):
+    def forward(ctx, pred, ref, mask, coef, ref_is_prob, want_edges, class_w=None):
         pred, ref = _dev_logits(pred, "pred"), _dev_logits(ref, "reference")
-        if pred.dtype != torch.float32 or ref.dtype != torch.float32:
+        if class_w is not None and len(class_w) != pred.shape[1]:
+            raise ValueError("class_w must have %d entries (one per class), got %d" % (pred.shape[1], len(class_w)))
+        if class_w is not None or pred.dtype != torch.float32 or ref.dtype != torch.float32:
             if isinstance(mask, torch.Tensor) and mask.dtype in (torch.bfloat16, torch.float16, torch.float64):
                 mask = mask.float()           # (small: the kernels read an fp32 mask)
             mask = None if mask is None else _dev(mask, "mask")
-            return _Consistency._forward_lp(ctx, pred, ref, mask, coef, ref_is_prob, want_edges)
+            return _Consistency._forward_lp(ctx, pred, ref, mask, coef, ref_is_prob, want_edges, class_w)
         mask = None if mask is None else _dev(mask, "mask")
         N, K = pred.shape[:2]
         nd = pred.dim() - 2
@@ -1635,8 +1658,9 @@ class _Consistency(torch.autograd.Function):
         return value, sums
 
     @staticmethod
-    def _forward_lp(ctx, pred, ref, mask, coef, ref_is_prob, want_edges):
-        """At least one operand stored in bf16 (csrc/loss_lp.hip): the run-time-K scheme for every K, read natively."""
+    def _forward_lp(ctx, pred, ref, mask, coef, ref_is_prob, want_edges, class_w=None):
+        """At least one operand stored in bf16, or class weights (csrc/loss_lp.hip): the run-time-K scheme for every K, each
+        operand read in its own storage type."""
         N, K = pred.shape[:2]
         nd = pred.dim() - 2
         dims = _lib.dims_array(pred.shape[2:])
@@ -1652,11 +1676,18 @@ class _Consistency(torch.autograd.Function):
         slots = _persistent_zeros("loss", (4, 64), pred.device)
         stats = torch.empty((N, 4) + tuple(pred.shape[2:]), device=pred.device, dtype=torch.float32)
         lib = _lib.load()
+        cw = None if class_w is None else class_weights_device(class_w, pred.device)
         try:
-            _lib.check(lib.advchain_consistency_lp_fwd(
-                _ptr(pred), int(pred.dtype == torch.bfloat16), _ptr(ref), int(ref.dtype == torch.bfloat16), _ptr(mask),
-                _ptr(stats), _ptr(R), _ptr(slots), N, K, nd, dims, mch, int(ref_is_prob), int(want_edges), int(want_kl),
-                _stream()), "consistency_lp_fwd")
+            if cw is None:
+                _lib.check(lib.advchain_consistency_lp_fwd(
+                    _ptr(pred), int(pred.dtype == torch.bfloat16), _ptr(ref), int(ref.dtype == torch.bfloat16), _ptr(mask),
+                    _ptr(stats), _ptr(R), _ptr(slots), N, K, nd, dims, mch, int(ref_is_prob), int(want_edges), int(want_kl),
+                    _stream()), "consistency_lp_fwd")
+            else:
+                _lib.check(lib.advchain_consistency_cw_fwd(
+                    _ptr(pred), int(pred.dtype == torch.bfloat16), _ptr(ref), int(ref.dtype == torch.bfloat16), _ptr(mask),
+                    _ptr(stats), _ptr(R), _ptr(slots), N, K, nd, dims, mch, int(ref_is_prob), int(want_edges), int(want_kl),
+                    _ptr(cw), _stream()), "consistency_cw_fwd")
             _lib.check(lib.advchain_consistency_finish(_ptr(slots), _lib.float_array(coef), _ptr(sums), _ptr(value), 1,
                                                        _stream()), "consistency_finish")
         except BaseException:
@@ -1666,6 +1697,7 @@ class _Consistency(torch.autograd.Function):
             ctx.save_for_backward(pred, ref, R, mask, stats)
         ctx.ref_grad = need_ref and not (ref_is_prob and coef[0] == 0.0 and not (want_edges and K > 1))
         ctx.lp = True
+        ctx.cw = cw                 # (a constant of the cache, not an autograd input)
         ctx.cfg = (coef, mch, int(ref_is_prob))
         ctx.mark_non_differentiable(sums)
         ctx.set_materialize_grads(False)
@@ -1680,25 +1712,29 @@ class _Consistency(torch.autograd.Function):
         pred, ref, R, mask, stats = ctx.saved_tensors
         N, K = pred.shape[:2]
         gpred = gref = None
-        for need, entry, name in ((need_pred, lib.advchain_consistency_lp_bwd, "consistency_lp_bwd"),
-                                  (need_ref, lib.advchain_consistency_lp_ref_bwd, "consistency_lp_ref_bwd")):
+        cw = ctx.cw
+        family = "lp" if cw is None else "cw"
+        weights = () if cw is None else (_ptr(cw),)         # (the cw entries: class_w in front of the stream)
+        for need, side in ((need_pred, "bwd"), (need_ref, "ref_bwd")):
             if not need:
                 continue
-            out = torch.empty_like(pred if name == "consistency_lp_bwd" else ref)     # (the operand's dtype)
-            _lib.check(entry(_ptr(pred), int(pred.dtype == torch.bfloat16), _ptr(ref), int(ref.dtype == torch.bfloat16),
-                             _ptr(stats), _ptr(R), _ptr(mask), _ptr(gs), _ptr(out), float(coef[0]), float(coef[1]),
-                             float(coef[2]), float(coef[3]), is_gt, N, K, pred.dim() - 2, _lib.dims_array(pred.shape[2:]), mch,
-                             _stream()), name)
-            if name == "consistency_lp_bwd":
+            name = "consistency_%s_%s" % (family, side)
+            out = torch.empty_like(pred if side == "bwd" else ref)     # (the operand's dtype)
+            _lib.check(getattr(lib, "advchain_" + name)(
+                _ptr(pred), int(pred.dtype == torch.bfloat16), _ptr(ref), int(ref.dtype == torch.bfloat16),
+                _ptr(stats), _ptr(R), _ptr(mask), _ptr(gs), _ptr(out), float(coef[0]), float(coef[1]),
+                float(coef[2]), float(coef[3]), is_gt, N, K, pred.dim() - 2, _lib.dims_array(pred.shape[2:]), mch,
+                *(weights + (_stream(),))), name)
+            if side == "bwd":
                 gpred = out
             else:
                 gref = out
-        return gpred, gref, None, None, None, None
+        return gpred, gref, None, None, None, None, None
 
     @staticmethod
     def backward(ctx, gloss, _gsums):
         if gloss is None:
-            return None, None, None, None, None, None
+            return None, None, None, None, None, None, None
         if getattr(ctx, "lp", False):
             return _Consistency._backward_lp(ctx, gloss)
         coef, mch, is_gt = ctx.cfg
@@ -1735,17 +1771,20 @@ class _Consistency(torch.autograd.Function):
                 _ptr(pred), _ptr(ref), _ptr(stats), _ptr(R), _ptr(mask), _ptr(gs), _ptr(gref),
                 float(coef[0]), float(coef[1]), float(coef[2]), float(coef[3]), is_gt, N, K, ref.dim() - 2,
                 _lib.dims_array(ref.shape[2:]), mch, _stream()), "consistency_ref_bwd")
-        return gpred, gref, None, None, None, None
+        return gpred, gref, None, None, None, None, None
 
 
 @_on_tensor_device
-def consistency_sums(pred, ref, mask, coef, ref_is_prob=False, want_edges=True):
+def consistency_sums(pred, ref, mask, coef, ref_is_prob=False, want_edges=True, class_w=None):
     """Returns (coef . sums, sums) with sums = [S_mse, S_edgeA, S_edgeB, S_kl] (device tensor, raw sums); `coef` has 3
-    (no 'kl' term) or 4 entries."""
+    (no 'kl' term) or 4 entries.  class_w: K finite, non-negative host numbers used as given inside the sums (S_mse and S_kl:
+    w_k per class; the edge energies: w_i per object class, w_0 unused), or None for the unweighted loss."""
     coef = tuple(float(c) for c in coef)
     if len(coef) == 3:
         coef = coef + (0.0,)
-    return _Consistency.apply(pred, ref, mask, coef, bool(ref_is_prob), bool(want_edges))
+    if class_w is not None:
+        class_w = tuple(float(w) for w in class_w)
+    return _Consistency.apply(pred, ref, mask, coef, bool(ref_is_prob), bool(want_edges), class_w)
 
 
 # ---- supervised segmentation losses (csrc/seg_loss.hip) ---------------------------------------------------------------

@@ -501,6 +501,27 @@ int advchain_consistency_lp_ref_bwd(const void* pred, int pred_bf16, const void*
                                     float c_mse, float c_a, float c_b, float c_kl, int ref_is_prob, int64_t N, int64_t K,
                                     int ndim, const int64_t* dims, int mask_channels, void* stream);
 
+/* class weights (round 11, loss_lp.hip): the lp entries with K finite, non-negative weights w_k in device memory (class_w, K
+ * floats, not NULL; read by the kernels, so they must stay unchanged until the launches have run), used as given:
+ *   S_mse = sum w_k (m_k D_k)^2,  S_kl = sum w_k m_k T'_k (log T'_k - log P_k),  edge energies of object class i times w_i
+ * (w_0 does not enter 'contour'); every normaliser is the caller's, in the coefficients, as before.  w = 1 is the loss of the
+ * lp entries.  The same kernels instantiated with a trailing weight argument: all four storage pairs (fp32-fp32 included), every
+ * K, 2D and 3D, the layouts, limits, rounding and reproducibility of the lp entries; stats and R as cw_fwd wrote them (R is
+ * saved unweighted, the backward entries scale the probability-space gradient of class k by w_k); finish with
+ * advchain_consistency_finish.  The weights are constants: no gradient. */
+int advchain_consistency_cw_fwd(const void* pred, int pred_bf16, const void* ref, int ref_bf16, const float* mask, float* stats,
+                                float* R /*nullable*/, float* sums, int64_t N, int64_t K, int ndim, const int64_t* dims,
+                                int mask_channels, int ref_is_prob, int want_edges, int want_kl, const float* class_w,
+                                void* stream);
+int advchain_consistency_cw_bwd(const void* pred, int pred_bf16, const void* ref, int ref_bf16, const float* stats,
+                                const float* R /*nullable*/, const float* mask, const float* grad_scale, void* grad_pred,
+                                float c_mse, float c_a, float c_b, float c_kl, int ref_is_prob, int64_t N, int64_t K, int ndim,
+                                const int64_t* dims, int mask_channels, const float* class_w, void* stream);
+int advchain_consistency_cw_ref_bwd(const void* pred, int pred_bf16, const void* ref, int ref_bf16, const float* stats,
+                                    const float* R /*nullable*/, const float* mask, const float* grad_scale, void* grad_ref,
+                                    float c_mse, float c_a, float c_b, float c_kl, int ref_is_prob, int64_t N, int64_t K,
+                                    int ndim, const int64_t* dims, int mask_channels, const float* class_w, void* stream);
+
 /* bf16 STORAGE experiment (round 6; BASELINE config 2 names "bf16"): the 2D K = 4 fused loss above (common/loss.py:8-87,
  * 102-220: mse + contour terms on logits) with pred / ref / R / grad_pred stored as bfloat16 (raw 16-bit words, 8-byte aligned)
  * and all arithmetic in fp32 registers.  NOT used by the product path -- the parity contract is fp32 at 1e-4; the entries exist

@@ -1,0 +1,65 @@
+"""Do the kernels of one source compile to the same instructions in two builds?
+
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Iinclude -Iadvchain_amd/csrc --cuda-device-only -S \\
+          advchain_amd/csrc/loss_lp.hip -o new.s          (and the same in a checkout of the other commit: old.s)
+    python tools/isa_same.py old.s new.s [--match k_lp_]
+
+Kernels are paired by their demangled names (c++filt), so a template that gained a trailing, empty parameter pack pairs with
+its earlier self.  Compared: every instruction line with its operands, in order, and the local labels (renumbered per
+function); comments and assembler directives are dropped.  Prints one line per kernel of `old.s` and exits 1 on a kernel
+that differs or has no partner.  Needs no GPU."""
+import argparse
+import re
+import subprocess
+import sys
+
+
+def functions(path):
+    out, name, body = {}, None, []
+    for line in open(path):
+        m = re.match(r"^(_Z\w+):", line)
+        if m:
+            name, body = m.group(1), []
+            continue
+        if name is None:
+            continue
+        if line.startswith(".Lfunc_end"):
+            out[name] = body
+            name = None
+            continue
+        text = line.split(";")[0].rstrip()
+        if not text.strip() or (text.strip().startswith(".") and not text.startswith(".LBB")):
+            continue
+        body.append(re.sub(r"\.LBB\d+_", ".LBB_", text))
+    return out
+
+
+def demangled(names):
+    res = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True)
+    return dict(zip(names, res.stdout.splitlines()))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("old")
+    ap.add_argument("new")
+    ap.add_argument("--match", default="k_lp_", help="substring of the demangled names to compare")
+    args = ap.parse_args()
+    old, new = functions(args.old), functions(args.new)
+    old_names = demangled(list(old))
+    by_name = {d: n for n, d in demangled(list(new)).items()}
+    bad = total = 0
+    for o, d in sorted(old_names.items(), key=lambda kv: kv[1]):
+        if args.match not in d:
+            continue
+        total += 1
+        n = by_name.get(d)
+        verdict = "no partner" if n is None else ("same" if old[o] == new[n] else "DIFFERENT")
+        bad += verdict != "same"
+        print("%-10s %5d instructions  %s" % (verdict, len(old[o]), d[:120]))
+    print("%d kernels compared, %d not the same" % (total, bad))
+    sys.exit(1 if bad or not total else 0)
+
+
+if __name__ == "__main__":
+    main()
