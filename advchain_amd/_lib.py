@@ -22,12 +22,15 @@ PROTOTYPES = {
     "advchain_grid_sample_fwd_ride": (_I, [_P, _P, _P, _P, _P, _L, _L, _I, _P, _P, _I, _I, _I, _I, _P]),
     "advchain_scatter_workspace": (_L, [_L, _I, _P]),
     "advchain_grid_sample_bwd": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _P, _I, _I, _I, _I, _P]),
+    "advchain_det_warp_workspace": (_L, [_L, _L, _I, _P]),
+    "advchain_grid_sample_bwd_det": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _P, _I, _I, _I, _P]),
     "advchain_compose_self_fwd": (_I, [_P, _P, _P, _L, _I, _P, _I, _P, _P]),
     "advchain_compose_self_bwd": (_I, [_P, _P, _P, _P, _I, _I, _L, _I, _P, _P]),
     "advchain_affine_warp_fwd": (_I, [_P, _P, _P, _L, _L, _I, _P, _I, _I, _P]),
     "advchain_affine_warp_fwd_ride": (_I, [_P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _I, _I, _P]),
     "advchain_affine_warp_bwd_workspace": (_L, [_L, _I, _P]),
     "advchain_affine_warp_bwd": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _I, _P]),
+    "advchain_affine_warp_bwd_det": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _I, _P]),
     "advchain_affine_theta_fwd": (_I, [_P, _P, _F, _P, _P, _L, _I, _P]),
     "advchain_affine_theta_bwd": (_I, [_P, _P, _F, _P, _P, _P, _L, _I, _P]),
     "advchain_tp_interp_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _F, _P, _P, _P]),

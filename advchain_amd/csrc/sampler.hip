@@ -17,6 +17,7 @@
 #include <stdlib.h>
 #include "sampler_common.h"
 #include "affine_geo.h"
+#include "det_fix.h"
 
 namespace advchain {
 
@@ -115,10 +116,15 @@ k_grid_sample_fwd(const float* __restrict__ in, const float* __restrict__ grid, 
   }
 }
 
-template <int DIM, int INTERP, int PAD, int VEC, bool NEED_GIN, bool NEED_GGRID>
+// DET (a trailing pack, empty or one DetImage): empty -- grad_in deposits are float atomics into `gin`; with a DetImage
+// (deterministic mode, advchain_grid_sample_bwd_det) they are 64-bit fixed point into the int64 image it names and `gin` is
+// not touched (k_det_convert writes it afterwards).  Everything else -- taps, grad_grid -- is the same code either way.
+template <int DIM, int INTERP, int PAD, int VEC, bool NEED_GIN, bool NEED_GGRID, class... DET>
 __global__ void __launch_bounds__(kBlock)
 k_grid_sample_bwd(const float* __restrict__ gout, const float* __restrict__ in, const float* __restrict__ grid,
-                  float* __restrict__ gin, float* __restrict__ ggrid, int C, Dims id, Dims od, int clamp_grid) {
+                  float* __restrict__ gin, float* __restrict__ ggrid, int C, Dims id, Dims od, int clamp_grid, DET... det) {
+  const auto dep = make_deposit(det...);
+  typedef typename decltype(dep)::cell_t cell_t;
   const int64_t IV = id.voxels(), OV = od.voxels();
   const int n = blockIdx.y;
   const int64_t v = (int64_t)blockIdx.x * (kBlock * VEC) + threadIdx.x;
@@ -130,7 +136,7 @@ k_grid_sample_bwd(const float* __restrict__ gout, const float* __restrict__ in, 
   load_str<VEC>(g + OV, na, gy);
   if (DIM == 3) load_str<VEC>(g + 2 * OV, na, gz);
   const float* inn = in + (int64_t)n * C * IV;
-  float* ginn = NEED_GIN ? gin + (int64_t)n * C * IV : nullptr;
+  cell_t* ginn = NEED_GIN ? deposit_base(gin, det...) + (int64_t)n * C * IV : nullptr;
   const float* gon = gout + (int64_t)n * C * OV + v;
   if (INTERP == INTERP_LINEAR) {
     Taps<DIM, PAD> t[VEC];
@@ -154,7 +160,7 @@ k_grid_sample_bwd(const float* __restrict__ gout, const float* __restrict__ in, 
 #pragma unroll
       for (int k = 0; k < VEC; ++k)
         sample_linear_bwd<DIM, PAD, NEED_GIN, NEED_GGRID>(inn + (int64_t)c * IV, NEED_GIN ? ginn + (int64_t)c * IV : nullptr,
-                                                          go[k], t[k], id, ax[k], ay[k], az[k]);
+                                                          go[k], t[k], id, ax[k], ay[k], az[k], dep);
     }
     if (NEED_GGRID) {
       float* gg = ggrid + (int64_t)n * DIM * OV + v;
@@ -181,7 +187,7 @@ k_grid_sample_bwd(const float* __restrict__ gout, const float* __restrict__ in, 
       const int iz = DIM == 3 ? nearest_index<PAD>(gz[k], id.s0, vz) : 0;
       if (NEED_GIN && k < na && vx && vy && vz) {
         const int off = (iz * id.s1 + iy) * id.s2 + ix;
-        for (int c = 0; c < C; ++c) atomic_add_f32(ginn + (int64_t)c * IV + off, gon[(int64_t)c * OV + k * kBlock]);
+        for (int c = 0; c < C; ++c) dep.add(ginn + (int64_t)c * IV + off, gon[(int64_t)c * OV + k * kBlock]);
       }
     }
     if (NEED_GGRID) {  // nearest has zero gradient w.r.t. the grid (ATen does the same)
@@ -513,11 +519,15 @@ k_affine_warp_fwd_v(const float* __restrict__ in, const float* __restrict__ thet
 }
 
 // gtheta_partial: (N, gridDim.x, DIM*(DIM+1)) block partial sums, reduced by k_reduce_partials.
-template <int DIM, int INTERP, int PAD, bool NEED_GIN, bool NEED_GTHETA>
+// DET: as for k_grid_sample_bwd (advchain_affine_warp_bwd_det launches it with mode == nullptr: every sample is scattered).
+template <int DIM, int INTERP, int PAD, bool NEED_GIN, bool NEED_GTHETA, class... DET>
 __global__ void __launch_bounds__(kBlock)
 k_affine_warp_bwd(const float* __restrict__ gout, const float* __restrict__ in, const float* __restrict__ theta,
                   float* __restrict__ gin, float* __restrict__ gtheta_partial, int C, Dims d,
-                  const int* __restrict__ mode, const float* __restrict__ red_partial, float* __restrict__ red_out, int red_nb) {
+                  const int* __restrict__ mode, const float* __restrict__ red_partial, float* __restrict__ red_out, int red_nb,
+                  DET... det) {
+  const auto dep = make_deposit(det...);
+  typedef typename decltype(dep)::cell_t cell_t;
   constexpr int NT = DIM * (DIM + 1);
   __shared__ float smem[4 * NT];
   const int64_t V = d.voxels();
@@ -548,7 +558,7 @@ k_affine_warp_bwd(const float* __restrict__ gout, const float* __restrict__ in, 
     float bx, by, bz, gx, gy, gz;
     affine_position<DIM>(th, v, d, bx, by, bz, gx, gy, gz);
     const float* inn = in + (int64_t)n * C * V;
-    float* ginn = NEED_GIN ? gin + (int64_t)n * C * V : nullptr;
+    cell_t* ginn = NEED_GIN ? deposit_base(gin, det...) + (int64_t)n * C * V : nullptr;
     const float* gon = gout + (int64_t)n * C * V + v;
     if (INTERP == INTERP_LINEAR) {
       Taps<DIM, PAD> t;
@@ -556,7 +566,7 @@ k_affine_warp_bwd(const float* __restrict__ gout, const float* __restrict__ in, 
       float ax = 0.f, ay = 0.f, az = 0.f;
       for (int c = 0; c < C; ++c) {
         if (do_gin) sample_linear_bwd<DIM, PAD, NEED_GIN, NEED_GTHETA>(inn + (int64_t)c * V, NEED_GIN ? ginn + (int64_t)c * V : nullptr,
-                                                                       gon[(int64_t)c * V], t, d, ax, ay, az);
+                                                                       gon[(int64_t)c * V], t, d, ax, ay, az, dep);
         else sample_linear_bwd<DIM, PAD, false, NEED_GTHETA>(inn + (int64_t)c * V, nullptr, gon[(int64_t)c * V], t, d, ax, ay, az);
       }
       if (NEED_GTHETA) {
@@ -576,7 +586,7 @@ k_affine_warp_bwd(const float* __restrict__ gout, const float* __restrict__ in, 
       const int iz = DIM == 3 ? nearest_index<PAD>(gz, d.s0, vz) : 0;
       if (vx && vy && vz) {
         const int off = (iz * d.s1 + iy) * d.s2 + ix;
-        for (int c = 0; c < C; ++c) atomic_add_f32(ginn + (int64_t)c * V + off, gon[(int64_t)c * V]);
+        for (int c = 0; c < C; ++c) dep.add(ginn + (int64_t)c * V + off, gon[(int64_t)c * V]);
       }
     }
   }
@@ -852,6 +862,49 @@ static int launch_grid_sample_bwd(const float* gout, const float* in, const floa
   return ADVCHAIN_OK;
 }
 
+template <int DIM, int INTERP, int PAD, int VEC>
+static void launch_gs_bwd_det_flags(dim3 g, dim3 b, hipStream_t st, const float* gout, const float* in, const float* grid,
+                                    unsigned long long* acc, float* ggrid, const float* maxn, int bits, int C, Dims id, Dims od,
+                                    int clamp_grid) {
+  const DetImage im{acc, maxn, bits};
+  float* const gin = nullptr;   // the det instantiations do not touch grad_in: k_det_convert writes it
+  if (ggrid) hipLaunchKernelGGL((k_grid_sample_bwd<DIM, INTERP, PAD, VEC, true, true, DetImage>), g, b, 0, st, gout, in, grid, gin, ggrid, C, id, od, clamp_grid, im);
+  else hipLaunchKernelGGL((k_grid_sample_bwd<DIM, INTERP, PAD, VEC, true, false, DetImage>), g, b, 0, st, gout, in, grid, gin, ggrid, C, id, od, clamp_grid, im);
+}
+
+// the launch geometry of launch_grid_sample_bwd: the grad_grid arithmetic of a thread is the same code on the same samples
+template <int DIM>
+static int launch_grid_sample_bwd_det(const float* gout, const float* in, const float* grid, unsigned long long* acc,
+                                      float* ggrid, const float* maxn, int bits, int64_t N, int64_t C, Dims id, Dims od,
+                                      int interp, int padding, int clamp_grid, hipStream_t st) {
+  const int64_t OV = od.voxels();
+  const bool vec4 = use_unroll(OV, DIM);
+  const int vec = vec4 ? 4 : 1;
+  dim3 g(advchain_blocks(OV, kBlock * vec), (unsigned)N), b(kBlock);
+  DISPATCH_PAD(padding, {
+    if (interp == INTERP_LINEAR) {
+      if (vec4) launch_gs_bwd_det_flags<DIM, INTERP_LINEAR, PAD, 4>(g, b, st, gout, in, grid, acc, ggrid, maxn, bits, (int)C, id, od, clamp_grid);
+      else launch_gs_bwd_det_flags<DIM, INTERP_LINEAR, PAD, 1>(g, b, st, gout, in, grid, acc, ggrid, maxn, bits, (int)C, id, od, clamp_grid);
+    } else {
+      if (vec4) launch_gs_bwd_det_flags<DIM, INTERP_NEAREST, PAD, 4>(g, b, st, gout, in, grid, acc, ggrid, maxn, bits, (int)C, id, od, clamp_grid);
+      else launch_gs_bwd_det_flags<DIM, INTERP_NEAREST, PAD, 1>(g, b, st, gout, in, grid, acc, ggrid, maxn, bits, (int)C, id, od, clamp_grid);
+    }
+  });
+  ADVCHAIN_LAUNCH_CHECK();
+  return ADVCHAIN_OK;
+}
+
+// Width of the fixed point of the int64 images of the deterministic warps: the tap weights of one output sample sum to at most
+// 1, so a cell of a channel receives at most OV * max |grad_out| -- OV * 2^bits stays below 2^63 (one bit spare for the
+// roundings).  kDetBits up to 2^22 output voxels per sample.
+static inline int det_warp_bits(int64_t out_voxels) {
+  int lg = 0;
+  while (((int64_t)1 << lg) < out_voxels) ++lg;
+  return 62 - lg < kDetBits ? 62 - lg : kDetBits;
+}
+// the workspace of the deterministic warps: [int64 image: N x C x V][max |grad_out| per entry: N, padded to 4]
+static inline int64_t det_warp_image_ints(int64_t N, int64_t C, int64_t V) { return 2 * N * C * V; }
+
 // min_voxels = 2 for a tensor that is GATHERED from (the paired corner gathers read two neighbouring elements:
 // sampler_common.h); the output side of a resampling warp may be a single voxel
 static inline bool dims_ok(int ndim, const int64_t* s, int64_t min_voxels = 2) {
@@ -970,6 +1023,46 @@ int advchain_grid_sample_bwd(const float* grad_out, const float* in, const float
   if (workspace && grad_in) advchain_zero_async(grad_in, sizeof(float) * N * C * id.voxels(), (hipStream_t)stream);
   return ndim == 3 ? launch_grid_sample_bwd<3>(grad_out, in, grid, grad_in, grad_grid, N, C, id, od, interp, padding, clamp_grid, (hipStream_t)stream)
                    : launch_grid_sample_bwd<2>(grad_out, in, grid, grad_in, grad_grid, N, C, id, od, interp, padding, clamp_grid, (hipStream_t)stream);
+}
+
+int64_t advchain_det_warp_workspace(int64_t N, int64_t C, int ndim, const int64_t* in_dims) {
+  if (!in_dims || !dims_ok(ndim, in_dims, 1) || N < 0 || C < 1) return -1;
+  return det_warp_image_ints(N, C, make_dims(ndim, in_dims).voxels()) + ((N + 3) & ~(int64_t)3);
+}
+
+// advchain_grid_sample_bwd's general kernel with grad_in accumulated in 64-bit fixed point: clear, maxima, scatter, convert.
+// Works whatever advchain_get_deterministic() says.
+int advchain_grid_sample_bwd_det(const float* grad_out, const float* in, const float* grid, float* grad_in,
+                                 float* grad_grid, int32_t* det_ws, int64_t N, int64_t C, int ndim,
+                                 const int64_t* in_dims, const int64_t* out_dims, int interp, int padding, int clamp_grid,
+                                 void* stream) {
+  ADVCHAIN_CHECK_ARG(grad_out && in && grid, "grid_sample_bwd_det: null pointer");
+  ADVCHAIN_CHECK_ARG(grad_in || grad_grid, "grid_sample_bwd_det: nothing to compute");
+  ADVCHAIN_CHECK_ARG(!grad_in || det_ws, "grid_sample_bwd_det: det_ws required for grad_in (advchain_det_warp_workspace int32 elements)");
+  ADVCHAIN_CHECK_ARG(in_dims && out_dims && dims_ok(ndim, in_dims) && dims_ok(ndim, out_dims, 1), "grid_sample_bwd_det: bad dims");
+  ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && C >= 1, "grid_sample_bwd_det: bad N/C");
+  ADVCHAIN_CHECK_ARG(interp == INTERP_LINEAR || interp == INTERP_NEAREST, "grid_sample_bwd_det: interp");
+  ADVCHAIN_CHECK_ARG(padding >= 0 && padding <= 2, "grid_sample_bwd_det: padding");
+  if (N == 0) return ADVCHAIN_OK;
+  const Dims id = make_dims(ndim, in_dims), od = make_dims(ndim, out_dims);
+  ADVCHAIN_CHECK_ARG(id.voxels() < (1ll << 31) && od.voxels() < (1ll << 31), "grid_sample_bwd_det: per-sample volume too large");
+  hipStream_t st = (hipStream_t)stream;
+  clamp_grid &= 1;
+  if (!grad_in)   // grad_grid alone needs no atomics: the default kernel
+    return ndim == 3 ? launch_grid_sample_bwd<3>(grad_out, in, grid, nullptr, grad_grid, N, C, id, od, interp, padding, clamp_grid, st)
+                     : launch_grid_sample_bwd<2>(grad_out, in, grid, nullptr, grad_grid, N, C, id, od, interp, padding, clamp_grid, st);
+  const int64_t image = det_warp_image_ints(N, C, id.voxels());
+  unsigned long long* acc = reinterpret_cast<unsigned long long*>(det_ws);
+  float* maxn = reinterpret_cast<float*>(det_ws + image);
+  const int bits = det_warp_bits(od.voxels());
+  advchain_zero_async(det_ws, sizeof(int32_t) * (image + N), st);     // image and maxima in one launch (they are neighbours)
+  advchain_det_absmax_launch(grad_out, maxn, N, C * od.voxels(), st);
+  const int rc = ndim == 3 ? launch_grid_sample_bwd_det<3>(grad_out, in, grid, acc, grad_grid, maxn, bits, N, C, id, od, interp, padding, clamp_grid, st)
+                           : launch_grid_sample_bwd_det<2>(grad_out, in, grid, acc, grad_grid, maxn, bits, N, C, id, od, interp, padding, clamp_grid, st);
+  if (rc != ADVCHAIN_OK) return rc;
+  advchain_det_convert_launch(acc, maxn, grad_in, N, C * id.voxels(), bits, st);
+  ADVCHAIN_LAUNCH_CHECK();
+  return ADVCHAIN_OK;
 }
 
 int advchain_compose_self_fwd(const float* phi, float* out, const float* phi0, int64_t N, int ndim,
@@ -1385,6 +1478,74 @@ int advchain_affine_warp_bwd(const float* grad_out, const float* in, const float
       ADVCHAIN_LAUNCH_CHECK();
     }
   }
+  return ADVCHAIN_OK;
+}
+
+// advchain_affine_warp_bwd's scatter of every sample (what it does for C > 8, nearest, or non-zeros padding) with grad_in
+// accumulated in 64-bit fixed point; grad_theta: the block partials of that scatter's own launch and the same second stage.
+// Works whatever advchain_get_deterministic() says.
+int advchain_affine_warp_bwd_det(const float* grad_out, const float* in, const float* theta, float* grad_in,
+                                 float* grad_theta, float* workspace, int32_t* det_ws, int64_t N, int64_t C, int ndim,
+                                 const int64_t* dims, int interp, int padding, void* stream) {
+  ADVCHAIN_CHECK_ARG(grad_out && in && theta, "affine_warp_bwd_det: null pointer");
+  ADVCHAIN_CHECK_ARG(grad_in || grad_theta, "affine_warp_bwd_det: nothing to compute");
+  ADVCHAIN_CHECK_ARG(workspace, "affine_warp_bwd_det: workspace required (advchain_affine_warp_bwd_workspace floats)");
+  ADVCHAIN_CHECK_ARG(!grad_in || det_ws, "affine_warp_bwd_det: det_ws required for grad_in (advchain_det_warp_workspace int32 elements)");
+  ADVCHAIN_CHECK_ARG(dims && dims_ok(ndim, dims), "affine_warp_bwd_det: bad dims");
+  ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && C >= 1, "affine_warp_bwd_det: bad N/C");
+  ADVCHAIN_CHECK_ARG(interp == INTERP_LINEAR || interp == INTERP_NEAREST, "affine_warp_bwd_det: interp");
+  ADVCHAIN_CHECK_ARG(padding >= 0 && padding <= 2, "affine_warp_bwd_det: padding");
+  if (N == 0) return ADVCHAIN_OK;
+  if (!grad_in)   // grad_theta alone needs no atomics
+    return advchain_affine_warp_bwd(grad_out, in, theta, nullptr, grad_theta, workspace, N, C, ndim, dims, interp, padding, stream);
+  const Dims d = make_dims(ndim, dims);
+  ADVCHAIN_CHECK_ARG(d.voxels() < (1ll << 31), "affine_warp_bwd_det: per-sample volume too large");
+  const int nb = affine_grid_blocks(d);
+  dim3 g(nb, (unsigned)N), b(kBlock);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t image = det_warp_image_ints(N, C, d.voxels());
+  unsigned long long* acc = reinterpret_cast<unsigned long long*>(det_ws);
+  float* maxn = reinterpret_cast<float*>(det_ws + image);
+  const int bits = det_warp_bits(d.voxels());
+  advchain_zero_async(det_ws, sizeof(int32_t) * (image + N), st);
+  advchain_det_absmax_launch(grad_out, maxn, N, C * d.voxels(), st);
+  // grad_theta must be the default mode's bit for bit, and it is not when the twin computes it: the compiler packs and
+  // contracts the position and tap arithmetic of the DetImage instantiation differently from the float-atomic one (seen in
+  // 3D: last-bit differences in the partials).  So the partials come from the code that computes them in the default mode --
+  // the float-atomic launch of advchain_affine_warp_bwd for these shapes, run for its partials alone: its deposits land in
+  // grad_in, which the conversion pass overwrites below.
+  if (grad_theta && interp == INTERP_LINEAR) {
+    advchain_zero_async(grad_in, sizeof(float) * N * C * d.voxels(), st);
+    DISPATCH_PAD(padding, {
+      if (ndim == 3) launch_affine_bwd<3, INTERP_LINEAR, PAD>(g, b, st, grad_out, in, theta, grad_in, workspace, (int)C, d, nullptr);
+      else launch_affine_bwd<2, INTERP_LINEAR, PAD>(g, b, st, grad_out, in, theta, grad_in, workspace, (int)C, d, nullptr);
+    });
+    ADVCHAIN_LAUNCH_CHECK();
+  }
+  const DetImage im{acc, maxn, bits};
+  float* const no_gin = nullptr;      // the det instantiations do not touch grad_in: k_det_convert writes it
+  float* const no_gpart = nullptr;
+  const int* const no_mode = nullptr; // every sample is scattered
+  const float* const no_red = nullptr;
+#define GO(DIM_, INTERP_) hipLaunchKernelGGL((k_affine_warp_bwd<DIM_, INTERP_, PAD, true, false, DetImage>), g, b, 0, st, grad_out, in, theta, no_gin, no_gpart, (int)C, d, no_mode, no_red, no_gin, 0, im)
+  DISPATCH_PAD(padding, {
+    if (ndim == 3) {
+      if (interp == INTERP_NEAREST) GO(3, INTERP_NEAREST);
+      else GO(3, INTERP_LINEAR);
+    } else {
+      if (interp == INTERP_NEAREST) GO(2, INTERP_NEAREST);
+      else GO(2, INTERP_LINEAR);
+    }
+  });
+#undef GO
+  ADVCHAIN_LAUNCH_CHECK();
+  advchain_det_convert_launch(acc, maxn, grad_in, N, C * d.voxels(), bits, st);
+  if (grad_theta) {
+    const int K = ndim * (ndim + 1);
+    if (interp == INTERP_NEAREST) advchain_zero_async(grad_theta, sizeof(float) * N * K, st);   // nearest: zero gradient w.r.t. theta
+    else hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)N, K), dim3(kBlock), 0, st, workspace, grad_theta, nb, K);
+  }
+  ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
 }
 

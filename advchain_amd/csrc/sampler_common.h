@@ -119,11 +119,40 @@ __device__ __forceinline__ float sample_linear(const float* __restrict__ in, con
   return acc;
 }
 
+// How a grad_in deposit reaches global memory: the deposit policy of sample_linear_bwd and of the kernels built on it.
+// DepositFloat: a float atomic into grad_in itself -- the sum depends on the order of arrival in its last bits.
+// DepositFix64 (deterministic mode, det_fix.h): a 64-bit integer atomic of the deposit in fixed point, scaled by the batch
+// entry's max |grad_out|, into an int64 image of grad_in that a last pass converts -- integer adds commute, so the bits do
+// not depend on the order.  Consecutive lanes own consecutive samples, so under a near-identity warp one wave-instruction
+// adds into one contiguous row segment (512 B of int64 cells; float atomics run at full rate with 256 contiguous bytes,
+// the rate of the 64-bit integer form is not known).
+struct DepositFloat {
+  typedef float cell_t;
+  __device__ __forceinline__ void add(float* p, float v) const { atomic_add_f32(p, v); }
+};
+struct DepositFix64 {
+  typedef unsigned long long cell_t;
+  FixScale s;
+  __device__ __forceinline__ void add(unsigned long long* p, float v) const {
+    atomicAdd(p, (unsigned long long)__float2ll_rn(fix_in(v * s.mul, s)));
+  }
+};
+// What a kernel with a trailing `DET...` pack is launched with for the second policy: the int64 image (N, C, in_dims), the
+// maxima per batch entry and the width of the fixed point.  An empty pack selects DepositFloat -- and leaves the kernel's
+// name, parameters and instructions what they were before the pack.
+struct DetImage { unsigned long long* acc; const float* maxn; int bits; };
+__device__ __forceinline__ DepositFloat make_deposit() { return DepositFloat(); }
+__device__ __forceinline__ DepositFix64 make_deposit(const DetImage& im) {   // (batch entry = blockIdx.y in these kernels)
+  return DepositFix64{fix_scale(im.maxn[blockIdx.y], im.bits)};
+}
+__device__ __forceinline__ float* deposit_base(float* gin) { return gin; }
+__device__ __forceinline__ unsigned long long* deposit_base(float*, const DetImage& im) { return im.acc; }
+
 // scatter go*w into gin and accumulate d(out)/d(unnormalised coordinate) * go into (ax, ay, az)
-template <int DIM, int PAD, bool NEED_GIN, bool NEED_GGRID>
-__device__ __forceinline__ void sample_linear_bwd(const float* __restrict__ in, float* __restrict__ gin, float go,
+template <int DIM, int PAD, bool NEED_GIN, bool NEED_GGRID, class DEP = DepositFloat>
+__device__ __forceinline__ void sample_linear_bwd(const float* __restrict__ in, typename DEP::cell_t* __restrict__ gin, float go,
                                                   const Taps<DIM, PAD>& t, const Dims& d, float& ax, float& ay,
-                                                  float& az) {
+                                                  float& az, DEP dep = DEP()) {
   float v[8];
   if (NEED_GGRID) {   // corner values first, unconditionally (see CornerOffsets)
     const CornerOffsets<DIM, PAD> o(t, d);
@@ -137,7 +166,7 @@ __device__ __forceinline__ void sample_linear_bwd(const float* __restrict__ in, 
       for (int cx = 0; cx < 2; ++cx) {
         const bool ok = t.ok(cz, cy, cx);
         if (NEED_GIN) {
-          if (ok) atomic_add_f32(gin + t.off(cz, cy, cx, d), t.w(cz, cy, cx) * go);
+          if (ok) dep.add(gin + t.off(cz, cy, cx, d), t.w(cz, cy, cx) * go);
         }
         if (NEED_GGRID) {
           // a select on the value, no branch: the loads of the next channel / sample must not wait behind control flow

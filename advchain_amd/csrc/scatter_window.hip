@@ -16,6 +16,7 @@
 // the price is a zero-filled destination and float-atomic (order-dependent, ~1e-7 relative) accumulation across tiles.
 #include <stdlib.h>
 #include "sampler_common.h"
+#include "det_fix.h"   // kDetBits, det_scale, k_det_absmax, k_det_convert
 
 namespace advchain {
 
@@ -26,66 +27,12 @@ namespace advchain {
 // to run.  The scale comes from a max |grad_out| per batch entry (k_det_absmax; a NaN / inf there turns the entry's
 // outputs into NaN) -- per entry, so that a sample's result does not depend on what else is in the batch.  Resolution
 // 2^-40 of that maximum per addition; 2^22 additions of the maximum itself fit below 2^63.
-constexpr int kDetBits = 40;   // (fix_scale)
 template <bool DET>
 __device__ __forceinline__ void win_global_add(float* __restrict__ gin, unsigned long long* __restrict__ acc, int64_t idx,
                                                float v, const FixScale& sdet) {
   if (DET) atomicAdd(acc + idx, (unsigned long long)__float2ll_rn(fix_in(v * sdet.mul, sdet)));
   else atomic_add_f32(gin + idx, v);
 }
-__device__ __forceinline__ FixScale det_scale(const float* __restrict__ maxn, int n) { return fix_scale(maxn[n], kDetBits); }
-
-// max |x| per batch entry (over `per_n` floats) -> maxn[n] (zeroed by the caller); non-finite -> +inf
-__global__ void __launch_bounds__(kBlock) k_det_absmax(const float* __restrict__ x, float* __restrict__ maxn, int64_t per_n) {
-  const int n = blockIdx.y;
-  const float* p = x + (int64_t)n * per_n;
-  float m = 0.f;
-  bool bad = false;
-  const int64_t stride = (int64_t)gridDim.x * kBlock * 4;
-  for (int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * 4; i < per_n; i += stride) {
-    float v[4];
-    if (i + 4 <= per_n && ((uintptr_t)(p + i) & 15) == 0) {
-      const float4 q = *reinterpret_cast<const float4*>(p + i);
-      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = i + j < per_n ? p[i + j] : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { m = fmaxf(m, fabsf(v[j])); bad = bad || !(fabsf(v[j]) <= 3.0e38f); }
-  }
-  if (bad) m = __int_as_float(0x7f800000);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  __shared__ float wm[kBlock / 64];
-  if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 1; w < kBlock / 64; ++w) m = fmaxf(m, wm[w]);
-    atomicMax(reinterpret_cast<int*>(maxn) + n, __float_as_int(m));      // (non-negative floats order as their bit patterns)
-  }
-}
-
-// grad_in = int64 image * max / 2^40 (fix_out; a non-finite maximum: 0 * inf = NaN, as the owner-computes scatters do)
-__global__ void __launch_bounds__(kBlock) k_det_convert(const long long* __restrict__ acc, const float* __restrict__ maxn,
-                                                        float* __restrict__ gin, int64_t per_n) {
-  const int n = blockIdx.y;
-  const FixScale fs = det_scale(maxn, n);
-  const long long* a = acc + (int64_t)n * per_n;
-  float* g = gin + (int64_t)n * per_n;
-  const int64_t stride = (int64_t)gridDim.x * kBlock * 2;
-  for (int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * 2; i < per_n; i += stride) {
-    if (i + 2 <= per_n) {
-      const longlong2 q = *reinterpret_cast<const longlong2*>(a + i);
-      g[i] = fix_out((float)q.x, fs);
-      g[i + 1] = fix_out((float)q.y, fs);
-    } else {
-      g[i] = fix_out((float)a[i], fs);
-    }
-  }
-}
-
 // A/B build switch (tools/ab/build_all_variant.sh -DADVCHAIN_WINDOW_FLAT=0): the branch-light deposits of the 3D window scatter
 #ifndef ADVCHAIN_WINDOW_FLAT
 #define ADVCHAIN_WINDOW_FLAT 1

@@ -195,8 +195,10 @@ RIDE_INTERPS = ("bilinear", "trilinear", "linear", "nearest")
 
 
 def set_deterministic(on):
-    """Process-wide: route the one backward formulation whose bits depend on arrival order (the window scatter's float-atomic
-    flush) through its 64-bit fixed-point twin (include/advchain_hip.h: advchain_set_deterministic).  The solver sets it at
+    """Process-wide: route the backward formulations whose bits depend on arrival order -- the window scatter's float-atomic
+    flush, and the general float-atomic kernels that warps of more than four channels (affine: more than eight), nearest and
+    size-changing warps end in -- through their 64-bit fixed-point twins (include/advchain_hip.h: advchain_set_deterministic,
+    advchain_grid_sample_bwd_det, advchain_affine_warp_bwd_det).  The solver sets it at
     the start of every call from its `deterministic` attribute; two solvers with different settings in one process are fine as
     long as their calls do not interleave (a workspace is sized when it is allocated, for the mode of that moment)."""
     _lib.load().advchain_set_deterministic(1 if on else 0)
@@ -211,9 +213,30 @@ def _scatter_workspace(N, dims, device):
     return torch.empty(n, device=device, dtype=torch.int32)
 
 
+def _det_warp_workspace(N, C, dims, device):
+    n = _lib.load().advchain_det_warp_workspace(N, C, len(dims), _lib.dims_array(dims))
+    return torch.empty(max(1, n), device=device, dtype=torch.int32)
+
+
+def _general_warp_kernel(C, interp, in_dims, out_dims):
+    """True for the calls advchain_grid_sample_bwd sends to its general float-atomic kernel rather than to a C <= 4 route:
+    the negation of the condition `same && interp == INTERP_LINEAR && C <= 4` of advchain_grid_sample_bwd in
+    csrc/sampler.hip (keep the two in step).  Deterministic mode sends these to advchain_grid_sample_bwd_det."""
+    return C > 4 or interp != 0 or tuple(in_dims) != tuple(out_dims)
+
+
 def raw_grid_sample_bwd(gout, inp, grid, interp, padding, clamp_grid, need_gin, need_ggrid, halo=0):
     N, C = inp.shape[:2]
     nd = inp.dim() - 2
+    if need_gin and is_deterministic() and _general_warp_kernel(C, interp, inp.shape[2:], grid.shape[2:]):
+        ws = _det_warp_workspace(N, C, inp.shape[2:], inp.device)
+        gin = torch.empty_like(inp)
+        ggrid = torch.empty_like(grid) if need_ggrid else None
+        _lib.check(_lib.load().advchain_grid_sample_bwd_det(_ptr(gout), _ptr(inp), _ptr(grid), _ptr(gin), _ptr(ggrid), _ptr(ws),
+                                                            N, C, nd, _lib.dims_array(inp.shape[2:]),
+                                                            _lib.dims_array(grid.shape[2:]), interp, padding, int(clamp_grid),
+                                                            _stream()), "grid_sample_bwd_det")
+        return gin, ggrid
     tiled = TILED_SCATTER and need_gin
     ws = _scatter_workspace(N, inp.shape[2:], inp.device) if tiled else None
     gin = (torch.empty_like(inp) if tiled else torch.zeros_like(inp)) if need_gin else None
@@ -1062,6 +1085,15 @@ class _AffineWarp(torch.autograd.Function):
         gth = torch.empty_like(theta) if need_th else None
         ws = torch.empty(max(1, lib.advchain_affine_warp_bwd_workspace(N, nd, dims)), device=inp.device,
                          dtype=torch.float32)
+        # Deterministic mode: the calls advchain_affine_warp_bwd answers by zeroing grad_in and scattering every sample with
+        # float atomics take the fixed-point twin.  C <= 8 with linear / zeros keeps its atomic-free gather (C <= 4: the box
+        # tiles); the samples that gather flags as degenerate keep today's scatter -- the remainder the mode does not cover.
+        if need_in and is_deterministic() and (C > 8 or (C > 4 and (interp != 0 or padding != 0))):
+            dws = _det_warp_workspace(N, C, inp.shape[2:], inp.device)
+            _lib.check(lib.advchain_affine_warp_bwd_det(_ptr(_dev(gout, "grad")), _ptr(inp), _ptr(theta), _ptr(gin), _ptr(gth),
+                                                        _ptr(ws), _ptr(dws), N, C, nd, dims, interp, padding, _stream()),
+                       "affine_warp_bwd_det")
+            return gin, gth, None, None, None, None
         _lib.check(lib.advchain_affine_warp_bwd(_ptr(_dev(gout, "grad")), _ptr(inp), _ptr(theta), _ptr(gin), _ptr(gth),
                                                 _ptr(ws), N, C, nd, dims, interp, padding, _stream()), "affine_warp_bwd")
         return gin, gth, None, None, None, None

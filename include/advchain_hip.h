@@ -46,16 +46,21 @@ const char* advchain_last_error(void);
  * replaces: nothing the reference writes down -- its CPU path (the parity target) is deterministic by construction, and
  *           on a GPU it inherits torch.use_deterministic_algorithms(), under which grid_sampler_{2,3}d_backward
  *           (reached from adv_morph.py:546-557 through autograd) raises for want of a deterministic kernel.  Here the one
- *           formulation whose bits depend on arrival order -- the source-tiled window scatter (2D image warps above
- *           16 px, squarings above 32 px; 3D above 4 voxels), which flushes its LDS windows with float atomics -- gets a
- *           bit-reproducible twin: the tiles add 64-bit fixed point (2^40 / max|grad_out| of the batch entry) into an
- *           int64 image of grad_in inside the caller's workspace and one more pass converts it.  Every other backward
- *           formulation (gather forms, owner-computes scatters, affine tiles) is deterministic already.
+ *           formulation of the C <= 4 routes whose bits depend on arrival order -- the source-tiled window scatter (2D
+ *           image warps above 16 px, squarings above 32 px; 3D above 4 voxels), which flushes its LDS windows with float
+ *           atomics -- gets a bit-reproducible twin: the tiles add 64-bit fixed point (2^40 / max|grad_out| of the batch
+ *           entry) into an int64 image of grad_in inside the caller's workspace and one more pass converts it.  The
+ *           general float-atomic kernels (warps of more than four channels, nearest, size-changing; the affine scatter
+ *           of more than eight channels) have twins of the same kind as entries of their own --
+ *           advchain_grid_sample_bwd_det, advchain_affine_warp_bwd_det -- which the Python layer calls when the switch
+ *           is on.  Every other backward formulation (gather forms, owner-computes scatters, affine tiles) is
+ *           deterministic already.
  * PROCESS-WIDE switch, read when a backward entry is called and by advchain_scatter_workspace (which then returns the larger
  * size: allocate workspaces AFTER setting the mode; a workspace sized in the other mode must not be reused).  Not covered
  * (still float atomics): the overflow list of the LDS-tiled scatter (reflection padding, 3-channel image warps, calls without
- * a displacement bound), nearest-neighbour / size-changing backward, the bicubic backward, affine samples flagged as
- * degenerate, and the VALUE of the consistency loss / of the 3D step-count norm (partial sums arrive in any order; nothing
+ * a displacement bound), nearest-neighbour / size-changing backward THROUGH advchain_grid_sample_bwd ITSELF (call
+ * advchain_grid_sample_bwd_det), the bicubic backward, affine samples flagged as degenerate by the gather form (C <= 8), and
+ * the VALUE of the consistency loss / of the 3D step-count norm (partial sums arrive in any order; nothing
  * downstream of them but the number itself depends on the order).                                                       */
 void advchain_set_deterministic(int on);
 int advchain_get_deterministic(void);
@@ -101,6 +106,22 @@ int advchain_grid_sample_bwd(const float* grad_out, const float* in, const float
                              float* grad_grid, int32_t* workspace, int64_t N, int64_t C, int ndim,
                              const int64_t* in_dims, const int64_t* out_dims, int interp, int padding, int clamp_grid,
                              int halo, void* stream);
+/* Deterministic twin of the GENERAL kernel of the call above (the one it uses for C > 4, nearest interpolation or
+ * in_dims != out_dims: any C >= 1, 2D / 3D, linear / nearest, every padding, clamp_grid bit 0).
+ * replaces: the same grid_sampler_{2,3}d_backward, as torch.use_deterministic_algorithms() would want it (it raises instead).
+ * grad_in is accumulated with 64-bit integer atomics as fixed point, 2^bits / max|grad_out| of the batch entry with
+ * bits = min(40, 62 - ceil(log2(out voxels per sample))), in an int64 image inside `det_ws`
+ * (int32[advchain_det_warp_workspace(N, C, ndim, in_dims)]: 2 N C V for the image + N maxima padded to a multiple of 4;
+ * 8-byte aligned; host-only size query, independent of the switch), and one more pass converts it: equal bits run to run,
+ * quantum max|grad_out| / 2^bits per deposit; a NaN / inf in an entry's grad_out turns that entry's grad_in into NaN.
+ * grad_in is overwritten (no pre-zeroing); grad_grid is bit for bit what advchain_grid_sample_bwd's general kernel writes.
+ * Works whatever advchain_get_deterministic() says -- the switch is consulted by the Python layer, not here.  Four launches
+ * (clear, maxima, scatter, convert), all kernels.                                                                    */
+int64_t advchain_det_warp_workspace(int64_t N, int64_t C, int ndim, const int64_t* in_dims); /* int32 elements */
+int advchain_grid_sample_bwd_det(const float* grad_out, const float* in, const float* grid, float* grad_in,
+                                 float* grad_grid, int32_t* det_ws, int64_t N, int64_t C, int ndim,
+                                 const int64_t* in_dims, const int64_t* out_dims, int interp, int padding, int clamp_grid,
+                                 void* stream);
 
 /* ---- scaling-and-squaring step ---------------------------------------------------------
  * replaces: applyComposition{2,3}D(phi, phi) = F.grid_sample(phi, phi^T, 'border',
@@ -223,6 +244,15 @@ int64_t advchain_affine_warp_bwd_workspace(int64_t N, int ndim, const int64_t* d
 int advchain_affine_warp_bwd(const float* grad_out, const float* in, const float* theta, float* grad_in,
                              float* grad_theta, float* workspace, int64_t N, int64_t C, int ndim,
                              const int64_t* dims, int interp, int padding, void* stream);
+/* Deterministic twin of the scatter the call above falls back to (C > 8, nearest, or non-zeros padding): every sample's
+ * grad_in deposits go through the int64 image of advchain_grid_sample_bwd_det (`det_ws`:
+ * int32[advchain_det_warp_workspace(N, C, ndim, dims)], required when grad_in is asked for); grad_theta keeps the block
+ * partials and the fixed-order second stage of that scatter and comes out bit for bit as from it.  Any C >= 1; for the
+ * shapes the call above serves without atomics (C <= 8, linear, zeros) it is correct but slower and its grad_theta is
+ * the scatter kernel's, not the box kernel's.  `workspace` as above.  Independent of the process-wide switch.          */
+int advchain_affine_warp_bwd_det(const float* grad_out, const float* in, const float* theta, float* grad_in,
+                                 float* grad_theta, float* workspace, int32_t* det_ws, int64_t N, int64_t C, int ndim,
+                                 const int64_t* dims, int interp, int padding, void* stream);
 
 /* ---- bicubic sampling (2D) ----------------------------------------------------------------
  * replaces: F.grid_sample(data, grid, mode='bicubic', padding_mode, align_corners=True), reached through the

@@ -3,7 +3,7 @@ has K > 4 channels?  The K-channel prediction and the validity mask ride through
 through the general-C kernels (k_grid_sample_fwd/bwd, k_affine_warp_fwd/bwd of csrc/sampler.hip: the fast formulations are
 gated on C <= 4, and the backward's grad_in is a float-atomic scatter).
 
-    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o k20 -- python tools/many_class_solver_trace.py [--classes 20]
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o k20 -- python tools/many_class_solver_trace.py [--classes 20] [--deterministic]
     python tools/many_class_solver_trace.py --summarize DIR/.../k20_kernel_stats.csv --ms-per-call MS [--out FILE]
 
 Needs a GPU (no fall-back)."""
@@ -18,6 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 GROUPS = (("general-C warps (C = K)", ("k_grid_sample_fwd", "k_grid_sample_bwd", "k_affine_warp_fwd", "k_affine_warp_bwd")),
+          ("passes around the int64 image (deterministic mode)", ("k_det_absmax", "k_det_convert", "k_det_convert_bits")),
           ("wide loss", ("k_wide_stats", "k_wide_edge", "k_wide_bwd", "k_consistency_finish")))
 
 
@@ -31,7 +32,7 @@ def run(args):
     names = ["noise", "bias", "morph", "affine"] if len(dims) == 2 else ["bias", "morph", "affine"]
     cls = {"noise": AdvNoise, "bias": AdvBias, "morph": AdvMorph, "affine": AdvAffine}
     chain = [cls[nm](spatial_dims=len(dims), config_dict=cfg, device=dev) for nm, cfg in bench.transform_configs(dims, args.batch, names)]
-    solver = ComposeAdversarialTransformSolver(chain_of_transforms=chain)
+    solver = ComposeAdversarialTransformSolver(chain_of_transforms=chain, deterministic=True if args.deterministic else None)
     conv = torch.nn.Conv2d if len(dims) == 2 else torch.nn.Conv3d
     torch.manual_seed(0)
     model = conv(1, args.classes, 3, 1, 1).to(dev).eval()
@@ -43,7 +44,7 @@ def run(args):
         loss = solver.adversarial_training(data=data, model=model, n_iter=args.n_iter, lazy_load=False, step_sizes=1)
     ev[1].record()
     torch.cuda.synchronize()
-    print(json.dumps(dict(classes=args.classes, batch=args.batch, dims=list(dims), n_iter=args.n_iter, calls=args.warmup + args.calls,
+    print(json.dumps(dict(classes=args.classes, deterministic=bool(args.deterministic), batch=args.batch, dims=list(dims), n_iter=args.n_iter, calls=args.warmup + args.calls,
                           ms_per_call=ev[0].elapsed_time(ev[1]) / args.calls, loss=float(loss))))
 
 
@@ -76,6 +77,7 @@ def main():
     ap.add_argument("--n-iter", type=int, default=1)
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--deterministic", action="store_true", help="deterministic=True: the fixed-point twins of the general-C warps")
     ap.add_argument("--summarize", metavar="STATS_CSV", default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("--traced-calls", type=int, default=7, help="--summarize: adversarial_training calls of the traced run")
