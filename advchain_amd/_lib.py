@@ -96,6 +96,20 @@ PROTOTYPES = {
     "advchain_jacobian_det2d_bwd": (_I, [_P, _P, _P, _L, _P, _P]),
     "advchain_expo_start": (_I, [_P, _P, _F, _L, _I, _P, _P]),
     "advchain_sumsq_ordered": (_I, [_P, _L, _P, _P, _P]),
+    "advchain_bicubic2d_det_workspace": (_L, [_L, _L, _P]),
+    "advchain_grid_sample_bicubic2d_bwd_det": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P]),
+    "advchain_tp_interp_sumsq_partials": (_L, [_P, _L]),
+    "advchain_tp_interp_sumsq_ordered": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _P, _P, _P]),
+    # (the *_fwd_ord lists: their family's with `partials, stride, counts` in place of `sums`)
+    "advchain_consistency_fwd_partials": (_L, [_L, _L, _I, _P, _I, _I, _I]),
+    "advchain_consistency_fwd_ord": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _L, _I, _P, _I, _I, _I, _I, _P]),
+    "advchain_consistency_fused_fwd_partials": (_L, [_L, _L, _I, _P, _I, _I, _I, _I]),
+    "advchain_consistency_fused_fwd_ord": (_I, [_P, _P, _P, _P, _P, _L, _P, _L, _L, _I, _P, _I, _I, _I, _I, _P]),
+    "advchain_consistency_wide_fwd_partials": (_L, [_L, _L, _I, _P, _I, _I]),
+    "advchain_consistency_wide_fwd_ord": (_I, [_P, _P, _P, _P, _P, _P, _L, _P, _L, _L, _I, _P, _I, _I, _I, _I, _P]),
+    "advchain_consistency_lp_fwd_partials": (_L, [_L, _L, _I, _P, _I]),
+    "advchain_consistency_lp_fwd_ord": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _L, _P, _L, _L, _I, _P, _I, _I, _I, _I, _P, _P]),
+    "advchain_consistency_finish_ord": (_I, [_P, _L, _P, _P, _P, _P, _P]),
 }
 
 class UpdateDesc(ctypes.Structure):

@@ -6,8 +6,11 @@
 //   advchain_grid_sample_bicubic2d_fwd / _bwd : dense planar grid (N, 2, H, W)
 //   advchain_affine_grid2d_fwd / _bwd         : theta (N, 2, 3) -> planar grid and its adjoint (F.affine_grid), so that an
 //                                               affine bicubic warp is the composition of the two
+//   advchain_grid_sample_bicubic2d_bwd_det    : the backward with grad_in through an int64 fixed-point image (deterministic
+//                                               mode; the passes of det_fix.h)
 #include <stdlib.h>
 #include "common.h"
+#include "det_fix.h"
 
 namespace advchain {
 
@@ -141,6 +144,52 @@ k_bicubic2d_bwd(const float* __restrict__ gout, const float* __restrict__ in, co
   }
 }
 
+// Deterministic twin of the grad_in half of k_bicubic2d_bwd: the same 16 deposits per sample and channel, as 64-bit fixed
+// point (2^bits / max|grad_out| of the batch entry) into the int64 image `acc` (N, C, H, W).  Integer additions commute, so
+// the image -- and the grad_in that k_bicubic_det_convert makes of it -- does not depend on arrival order.
+// Width: a deposit is go * cx * cy.  For A = -0.75 the weights are cubic1(t) = (1.25 t - 2.25) t^2 + 1 on [0, 1] (falls
+// from 1 to 0) and cubic2(x) = -0.75 (x - 1)(x - 2)^2 on [1, 2] (extreme -0.75 * 4/27 = -1/9 at x = 4/3), so |cx|, |cy| <= 1
+// and |deposit| <= max|grad_out| = 2^bits in fixed point.  Border and reflection padding fold several taps of one sample onto
+// one cell, at most all 16, so a cell receives at most 16 * OH * OW deposits: bits = min(40, 62 - ceil(log2(16 OH OW)))
+// keeps the sum below 2^62 (bicubic_det_bits; OH * OW < 2^30, so bits >= 28).
+template <int PAD>
+__global__ void __launch_bounds__(kBlock)
+k_bicubic2d_bwd_det(const float* __restrict__ gout, const float* __restrict__ grid, unsigned long long* __restrict__ acc,
+                    const float* __restrict__ maxn, int bits, int C, int H, int W, int OH, int OW) {
+  const int n = blockIdx.y;
+  const int o = blockIdx.x * kBlock + threadIdx.x;
+  const int OV = OH * OW, V = H * W;
+  if (o >= OV) return;
+  const FixScale fs = fix_scale(maxn[n], bits);
+  const float* gn = grid + (int64_t)n * 2 * OV;
+  const CubicTaps t = cubic_taps<PAD>(gn[o], gn[OV + o], W, H);
+  for (int c = 0; c < C; ++c) {
+    const float go = gout[((int64_t)n * C + c) * OV + o];
+    unsigned long long* q = acc + ((int64_t)n * C + c) * V;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const bool ok = t.xi[i] >= 0 && t.yi[j] >= 0;
+        const int off = max(t.yi[j], 0) * W + max(t.xi[i], 0);
+        if (ok) atomicAdd(q + off, (unsigned long long)__float2ll_rn(fix_in(go * t.cx[i] * t.cy[j] * fs.mul, fs)));
+      }
+  }
+}
+
+// grad_in = int64 image * max / 2^bits, like k_det_convert_bits but with 8-byte loads: with an odd C * H * W the image of the
+// second batch entry is only 8-byte aligned.
+__global__ void __launch_bounds__(kBlock)
+k_bicubic_det_convert(const long long* __restrict__ acc, const float* __restrict__ maxn, float* __restrict__ gin, int64_t per_n,
+                      int bits) {
+  const int n = blockIdx.y;
+  const FixScale fs = fix_scale(maxn[n], bits);
+  const long long* a = acc + (int64_t)n * per_n;
+  float* g = gin + (int64_t)n * per_n;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < per_n; i += stride) g[i] = fix_out((float)a[i], fs);
+}
+
 // F.affine_grid(theta, (N, C, H, W), align_corners=True), planar: grid[n][r][y][x] = th[r][0] bx + th[r][1] by + th[r][2]
 __global__ void __launch_bounds__(kBlock)
 k_affine_grid2d_fwd(const float* __restrict__ theta, float* __restrict__ grid, int H, int W) {
@@ -225,6 +274,53 @@ int advchain_grid_sample_bicubic2d_bwd(const float* grad_out, const float* in, c
   if (grad_in) advchain_zero_async(grad_in, sizeof(float) * N * C * H * W, st);
   dim3 g(advchain_blocks((int64_t)OH * OW, kBlock), (unsigned)N), b(kBlock);
   BICUBIC_PAD(padding, { hipLaunchKernelGGL(k_bicubic2d_bwd<PAD>, g, b, 0, st, grad_out, in, grid, grad_in, grad_grid, (int)C, H, W, OH, OW); });
+  ADVCHAIN_LAUNCH_CHECK();
+  return ADVCHAIN_OK;
+}
+
+static inline int bicubic_det_bits(int64_t out_pixels) {
+  int lg = 0;
+  while (((int64_t)1 << lg) < 16 * out_pixels) ++lg;
+  return 62 - lg < kDetBits ? 62 - lg : kDetBits;
+}
+// [int64 image: N x C x H x W][max |grad_out| per entry: N, padded to 4], in int32 elements
+static inline int64_t bicubic_det_image_ints(int64_t N, int64_t C, int64_t V) { return 2 * N * C * V; }
+
+int64_t advchain_bicubic2d_det_workspace(int64_t N, int64_t C, const int64_t* in_dims) {
+  if (!bdims_ok(in_dims) || N < 0 || C < 1) return -1;
+  return bicubic_det_image_ints(N, C, in_dims[0] * in_dims[1]) + ((N + 3) & ~(int64_t)3);
+}
+
+// Works whatever advchain_get_deterministic() says.  grad_grid comes from k_bicubic2d_bwd itself, launched without grad_in: the
+// same instructions as in the default mode, so the same bits.
+int advchain_grid_sample_bicubic2d_bwd_det(const float* grad_out, const float* in, const float* grid, float* grad_in,
+                                           float* grad_grid, int32_t* det_ws, int64_t N, int64_t C, const int64_t* in_dims,
+                                           const int64_t* out_dims, int padding, void* stream) {
+  ADVCHAIN_CHECK_ARG(grad_out && in && grid && (grad_in || grad_grid), "grid_sample_bicubic2d_bwd_det: null pointer");
+  ADVCHAIN_CHECK_ARG(!grad_in || det_ws, "grid_sample_bicubic2d_bwd_det: det_ws required for grad_in (advchain_bicubic2d_det_workspace int32 elements)");
+  ADVCHAIN_CHECK_ARG(bdims_ok(in_dims) && bdims_ok(out_dims), "grid_sample_bicubic2d_bwd_det: bad dims");
+  ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && C >= 1 && padding >= 0 && padding <= 2, "grid_sample_bicubic2d_bwd_det: bad N/C/padding");
+  if (N == 0) return ADVCHAIN_OK;
+  const int H = (int)in_dims[0], W = (int)in_dims[1], OH = (int)out_dims[0], OW = (int)out_dims[1];
+  hipStream_t st = (hipStream_t)stream;
+  dim3 g(advchain_blocks((int64_t)OH * OW, kBlock), (unsigned)N), b(kBlock);
+  if (grad_grid) {
+    float* const no_gin = nullptr;
+    BICUBIC_PAD(padding, { hipLaunchKernelGGL(k_bicubic2d_bwd<PAD>, g, b, 0, st, grad_out, in, grid, no_gin, grad_grid, (int)C, H, W, OH, OW); });
+    ADVCHAIN_LAUNCH_CHECK();
+  }
+  if (!grad_in) return ADVCHAIN_OK;
+  const int64_t V = (int64_t)H * W, image = bicubic_det_image_ints(N, C, V);
+  unsigned long long* acc = reinterpret_cast<unsigned long long*>(det_ws);
+  float* maxn = reinterpret_cast<float*>(det_ws + image);
+  const int bits = bicubic_det_bits((int64_t)OH * OW);
+  advchain_zero_async(det_ws, sizeof(int32_t) * (image + N), st);     // image and maxima in one launch (they are neighbours)
+  advchain_det_absmax_launch(grad_out, maxn, N, C * (int64_t)OH * OW, st);
+  BICUBIC_PAD(padding, { hipLaunchKernelGGL(k_bicubic2d_bwd_det<PAD>, g, b, 0, st, grad_out, grid, acc, maxn, bits, (int)C, H, W, OH, OW); });
+  int64_t nb = (C * V + kBlock * 4 - 1) / (kBlock * 4);
+  if (nb > 2048) nb = 2048;
+  hipLaunchKernelGGL(k_bicubic_det_convert, dim3((unsigned)nb, (unsigned)N), b, 0, st, reinterpret_cast<const long long*>(acc), maxn,
+                     grad_in, C * V, bits);
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
 }

@@ -180,9 +180,30 @@ __device__ __forceinline__ void tp_rows(const float* __restrict__ coef, const Ba
   }
 }
 
+// Where a workgroup's partial of the step-count norm goes.  An empty ORD pack (every default-mode launch): a float atomic
+// into one of the 64 slots, and the kernel's name, parameters and instructions are what they were before the pack.
+// ORD = SumsqOrdered (advchain_tp_interp_sumsq_ordered): `sumsq` holds one float per workgroup of the launch and every
+// workgroup stores its own, so that k_tp_partials_sum can add them in a fixed order.
+struct SumsqOrdered {};
+template <class... ORD>
+__device__ __forceinline__ void tp_sumsq_put(float* __restrict__ sumsq, float v) {
+  if constexpr (sizeof...(ORD) == 0)
+    atomic_add_f32(sumsq + (blockIdx.x + blockIdx.y * 3u + blockIdx.z * 7u) % kSumSlots, v);
+  else
+    sumsq[((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = v;
+}
+// one workgroup adds the partials in a fixed order (fixed stride, fixed tree): a deterministic function of the partials
+static __global__ void __launch_bounds__(kBlock) k_tp_partials_sum(const float* __restrict__ partials, int64_t nb, float* __restrict__ out) {
+  __shared__ float smem[4];
+  float v[1] = {0.f};
+  for (int64_t i = threadIdx.x; i < nb; i += kBlock) v[0] += partials[i];
+  block_sum<1>(v, smem);
+  if (threadIdx.x == 0) out[0] = v[0];
+}
+
 // out[plane][v] = (add_identity ? identity_coord(channel) : 0) + scale * interp ; optional sum of interp^2
-// (64 slot accumulators) for the 3D step-count rule.  grid = (i1 chunks, S0, planes).
-template <int VEC>
+// (64 slot accumulators, or one partial per workgroup: tp_sumsq_put) for the 3D step-count rule.  grid = (i1 chunks, S0, planes).
+template <int VEC, class... ORD>
 __global__ void __launch_bounds__(kBlock)
 k_tp_interp_fwd(const float* __restrict__ coef, float* __restrict__ out, BandTables T, Dims full, int C,
                 int add_identity, float scale, float* __restrict__ sumsq, float* __restrict__ disp_out) {
@@ -211,7 +232,7 @@ k_tp_interp_fwd(const float* __restrict__ coef, float* __restrict__ out, BandTab
   if (disp_out) wave_max_to_slots(fminf(dmax * to_vox, 1.0e9f), disp_out);   // displacement of base + scale * val, in voxels
   if (sumsq) {
     block_sum<1>(sq, smem);
-    if (threadIdx.x == 0) atomic_add_f32(sumsq + (blockIdx.x + blockIdx.y * 3u + blockIdx.z * 7u) % kSumSlots, sq[0]);
+    if (threadIdx.x == 0) tp_sumsq_put<ORD...>(sumsq, sq[0]);
   }
 }
 
@@ -283,7 +304,7 @@ k_tp_interp_fwd_gs(const float* __restrict__ vel, float* __restrict__ s1, float*
 // i0 are formed and blended after them, into the other half of a double LDS buffer: one barrier per plane, the coefficient
 // round trip under the stores.  Same sums in the same order as tp_rows: bit-identical.
 constexpr int kTpZB = 4;
-template <int VEC>
+template <int VEC, class... ORD>
 __global__ void __launch_bounds__(kBlock)
 k_tp_interp_fwd_planes(const float* __restrict__ coef, float* __restrict__ out, BandTables T, Dims full, int C, int add_identity,
                        float scale, float* __restrict__ sumsq, float* __restrict__ disp_out) {
@@ -405,7 +426,7 @@ k_tp_interp_fwd_planes(const float* __restrict__ coef, float* __restrict__ out, 
   if (disp_out) wave_max_to_slots(fminf(dmax * to_vox, 1.0e9f), disp_out);
   if (sumsq) {
     block_sum<1>(sq, smem);
-    if (threadIdx.x == 0) atomic_add_f32(sumsq + (blockIdx.x + blockIdx.y * 3u + blockIdx.z * 7u) % kSumSlots, sq[0]);
+    if (threadIdx.x == 0) tp_sumsq_put<ORD...>(sumsq, sq[0]);
   }
 }
 
@@ -1482,15 +1503,17 @@ static bool unpack_tables(const int32_t* itab, const float* ftab, const int64_t*
   return true;
 }
 
-extern "C" {
-
-int advchain_tp_interp_fwd(const float* coef, float* out, const int32_t* itab, const float* ftab, const int64_t* S,
-                           const int64_t* g, const int64_t* B, int64_t planes, int64_t C, int ndim, int add_identity,
-                           float scale, float* sumsq, float* disp_out, void* stream) {
+// advchain_tp_interp_fwd (ORD empty) and the first stage of advchain_tp_interp_sumsq_ordered (ORD = SumsqOrdered): the same
+// choice of kernel either way.  `nwg`: the number of workgroups launched.
+template <class... ORD>
+static int tp_interp_fwd_launch(const float* coef, float* out, const int32_t* itab, const float* ftab,
+                                const int64_t* S, const int64_t* g, const int64_t* B, int64_t planes, int64_t C, int add_identity,
+                                float scale, float* sumsq, float* disp_out, int64_t* nwg, void* stream) {
   ADVCHAIN_CHECK_ARG(coef && itab && ftab && (out || sumsq), "tp_interp_fwd: null pointer");
   ADVCHAIN_CHECK_ARG(planes >= 0 && planes < 65536 && C >= 1 && S[0] < 65536, "tp_interp_fwd: bad planes/C");
   BandTables T;
   ADVCHAIN_CHECK_ARG(unpack_tables(itab, ftab, S, g, B, T), "tp_interp_fwd: bad band tables");
+  *nwg = 0;
   if (planes == 0) return ADVCHAIN_OK;
   Dims full{(int)S[0], (int)S[1], (int)S[2]};
   ADVCHAIN_CHECK_ARG(full.voxels() < (1ll << 31), "tp_interp_fwd: volume too large");
@@ -1500,24 +1523,60 @@ int advchain_tp_interp_fwd(const float* coef, float* out, const int32_t* itab, c
   if (!no_planes && full.s0 >= 2 * kTpZB && T.a[0].B == 2 && T.a[1].B == 2 && T.a[2].B == 2 && kTpChunk * T.a[2].g <= kTpMaxLds) {
     // 3D linear upsampling: kTpZB planes per workgroup, pipelined
     dim3 gp(grid.x, (unsigned)((full.s0 + kTpZB - 1) / kTpZB), (unsigned)planes);
+    *nwg = (int64_t)gp.x * gp.y * gp.z;
     // 16 bytes per lane for long rows and for rows that do not fill whole waves one voxel per lane (cfg-5's rows of 80: 90
     // against 107 us); rows of exactly 64 time the same either way
     if (full.s2 % 4 == 0 && (full.s2 >= 128 || full.s2 % 64 != 0) && (reinterpret_cast<uintptr_t>(out) & 15) == 0)
-      hipLaunchKernelGGL(k_tp_interp_fwd_planes<4>, gp, dim3(kBlock), 0, (hipStream_t)stream, coef, out, T, full, (int)C, add_identity,
+      hipLaunchKernelGGL((k_tp_interp_fwd_planes<4, ORD...>), gp, dim3(kBlock), 0, (hipStream_t)stream, coef, out, T, full, (int)C, add_identity,
                          scale, sumsq, disp_out);
     else
-      hipLaunchKernelGGL(k_tp_interp_fwd_planes<1>, gp, dim3(kBlock), 0, (hipStream_t)stream, coef, out, T, full, (int)C, add_identity,
+      hipLaunchKernelGGL((k_tp_interp_fwd_planes<1, ORD...>), gp, dim3(kBlock), 0, (hipStream_t)stream, coef, out, T, full, (int)C, add_identity,
                          scale, sumsq, disp_out);
     ADVCHAIN_LAUNCH_CHECK();
     return ADVCHAIN_OK;
   }
+  *nwg = (int64_t)grid.x * grid.y * grid.z;
   // short rows (S2 < 128) leave a thread only two rows to amortise the bands of its 4 columns: measured slower (3D 53 -> 61 us)
   if (full.s2 % 4 == 0 && full.s2 >= 128 && (reinterpret_cast<uintptr_t>(out) & 15) == 0)
-    hipLaunchKernelGGL(k_tp_interp_fwd<4>, grid, dim3(kBlock), 0, (hipStream_t)stream, coef, out, T, full, (int)C,
+    hipLaunchKernelGGL((k_tp_interp_fwd<4, ORD...>), grid, dim3(kBlock), 0, (hipStream_t)stream, coef, out, T, full, (int)C,
                        add_identity, scale, sumsq, disp_out);
   else
-    hipLaunchKernelGGL(k_tp_interp_fwd<1>, grid, dim3(kBlock), 0, (hipStream_t)stream, coef, out, T, full, (int)C,
+    hipLaunchKernelGGL((k_tp_interp_fwd<1, ORD...>), grid, dim3(kBlock), 0, (hipStream_t)stream, coef, out, T, full, (int)C,
                        add_identity, scale, sumsq, disp_out);
+  ADVCHAIN_LAUNCH_CHECK();
+  return ADVCHAIN_OK;
+}
+
+extern "C" {
+
+int advchain_tp_interp_fwd(const float* coef, float* out, const int32_t* itab, const float* ftab, const int64_t* S,
+                           const int64_t* g, const int64_t* B, int64_t planes, int64_t C, int ndim, int add_identity,
+                           float scale, float* sumsq, float* disp_out, void* stream) {
+  (void)ndim;
+  int64_t nwg;
+  return tp_interp_fwd_launch<>(coef, out, itab, ftab, S, g, B, planes, C, add_identity, scale, sumsq, disp_out,
+                                &nwg, stream);
+}
+
+// The most workgroups a launch of advchain_tp_interp_fwd over a field of size S (3 entries, 2D: a leading 1) can have:
+// ceil(S[1] / 32) * S[0] * planes -- the floats `partials` of the call below must hold.  Host-only.
+int64_t advchain_tp_interp_sumsq_partials(const int64_t* S, int64_t planes) {
+  if (!S || planes < 0 || planes >= 65536 || S[0] < 1 || S[1] < 1 || S[2] < 1 || S[0] >= 65536) return -1;
+  return ((S[1] + kTpChunk - 1) / kTpChunk) * S[0] * planes;
+}
+
+// out[0] = sum of the squares of the interpolated field, which is not materialised: the kernel advchain_tp_interp_fwd picks
+// for (out = NULL, sumsq) with one partial per workgroup in `partials`, then one workgroup adds them in a fixed order -- the
+// value does not depend on arrival order.  Works whatever advchain_get_deterministic() says.
+int advchain_tp_interp_sumsq_ordered(const float* coef, const int32_t* itab, const float* ftab, const int64_t* S, const int64_t* g,
+                                     const int64_t* B, int64_t planes, int64_t C, float* partials, float* out, void* stream) {
+  ADVCHAIN_CHECK_ARG(partials && out, "tp_interp_sumsq_ordered: null pointer");
+  ADVCHAIN_CHECK_ARG(S && g && B, "tp_interp_sumsq_ordered: null dims");
+  int64_t nwg = 0;
+  const int rc = tp_interp_fwd_launch<SumsqOrdered>(coef, nullptr, itab, ftab, S, g, B, planes, C, 0,
+                                                    1.f, partials, nullptr, &nwg, stream);
+  if (rc != ADVCHAIN_OK) return rc;
+  hipLaunchKernelGGL(k_tp_partials_sum, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, partials, nwg, out);   // (nwg == 0: out = 0)
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
 }

@@ -17,16 +17,18 @@
 // The caller owns the normalisers (global N under batch sharding).
 // Streaming + 3^d stencil: HBM-bound, no MFMA.
 #include <stdlib.h>
+#include <algorithm>
 #include "loss_common.h"
 
 namespace advchain {
 
 constexpr int kMaxK = 16;
 
+template <class... ORD>
 __global__ void __launch_bounds__(kBlock)
 k_softmax_diff(const float* __restrict__ pred, const float* __restrict__ ref, const float* __restrict__ mask,
                float* __restrict__ P, float* __restrict__ D, float* __restrict__ sums, int K, int V, int mask_ch,
-               int ref_is_prob, int want_kl) {
+               int ref_is_prob, int want_kl, ORD... ord) {
   __shared__ float smem[8];
   const int n = blockIdx.y;
   const int v = blockIdx.x * kBlock + threadIdx.x;
@@ -61,19 +63,19 @@ k_softmax_diff(const float* __restrict__ pred, const float* __restrict__ ref, co
   }
   block_sum<2>(acc, smem);
   if (threadIdx.x == 0) {
-    atomic_add_f32(sums + sum_slot(), acc[0]);
-    if (want_kl) atomic_add_f32(sums + 3 * kSumSlots + sum_slot(), acc[1]);
+    sums_put(sums, 0, acc[0], ord...);
+    if (want_kl) sums_put(sums, 3, acc[1], ord...);
   }
 }
 
 // K known at compile time, V % 4 == 0: 4 voxels per thread with 16-byte loads and stores, every input read once
 // (the generic kernel above re-reads its 2K inputs three times with 4-byte loads: 36 vector-memory instructions per
 // voxel-wave at K = 4, against 4.25 here -- these streaming kernels are bound by that count).
-template <int K>
+template <int K, class... ORD>
 __global__ void __launch_bounds__(kBlock)
 k_softmax_diff_v4(const float* __restrict__ pred, const float* __restrict__ ref, const float* __restrict__ mask,
                   float* __restrict__ P, float* __restrict__ D, float* __restrict__ sums, int V, int mask_ch,
-                  int ref_is_prob, int want_kl) {
+                  int ref_is_prob, int want_kl, ORD... ord) {
   __shared__ float smem[8];
   const int n = blockIdx.y;
   const int v = (blockIdx.x * kBlock + threadIdx.x) * 4;
@@ -126,15 +128,15 @@ k_softmax_diff_v4(const float* __restrict__ pred, const float* __restrict__ ref,
   }
   block_sum<2>(acc, smem);
   if (threadIdx.x == 0) {
-    atomic_add_f32(sums + sum_slot(), acc[0]);
-    if (want_kl) atomic_add_f32(sums + 3 * kSumSlots + sum_slot(), acc[1]);
+    sums_put(sums, 0, acc[0], ord...);
+    if (want_kl) sums_put(sums, 3, acc[1], ord...);
   }
 }
 
-template <int DIM>
+template <int DIM, class... ORD>
 __global__ void __launch_bounds__(kBlock)
 k_edge_fwd(const float* __restrict__ D, const float* __restrict__ mask, float* __restrict__ R,
-           float* __restrict__ sums, int K, Dims d, int mask_ch) {
+           float* __restrict__ sums, int K, Dims d, int mask_ch, ORD... ord) {
   __shared__ float smem[8];
   const int n = blockIdx.y;
   const int V = (int)d.voxels();
@@ -178,8 +180,8 @@ k_edge_fwd(const float* __restrict__ D, const float* __restrict__ mask, float* _
   }
   block_sum<2>(acc, smem);
   if (threadIdx.x == 0) {
-    atomic_add_f32(sums + kSumSlots + sum_slot(), acc[0]);
-    atomic_add_f32(sums + 2 * kSumSlots + sum_slot(), acc[1]);
+    sums_put(sums, 1, acc[0], ord...);
+    sums_put(sums, 2, acc[1], ord...);
   }
 }
 
@@ -269,10 +271,10 @@ __device__ __forceinline__ RowTaps load_row_taps(const float* __restrict__ p, in
   return t;
 }
 
-template <int DIM>
+template <int DIM, class... ORD>
 __global__ void __launch_bounds__(kBlock)
 k_edge_fwd_rows(const float* __restrict__ D, const float* __restrict__ mask, float* __restrict__ R,
-                float* __restrict__ sums, int K, Dims d, int mask_ch) {
+                float* __restrict__ sums, int K, Dims d, int mask_ch, ORD... ord) {
   __shared__ float smem[8];
   const int n = blockIdx.y;
   const int V = (int)d.voxels();
@@ -313,8 +315,8 @@ k_edge_fwd_rows(const float* __restrict__ D, const float* __restrict__ mask, flo
   }
   block_sum<2>(acc, smem);
   if (threadIdx.x == 0) {
-    atomic_add_f32(sums + kSumSlots + sum_slot(), acc[0]);
-    atomic_add_f32(sums + 2 * kSumSlots + sum_slot(), acc[1]);
+    sums_put(sums, 1, acc[0], ord...);
+    sums_put(sums, 2, acc[1], ord...);
   }
 }
 
@@ -411,10 +413,10 @@ __device__ __forceinline__ bool strip_decode(int strip, const Dims& d, int& i0, 
   return true;
 }
 
-template <int DIM, int K>
+template <int DIM, int K, class... ORD>
 __global__ void __launch_bounds__(kBlock)
 k_edge_fwd_march(const float* __restrict__ D, const float* __restrict__ mask, float* __restrict__ R,
-                 float* __restrict__ sums, Dims d, int mask_ch) {
+                 float* __restrict__ sums, Dims d, int mask_ch, ORD... ord) {
   __shared__ float smem[8];
   const int n = blockIdx.y;
   const int V = (int)d.voxels();
@@ -458,8 +460,8 @@ k_edge_fwd_march(const float* __restrict__ D, const float* __restrict__ mask, fl
   }
   block_sum<2>(acc, smem);
   if (threadIdx.x == 0) {
-    atomic_add_f32(sums + kSumSlots + sum_slot(), acc[0]);
-    atomic_add_f32(sums + 2 * kSumSlots + sum_slot(), acc[1]);
+    sums_put(sums, 1, acc[0], ord...);
+    sums_put(sums, 2, acc[1], ord...);
   }
 }
 
@@ -622,10 +624,10 @@ __device__ __forceinline__ void strip_decode4(const Dims& d, int mlen, int& i0, 
   last = xq == lpr - 1;
 }
 
-template <int DIM, int K>
+template <int DIM, int K, class... ORD>
 __global__ void __launch_bounds__(kBlock)
 k_edge_fwd_march4(const float* __restrict__ D, const float* __restrict__ mask, float* __restrict__ R,
-                  float* __restrict__ sums, Dims d, int mask_ch, int mlen) {
+                  float* __restrict__ sums, Dims d, int mask_ch, int mlen, ORD... ord) {
   __shared__ float smem[8];
   const int n = blockIdx.y;
   const int V = (int)d.voxels();
@@ -678,8 +680,8 @@ k_edge_fwd_march4(const float* __restrict__ D, const float* __restrict__ mask, f
   }
   block_sum<2>(acc, smem);
   if (threadIdx.x == 0) {
-    atomic_add_f32(sums + kSumSlots + sum_slot(), acc[0]);
-    atomic_add_f32(sums + 2 * kSumSlots + sum_slot(), acc[1]);
+    sums_put(sums, 1, acc[0], ord...);
+    sums_put(sums, 2, acc[1], ord...);
   }
 }
 
@@ -834,10 +836,10 @@ __device__ __forceinline__ void softmax_pair4(const ST* __restrict__ pred, const
   softmax_quads<K, LOGS>(p, r, ref_is_prob, P, T, lq, lt);
 }
 
-template <int DIM, int K, bool KL, bool EDGES, typename ST = float>
+template <int DIM, int K, bool KL, bool EDGES, typename ST = float, class... ORD>
 __global__ void __launch_bounds__(kBlock)
 k_loss_fused_fwd4(const ST* __restrict__ pred, const ST* __restrict__ ref, const float* __restrict__ mask,
-                  ST* __restrict__ R, float* __restrict__ sums, Dims d, int mlen, int ref_is_prob) {
+                  ST* __restrict__ R, float* __restrict__ sums, Dims d, int mlen, int ref_is_prob, ORD... ord) {
   __shared__ float smem[16];
   const int n = blockIdx.y;
   const int V = (int)d.voxels();
@@ -940,12 +942,12 @@ k_loss_fused_fwd4(const ST* __restrict__ pred, const ST* __restrict__ ref, const
   }
   block_sum<4>(acc, smem);
   if (threadIdx.x == 0) {
-    atomic_add_f32(sums + sum_slot(), acc[0]);
+    sums_put(sums, 0, acc[0], ord...);
     if (EDGES) {
-      atomic_add_f32(sums + kSumSlots + sum_slot(), acc[1]);
-      atomic_add_f32(sums + 2 * kSumSlots + sum_slot(), acc[2]);
+      sums_put(sums, 1, acc[1], ord...);
+      sums_put(sums, 2, acc[2], ord...);
     }
-    if (KL) atomic_add_f32(sums + 3 * kSumSlots + sum_slot(), acc[3]);
+    if (KL) sums_put(sums, 3, acc[3], ord...);
   }
 }
 
@@ -1092,10 +1094,10 @@ __device__ __forceinline__ void xfold4(const float (&c)[4], bool first, bool las
   }
 }
 
-template <int K, bool KL>
+template <int K, bool KL, class... ORD>
 __global__ void __launch_bounds__(kZ3Waves * 64) __attribute__((amdgpu_waves_per_eu(3)))
 k_loss_fused_fwd3d_z(const float* __restrict__ pred, const float* __restrict__ ref, const float* __restrict__ mask,
-                     float* __restrict__ R, float* __restrict__ sums, Dims d, int zc, int ref_is_prob) {
+                     float* __restrict__ R, float* __restrict__ sums, Dims d, int zc, int ref_is_prob, ORD... ord) {
   constexpr int CH = 2 * (K - 1);
   extern __shared__ float4 xch[];                 // [2][RW][CH][lpr]
   __shared__ float smem[16];
@@ -1211,10 +1213,10 @@ k_loss_fused_fwd3d_z(const float* __restrict__ pred, const float* __restrict__ r
   }
   block_sum<4>(acc, smem);
   if (threadIdx.x == 0) {
-    atomic_add_f32(sums + sum_slot(), acc[0]);
-    atomic_add_f32(sums + kSumSlots + sum_slot(), acc[1]);
-    atomic_add_f32(sums + 2 * kSumSlots + sum_slot(), acc[2]);
-    if (KL) atomic_add_f32(sums + 3 * kSumSlots + sum_slot(), acc[3]);
+    sums_put(sums, 0, acc[0], ord...);
+    sums_put(sums, 1, acc[1], ord...);
+    sums_put(sums, 2, acc[2], ord...);
+    if (KL) sums_put(sums, 3, acc[3], ord...);
   }
 }
 
@@ -1401,29 +1403,41 @@ static inline dim3 march4_grid(const Dims& d, int64_t N, int mlen) {
   return dim3((unsigned)((strips + per_block - 1) / per_block), (unsigned)N);
 }
 
-template <int DIM>
-static bool launch_edge_march(int64_t K, int64_t N, const Dims& d, hipStream_t st, const float* D, const float* mask,
-                              float* R, float* sums, int mask_ch, bool rows) {
+// The marching edge kernel of a three-kernel forward, if one takes the call: its grid, and which of the two it is.
+struct EdgeMarch { bool four; int mlen; dim3 grid; };
+static bool edge_march_plan(int64_t K, int64_t N, const Dims& d, const float* D, const float* mask, float* R, bool rows, EdgeMarch& m) {
   if (g_no_march) return false;
-  if (march4_ok(d, D, mask, R, nullptr)) {
-    const int mlen = march4_len(d, N);
-    const dim3 g4 = march4_grid(d, N, mlen), b4(kBlock);
+  if (march4_ok(d, D, mask, R, nullptr) && K >= 2 && K <= 5) {
+    m.four = true;
+    m.mlen = march4_len(d, N);
+    m.grid = march4_grid(d, N, m.mlen);
+    return true;
+  }
+  if (!rows || K < 2 || K > 5) return false;   // the scalar march needs whole waves per row (S2 % 64 == 0)
+  m.four = false;
+  m.mlen = 0;
+  m.grid = march_grid(d, N);
+  return true;
+}
+
+template <int DIM, class... ORD>
+static void launch_edge_march(const EdgeMarch& m, int64_t K, const Dims& d, hipStream_t st, const float* D, const float* mask,
+                              float* R, float* sums, int mask_ch, ORD... ord) {
+  const dim3 b(kBlock);
+  if (m.four) {
+    const int mlen = m.mlen;
     switch (K) {
-      case 2: hipLaunchKernelGGL((k_edge_fwd_march4<DIM, 2>), g4, b4, 0, st, D, mask, R, sums, d, mask_ch, mlen); return true;
-      case 3: hipLaunchKernelGGL((k_edge_fwd_march4<DIM, 3>), g4, b4, 0, st, D, mask, R, sums, d, mask_ch, mlen); return true;
-      case 4: hipLaunchKernelGGL((k_edge_fwd_march4<DIM, 4>), g4, b4, 0, st, D, mask, R, sums, d, mask_ch, mlen); return true;
-      case 5: hipLaunchKernelGGL((k_edge_fwd_march4<DIM, 5>), g4, b4, 0, st, D, mask, R, sums, d, mask_ch, mlen); return true;
-      default: break;
+      case 2: hipLaunchKernelGGL((k_edge_fwd_march4<DIM, 2, ORD...>), m.grid, b, 0, st, D, mask, R, sums, d, mask_ch, mlen, ord...); return;
+      case 3: hipLaunchKernelGGL((k_edge_fwd_march4<DIM, 3, ORD...>), m.grid, b, 0, st, D, mask, R, sums, d, mask_ch, mlen, ord...); return;
+      case 4: hipLaunchKernelGGL((k_edge_fwd_march4<DIM, 4, ORD...>), m.grid, b, 0, st, D, mask, R, sums, d, mask_ch, mlen, ord...); return;
+      default: hipLaunchKernelGGL((k_edge_fwd_march4<DIM, 5, ORD...>), m.grid, b, 0, st, D, mask, R, sums, d, mask_ch, mlen, ord...); return;
     }
   }
-  if (!rows) return false;   // the scalar march needs whole waves per row (S2 % 64 == 0)
-  const dim3 g = march_grid(d, N), b(kBlock);
   switch (K) {
-    case 2: hipLaunchKernelGGL((k_edge_fwd_march<DIM, 2>), g, b, 0, st, D, mask, R, sums, d, mask_ch); return true;
-    case 3: hipLaunchKernelGGL((k_edge_fwd_march<DIM, 3>), g, b, 0, st, D, mask, R, sums, d, mask_ch); return true;
-    case 4: hipLaunchKernelGGL((k_edge_fwd_march<DIM, 4>), g, b, 0, st, D, mask, R, sums, d, mask_ch); return true;
-    case 5: hipLaunchKernelGGL((k_edge_fwd_march<DIM, 5>), g, b, 0, st, D, mask, R, sums, d, mask_ch); return true;
-    default: return false;
+    case 2: hipLaunchKernelGGL((k_edge_fwd_march<DIM, 2, ORD...>), m.grid, b, 0, st, D, mask, R, sums, d, mask_ch, ord...); return;
+    case 3: hipLaunchKernelGGL((k_edge_fwd_march<DIM, 3, ORD...>), m.grid, b, 0, st, D, mask, R, sums, d, mask_ch, ord...); return;
+    case 4: hipLaunchKernelGGL((k_edge_fwd_march<DIM, 4, ORD...>), m.grid, b, 0, st, D, mask, R, sums, d, mask_ch, ord...); return;
+    default: hipLaunchKernelGGL((k_edge_fwd_march<DIM, 5, ORD...>), m.grid, b, 0, st, D, mask, R, sums, d, mask_ch, ord...); return;
   }
 }
 
@@ -1475,15 +1489,18 @@ static bool launch_bwd_march(int64_t K, int64_t N, const Dims& d, hipStream_t st
   }
 }
 
-extern "C" {
-
-int advchain_consistency_fwd(const float* pred, const float* ref, const float* mask, float* P, float* D, float* R,
-                             float* sums, int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels,
-                             int ref_is_prob, int want_edges, int want_kl, void* stream) {
+// advchain_consistency_fwd (ORD empty, oc == nullptr: sums = the 4 x 64 slots) and advchain_consistency_fwd_ord (one
+// SumsOrdered, sums = the [4][oc->stride] partials): the same choice of kernels either way.
+template <class... ORD>
+static int consistency_fwd(const OrdCounts* oc, const float* pred, const float* ref, const float* mask, float* P, float* D, float* R,
+                           float* sums, int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels,
+                           int ref_is_prob, int want_edges, int want_kl, void* stream, ORD... ord) {
   ADVCHAIN_CHECK_ARG(pred && ref && P && D && sums, "consistency_fwd: null pointer");
   ADVCHAIN_CHECK_ARG(ldims_ok(ndim, dims), "consistency_fwd: bad dims");
   ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && K >= 1 && K <= kMaxK, "consistency_fwd: bad N/K (K <= 16)");
   ADVCHAIN_CHECK_ARG(!mask || mask_channels == 1 || mask_channels == K, "consistency_fwd: mask must have 1 or K channels");
+  if (oc)
+    for (int r = 0; r < 4; ++r) oc->counts[r] = 0;
   if (N == 0) return ADVCHAIN_OK;
   const Dims d = lmake_dims(ndim, dims);
   ADVCHAIN_CHECK_ARG(d.voxels() < (1ll << 31), "consistency_fwd: volume too large");
@@ -1492,31 +1509,161 @@ int advchain_consistency_fwd(const float* pred, const float* ref, const float* m
   hipStream_t st = (hipStream_t)stream;
   const bool al16 = ((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(ref) | reinterpret_cast<uintptr_t>(mask) |
                       reinterpret_cast<uintptr_t>(P) | reinterpret_cast<uintptr_t>(D)) & 15) == 0;
-  if (V % 4 == 0 && al16 && K >= 2 && K <= 5) {
-    dim3 g4(advchain_blocks(V / 4, kBlock), (unsigned)N);
+  const bool v4 = V % 4 == 0 && al16 && K >= 2 && K <= 5;
+  const dim3 g4(advchain_blocks(V / 4, kBlock), (unsigned)N);
+  const bool edges = want_edges && K > 1;
+  const bool rows = (d.s2 % 64) == 0;   // lane <-> x with whole waves per row: DPP neighbour exchange
+  EdgeMarch em;
+  const bool march = edges && mask_channels <= 1 && edge_march_plan(K, N, d, D, mask, R, rows, em);
+  if (oc) {
+    const dim3 gs = v4 ? g4 : g, ge = march ? em.grid : g;
+    ADVCHAIN_CHECK_ARG(oc->fits(gs) && (!edges || oc->fits(ge)),
+                       "consistency_fwd_ord: the partial buffer is smaller than a launch (advchain_consistency_fwd_partials)");
+    oc->set(0, gs);
+    if (want_kl) oc->set(3, gs);
+    if (edges) { oc->set(1, ge); oc->set(2, ge); }
+  }
+  if (v4) {
     switch (K) {
-      case 2: hipLaunchKernelGGL(k_softmax_diff_v4<2>, g4, b, 0, st, pred, ref, mask, P, D, sums, V, mask_channels, ref_is_prob, want_kl); break;
-      case 3: hipLaunchKernelGGL(k_softmax_diff_v4<3>, g4, b, 0, st, pred, ref, mask, P, D, sums, V, mask_channels, ref_is_prob, want_kl); break;
-      case 4: hipLaunchKernelGGL(k_softmax_diff_v4<4>, g4, b, 0, st, pred, ref, mask, P, D, sums, V, mask_channels, ref_is_prob, want_kl); break;
-      default: hipLaunchKernelGGL(k_softmax_diff_v4<5>, g4, b, 0, st, pred, ref, mask, P, D, sums, V, mask_channels, ref_is_prob, want_kl); break;
+      case 2: hipLaunchKernelGGL((k_softmax_diff_v4<2, ORD...>), g4, b, 0, st, pred, ref, mask, P, D, sums, V, mask_channels, ref_is_prob, want_kl, ord...); break;
+      case 3: hipLaunchKernelGGL((k_softmax_diff_v4<3, ORD...>), g4, b, 0, st, pred, ref, mask, P, D, sums, V, mask_channels, ref_is_prob, want_kl, ord...); break;
+      case 4: hipLaunchKernelGGL((k_softmax_diff_v4<4, ORD...>), g4, b, 0, st, pred, ref, mask, P, D, sums, V, mask_channels, ref_is_prob, want_kl, ord...); break;
+      default: hipLaunchKernelGGL((k_softmax_diff_v4<5, ORD...>), g4, b, 0, st, pred, ref, mask, P, D, sums, V, mask_channels, ref_is_prob, want_kl, ord...); break;
     }
   } else {
-    hipLaunchKernelGGL(k_softmax_diff, g, b, 0, st, pred, ref, mask, P, D, sums, (int)K, V, mask_channels, ref_is_prob, want_kl);
+    hipLaunchKernelGGL((k_softmax_diff<ORD...>), g, b, 0, st, pred, ref, mask, P, D, sums, (int)K, V, mask_channels, ref_is_prob, want_kl, ord...);
   }
-  if (want_edges && K > 1) {
-    const bool rows = (d.s2 % 64) == 0;   // lane <-> x with whole waves per row: DPP neighbour exchange
+  if (edges) {
     if (ndim == 3) {
-      if (mask_channels <= 1 && launch_edge_march<3>(K, N, d, st, D, mask, R, sums, mask_channels, rows)) {}
-      else if (rows) hipLaunchKernelGGL(k_edge_fwd_rows<3>, g, b, 0, st, D, mask, R, sums, (int)K, d, mask_channels);
-      else hipLaunchKernelGGL(k_edge_fwd<3>, g, b, 0, st, D, mask, R, sums, (int)K, d, mask_channels);
+      if (march) launch_edge_march<3>(em, K, d, st, D, mask, R, sums, mask_channels, ord...);
+      else if (rows) hipLaunchKernelGGL((k_edge_fwd_rows<3, ORD...>), g, b, 0, st, D, mask, R, sums, (int)K, d, mask_channels, ord...);
+      else hipLaunchKernelGGL((k_edge_fwd<3, ORD...>), g, b, 0, st, D, mask, R, sums, (int)K, d, mask_channels, ord...);
     } else {
-      if (mask_channels <= 1 && launch_edge_march<2>(K, N, d, st, D, mask, R, sums, mask_channels, rows)) {}
-      else if (rows) hipLaunchKernelGGL(k_edge_fwd_rows<2>, g, b, 0, st, D, mask, R, sums, (int)K, d, mask_channels);
-      else hipLaunchKernelGGL(k_edge_fwd<2>, g, b, 0, st, D, mask, R, sums, (int)K, d, mask_channels);
+      if (march) launch_edge_march<2>(em, K, d, st, D, mask, R, sums, mask_channels, ord...);
+      else if (rows) hipLaunchKernelGGL((k_edge_fwd_rows<2, ORD...>), g, b, 0, st, D, mask, R, sums, (int)K, d, mask_channels, ord...);
+      else hipLaunchKernelGGL((k_edge_fwd<2, ORD...>), g, b, 0, st, D, mask, R, sums, (int)K, d, mask_channels, ord...);
     }
   }
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
+}
+
+// ---- f2 fused (round 4): see k_loss_fused_fwd4.  ADVCHAIN_ERR_UNSUPPORTED (-2) for what the 16-byte marching form does not
+// take (rows of 4j <= 256 voxels, K = 2..4, at most a one-channel mask, 16-byte aligned tensors): use the entries above.
+// ORD / oc as for consistency_fwd.
+template <class... ORD>
+static int consistency_fused_fwd(const OrdCounts* oc, const float* pred, const float* ref, const float* mask, float* R, float* sums,
+                                 int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels, int ref_is_prob,
+                                 int want_edges, int want_kl, void* stream, ORD... ord) {
+  ADVCHAIN_CHECK_ARG(pred && ref && sums, "consistency_fused_fwd: null pointer");
+  ADVCHAIN_CHECK_ARG(ldims_ok(ndim, dims), "consistency_fused_fwd: bad dims");
+  ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && K >= 1 && K <= kMaxK, "consistency_fused_fwd: bad N/K (K <= 16)");
+  static const bool off = getenv("ADVCHAIN_NO_FUSED_LOSS") != nullptr;   // A/B knob
+  // 3D: the y-marching kernel below was measured SLOWER than the three-kernel form (K = 4: 4 x 4 x 128 x 128 x 64 230 against
+  // 199 us -- its z fold reads three planes per row) and is instantiated for 2D only since round 5; 3D takes
+  // k_loss_fused_fwd3d_z (z-marching with the y neighbours through LDS; edges wanted, rows of at most 128 voxels;
+  // ADVCHAIN_NO_FUSED_LOSS_3DZ switches it off for A/B) or the unfused entries.
+  const Dims d = lmake_dims(ndim, dims);
+  const bool edges = want_edges && K > 1;
+  const bool zmarch = ndim == 3 && z3_takes(d, edges);
+  if (off || (ndim == 3 && !zmarch) || K < 2 || K > 4 || (mask && mask_channels != 1)) return ADVCHAIN_ERR_UNSUPPORTED;
+  if (d.voxels() >= (1ll << 31) || !march4_ok(d, pred, ref, mask, R)) return ADVCHAIN_ERR_UNSUPPORTED;
+  if (oc)
+    for (int r = 0; r < 4; ++r) oc->counts[r] = 0;
+  if (N == 0) return ADVCHAIN_OK;
+  const int zc = zmarch ? z3_chunk(d, N) : 0;
+  const int mlen = zmarch ? 0 : march4_len(d, N);
+  const dim3 gf = zmarch ? z3_grid(d, N, zc) : march4_grid(d, N, mlen);
+  if (oc) {
+    ADVCHAIN_CHECK_ARG(oc->fits(gf), "consistency_fused_fwd_ord: the partial buffer is smaller than the launch (advchain_consistency_fused_fwd_partials)");
+    oc->set(0, gf);
+    if (edges) { oc->set(1, gf); oc->set(2, gf); }
+    if (want_kl) oc->set(3, gf);
+  }
+  if (zmarch) {
+    const dim3 gz = gf, bz(kZ3Waves * 64);
+    const size_t lds = z3_lds(d, K);
+    hipStream_t stz = (hipStream_t)stream;
+#define FWD3DZ(K_) do { \
+      if (want_kl) hipLaunchKernelGGL((k_loss_fused_fwd3d_z<K_, true, ORD...>), gz, bz, lds, stz, pred, ref, mask, R, sums, d, zc, ref_is_prob, ord...); \
+      else hipLaunchKernelGGL((k_loss_fused_fwd3d_z<K_, false, ORD...>), gz, bz, lds, stz, pred, ref, mask, R, sums, d, zc, ref_is_prob, ord...); } while (0)
+    switch (K) { case 2: FWD3DZ(2); break; case 3: FWD3DZ(3); break; default: FWD3DZ(4); break; }
+#undef FWD3DZ
+    ADVCHAIN_LAUNCH_CHECK();
+    return ADVCHAIN_OK;
+  }
+  if (edges && !R) R = nullptr;                      // (no gradient wanted: the sums only)
+  const dim3 g4 = gf, b4(kBlock);
+  hipStream_t st = (hipStream_t)stream;
+#define FUSED_FWD(DIM_, K_) do { \
+    if (want_kl) { if (edges) hipLaunchKernelGGL((k_loss_fused_fwd4<DIM_, K_, true, true, float, ORD...>), g4, b4, 0, st, pred, ref, mask, R, sums, d, mlen, ref_is_prob, ord...); \
+                   else hipLaunchKernelGGL((k_loss_fused_fwd4<DIM_, K_, true, false, float, ORD...>), g4, b4, 0, st, pred, ref, mask, R, sums, d, mlen, ref_is_prob, ord...); } \
+    else { if (edges) hipLaunchKernelGGL((k_loss_fused_fwd4<DIM_, K_, false, true, float, ORD...>), g4, b4, 0, st, pred, ref, mask, R, sums, d, mlen, ref_is_prob, ord...); \
+           else hipLaunchKernelGGL((k_loss_fused_fwd4<DIM_, K_, false, false, float, ORD...>), g4, b4, 0, st, pred, ref, mask, R, sums, d, mlen, ref_is_prob, ord...); } } while (0)
+  switch (K) { case 2: FUSED_FWD(2, 2); break; case 3: FUSED_FWD(2, 3); break; default: FUSED_FWD(2, 4); break; }
+#undef FUSED_FWD
+  ADVCHAIN_LAUNCH_CHECK();
+  return ADVCHAIN_OK;
+}
+
+// The ordered finisher: wave r adds the counts[r] cells of row r of the [4][stride] partials, lane j the cells j, j + 64, ...
+// in that order, then the fixed tree of wave_sum -- a deterministic function of the partials.  A row with count 0 is 0 and
+// its cells are never read.  The value: k_consistency_finish's expression.
+__global__ void __launch_bounds__(kBlock)
+k_consistency_finish_ord(const float* __restrict__ partials, int stride, int n0, int n1, int n2, int n3, float c0, float c1, float c2,
+                         float c3, float* __restrict__ sums, float* __restrict__ value) {
+  __shared__ float row[4];
+  const int r = threadIdx.x >> 6, j = threadIdx.x & 63;
+  const int cnt = r == 0 ? n0 : (r == 1 ? n1 : (r == 2 ? n2 : n3));
+  const float* p = partials + (int64_t)r * stride;
+  float v = 0.f;
+  for (int i = j; i < cnt; i += 64) v += p[i];
+  v = wave_sum(v);
+  if (j == 0) { row[r] = v; sums[r] = v; }
+  __syncthreads();
+  if (threadIdx.x == 0) value[0] = ((c0 * row[0] + c1 * row[1]) + c2 * row[2]) + c3 * row[3];
+}
+
+extern "C" {
+
+int advchain_consistency_fwd(const float* pred, const float* ref, const float* mask, float* P, float* D, float* R,
+                             float* sums, int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels,
+                             int ref_is_prob, int want_edges, int want_kl, void* stream) {
+  return consistency_fwd<>(nullptr, pred, ref, mask, P, D, R, sums, N, K, ndim, dims, mask_channels, ref_is_prob, want_edges,
+                           want_kl, stream);
+}
+
+// The most workgroups a launch of advchain_consistency_fwd(_ord) has for these arguments (aligned16: every tensor is 16-byte
+// aligned): the capacity `stride` of a row of the partial buffer.  Host-only.
+int64_t advchain_consistency_fwd_partials(int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels, int want_edges,
+                                          int aligned16) {
+  if (!dims || !ldims_ok(ndim, dims) || N < 0 || N >= 65536 || K < 1 || K > kMaxK) return -1;
+  const Dims d = lmake_dims(ndim, dims);
+  if (d.voxels() >= (1ll << 31)) return -1;
+  const int64_t V = d.voxels();
+  const int64_t all = (int64_t)advchain_blocks(V, kBlock) * N;
+  int64_t w = (V % 4 == 0 && aligned16 && K >= 2 && K <= 5) ? (int64_t)advchain_blocks(V / 4, kBlock) * N : all;
+  if (want_edges && K > 1) {
+    EdgeMarch em;
+    const float* a = reinterpret_cast<const float*>(aligned16 ? (uintptr_t)0 : (uintptr_t)4);
+    if (N > 0 && mask_channels <= 1 && edge_march_plan(K, N, d, a, a, nullptr, (d.s2 % 64) == 0, em))
+      w = std::max(w, (int64_t)em.grid.x * em.grid.y);
+    else
+      w = std::max(w, all);
+  }
+  return w;
+}
+
+// advchain_consistency_fwd with the sums in a fixed order (deterministic mode): every workgroup stores its partial of row r at
+// partials[r * stride + workgroup] instead of adding it into a slot; counts[r] (host, 4 entries) receives the number of cells
+// of row r that were written (0: the row is not part of this evaluation) -- what advchain_consistency_finish_ord adds up.
+int advchain_consistency_fwd_ord(const float* pred, const float* ref, const float* mask, float* P, float* D, float* R,
+                                 float* partials, int64_t stride, int32_t* counts, int64_t N, int64_t K, int ndim,
+                                 const int64_t* dims, int mask_channels, int ref_is_prob, int want_edges, int want_kl, void* stream) {
+  ADVCHAIN_CHECK_ARG(counts && stride >= 1 && stride < (1ll << 31), "consistency_fwd_ord: bad partial buffer (stride / counts)");
+  const OrdCounts oc{stride, counts};
+  return consistency_fwd<SumsOrdered>(&oc, pred, ref, mask, P, D, R, partials, N, K, ndim, dims, mask_channels, ref_is_prob,
+                                      want_edges, want_kl, stream, SumsOrdered{(int)stride});
 }
 
 int advchain_consistency_finish(float* slots, const float* coef4_host, float* sums, float* value, int reset, void* stream) {
@@ -1555,49 +1702,51 @@ int advchain_consistency_bwd(const float* P, const float* D, const float* R, con
   return ADVCHAIN_OK;
 }
 
-// ---- f2 fused (round 4): see k_loss_fused_fwd4.  ADVCHAIN_ERR_UNSUPPORTED (-2) for what the 16-byte marching form does not
-// take (rows of 4j <= 256 voxels, K = 2..4, at most a one-channel mask, 16-byte aligned tensors): use the entries above.
 int advchain_consistency_fused_fwd(const float* pred, const float* ref, const float* mask, float* R, float* sums, int64_t N,
                                    int64_t K, int ndim, const int64_t* dims, int mask_channels, int ref_is_prob, int want_edges,
                                    int want_kl, void* stream) {
-  ADVCHAIN_CHECK_ARG(pred && ref && sums, "consistency_fused_fwd: null pointer");
-  ADVCHAIN_CHECK_ARG(ldims_ok(ndim, dims), "consistency_fused_fwd: bad dims");
-  ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && K >= 1 && K <= kMaxK, "consistency_fused_fwd: bad N/K (K <= 16)");
-  static const bool off = getenv("ADVCHAIN_NO_FUSED_LOSS") != nullptr;   // A/B knob
-  // 3D: the y-marching kernel below was measured SLOWER than the three-kernel form (K = 4: 4 x 4 x 128 x 128 x 64 230 against
-  // 199 us -- its z fold reads three planes per row) and is instantiated for 2D only since round 5; 3D takes
-  // k_loss_fused_fwd3d_z (z-marching with the y neighbours through LDS; edges wanted, rows of at most 128 voxels;
-  // ADVCHAIN_NO_FUSED_LOSS_3DZ switches it off for A/B) or the unfused entries.
+  return consistency_fused_fwd<>(nullptr, pred, ref, mask, R, sums, N, K, ndim, dims, mask_channels, ref_is_prob, want_edges,
+                                 want_kl, stream);
+}
+
+// The workgroups of advchain_consistency_fused_fwd(_ord)'s one launch, or ADVCHAIN_ERR_UNSUPPORTED (-2) where the entry
+// returns it (has_mask: a mask is given; aligned16: every tensor is 16-byte aligned).  Host-only.
+int64_t advchain_consistency_fused_fwd_partials(int64_t N, int64_t K, int ndim, const int64_t* dims, int has_mask, int mask_channels,
+                                                int want_edges, int aligned16) {
+  if (!dims || !ldims_ok(ndim, dims) || N < 0 || N >= 65536 || K < 1 || K > kMaxK) return -1;
+  static const bool off = getenv("ADVCHAIN_NO_FUSED_LOSS") != nullptr;
   const Dims d = lmake_dims(ndim, dims);
   const bool edges = want_edges && K > 1;
   const bool zmarch = ndim == 3 && z3_takes(d, edges);
-  if (off || (ndim == 3 && !zmarch) || K < 2 || K > 4 || (mask && mask_channels != 1)) return ADVCHAIN_ERR_UNSUPPORTED;
-  if (d.voxels() >= (1ll << 31) || !march4_ok(d, pred, ref, mask, R)) return ADVCHAIN_ERR_UNSUPPORTED;
-  if (N == 0) return ADVCHAIN_OK;
-  if (zmarch) {
-    const int zc = z3_chunk(d, N);
-    const dim3 gz = z3_grid(d, N, zc), bz(kZ3Waves * 64);
-    const size_t lds = z3_lds(d, K);
-    hipStream_t stz = (hipStream_t)stream;
-#define FWD3DZ(K_) do { \
-      if (want_kl) hipLaunchKernelGGL((k_loss_fused_fwd3d_z<K_, true>), gz, bz, lds, stz, pred, ref, mask, R, sums, d, zc, ref_is_prob); \
-      else hipLaunchKernelGGL((k_loss_fused_fwd3d_z<K_, false>), gz, bz, lds, stz, pred, ref, mask, R, sums, d, zc, ref_is_prob); } while (0)
-    switch (K) { case 2: FWD3DZ(2); break; case 3: FWD3DZ(3); break; default: FWD3DZ(4); break; }
-#undef FWD3DZ
-    ADVCHAIN_LAUNCH_CHECK();
-    return ADVCHAIN_OK;
-  }
-  if (edges && !R) R = nullptr;                      // (no gradient wanted: the sums only)
-  const int mlen = march4_len(d, N);
-  const dim3 g4 = march4_grid(d, N, mlen), b4(kBlock);
-  hipStream_t st = (hipStream_t)stream;
-#define FUSED_FWD(DIM_, K_) do { \
-    if (want_kl) { if (edges) hipLaunchKernelGGL((k_loss_fused_fwd4<DIM_, K_, true, true>), g4, b4, 0, st, pred, ref, mask, R, sums, d, mlen, ref_is_prob); \
-                   else hipLaunchKernelGGL((k_loss_fused_fwd4<DIM_, K_, true, false>), g4, b4, 0, st, pred, ref, mask, R, sums, d, mlen, ref_is_prob); } \
-    else { if (edges) hipLaunchKernelGGL((k_loss_fused_fwd4<DIM_, K_, false, true>), g4, b4, 0, st, pred, ref, mask, R, sums, d, mlen, ref_is_prob); \
-           else hipLaunchKernelGGL((k_loss_fused_fwd4<DIM_, K_, false, false>), g4, b4, 0, st, pred, ref, mask, R, sums, d, mlen, ref_is_prob); } } while (0)
-  switch (K) { case 2: FUSED_FWD(2, 2); break; case 3: FUSED_FWD(2, 3); break; default: FUSED_FWD(2, 4); break; }
-#undef FUSED_FWD
+  if (off || (ndim == 3 && !zmarch) || K < 2 || K > 4 || (has_mask && mask_channels != 1)) return ADVCHAIN_ERR_UNSUPPORTED;
+  const void* a = reinterpret_cast<const void*>(aligned16 ? (uintptr_t)0 : (uintptr_t)4);
+  if (d.voxels() >= (1ll << 31) || !march4_ok(d, a, a, a, a)) return ADVCHAIN_ERR_UNSUPPORTED;
+  if (N == 0) return 0;
+  const dim3 g = zmarch ? z3_grid(d, N, z3_chunk(d, N)) : march4_grid(d, N, march4_len(d, N));
+  return (int64_t)g.x * g.y;
+}
+
+// advchain_consistency_fused_fwd with the sums in a fixed order: partials / stride / counts as for advchain_consistency_fwd_ord.
+int advchain_consistency_fused_fwd_ord(const float* pred, const float* ref, const float* mask, float* R, float* partials,
+                                       int64_t stride, int32_t* counts, int64_t N, int64_t K, int ndim, const int64_t* dims,
+                                       int mask_channels, int ref_is_prob, int want_edges, int want_kl, void* stream) {
+  ADVCHAIN_CHECK_ARG(counts && stride >= 1 && stride < (1ll << 31), "consistency_fused_fwd_ord: bad partial buffer (stride / counts)");
+  const OrdCounts oc{stride, counts};
+  return consistency_fused_fwd<SumsOrdered>(&oc, pred, ref, mask, R, partials, N, K, ndim, dims, mask_channels, ref_is_prob,
+                                            want_edges, want_kl, stream, SumsOrdered{(int)stride});
+}
+
+// The finisher of the *_fwd_ord entries: sums[r] = the counts[r] cells of row r of `partials` added in a fixed order,
+// value = sum_r coef[r] * sums[r] (k_consistency_finish's expression).  Nothing to reset.
+int advchain_consistency_finish_ord(const float* partials, int64_t stride, const int32_t* counts4_host, const float* coef4_host,
+                                    float* sums, float* value, void* stream) {
+  ADVCHAIN_CHECK_ARG(partials && counts4_host && coef4_host && sums && value, "consistency_finish_ord: null pointer");
+  ADVCHAIN_CHECK_ARG(stride >= 1 && stride < (1ll << 31), "consistency_finish_ord: bad stride");
+  for (int r = 0; r < 4; ++r)
+    ADVCHAIN_CHECK_ARG(counts4_host[r] >= 0 && counts4_host[r] <= stride, "consistency_finish_ord: a count exceeds the stride");
+  hipLaunchKernelGGL(k_consistency_finish_ord, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, partials, (int)stride, counts4_host[0],
+                     counts4_host[1], counts4_host[2], counts4_host[3], coef4_host[0], coef4_host[1], coef4_host[2], coef4_host[3],
+                     sums, value);
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
 }

@@ -41,6 +41,31 @@ __device__ __forceinline__ float kl_term(float t, float log_t, float log_q, floa
   return m * (p * lp) - m * (p * log_q);
 }
 
+// Where a forward kernel's workgroup partial of sum `row` (0 mse, 1 edge A, 2 edge B, 3 kl) goes.  The forward kernels end in
+// a parameter pack: EMPTY in the default mode -- a float atomic into slot sum_slot() of the row's 64 accumulators, and the
+// kernel's name, parameters and instructions are what they were before the pack -- or one SumsOrdered (the *_fwd_ord entries,
+// deterministic mode): `sums` is then a [4][stride] buffer and every workgroup STORES its partial into its own cell of the
+// row (zeros included, so the buffer needs no clearing), for k_consistency_finish_ord to add up in a fixed order.
+struct SumsOrdered { int stride; };
+__device__ __forceinline__ void sums_put(float* __restrict__ sums, int row, float v) {
+  atomic_add_f32(sums + row * kSumSlots + sum_slot(), v);
+}
+__device__ __forceinline__ void sums_put(float* __restrict__ sums, int row, float v, const SumsOrdered& o) {
+  sums[(int64_t)row * o.stride + ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = v;
+}
+// (loss_lp.hip: the class weights of the cw entries travel in the same pack, in front)
+__device__ __forceinline__ void sums_put(float* __restrict__ sums, int row, float v, const float*) { sums_put(sums, row, v); }
+__device__ __forceinline__ void sums_put(float* __restrict__ sums, int row, float v, const float*, const SumsOrdered& o) {
+  sums_put(sums, row, v, o);
+}
+// Host side of the *_fwd_ord entries: the grid of a launch fits the buffer, and the rows it writes get its workgroup count.
+struct OrdCounts {
+  int64_t stride;
+  int32_t* counts;     // [4], host
+  bool fits(dim3 g) const { return (int64_t)g.x * g.y * g.z <= stride; }
+  void set(int row, dim3 g) const { counts[row] = (int32_t)((int64_t)g.x * g.y * g.z); }
+};
+
 // ---- the run-time-K kernels (loss_wide.hip, loss_ref.hip) ----
 
 // running max / sum of exp(x - max): ONE exp per element (the other factor of the usual two is exp(0))

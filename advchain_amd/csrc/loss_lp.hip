@@ -35,6 +35,7 @@
 // loss_ref.hip does).  No atomics on the gradients and no shared accumulator: bit-reproducible.  Streaming + 3^d stencil:
 // memory-bound, no MFMA.
 #include <stdio.h>
+#include <algorithm>
 
 #include "loss_common.h"
 
@@ -70,6 +71,14 @@ __device__ __forceinline__ float lp_cw(int) { return 1.f; }
 __device__ __forceinline__ float lp_cw(int k, const float* cw) {
   return ((const __attribute__((address_space(4))) float*)cw)[k];
 }
+// The two FORWARD kernels may carry one more element behind the weights: a SumsOrdered (loss_common.h; the *_fwd_ord
+// entries), which sends the workgroup partials to their own cells instead of the 64 slots.  W... is then one of
+// {}, {const float*}, {SumsOrdered}, {const float*, SumsOrdered}; the first two are the kernels of the default mode.
+__device__ __forceinline__ float lp_cw(int, const SumsOrdered&) { return 1.f; }
+__device__ __forceinline__ float lp_cw(int k, const float* cw, const SumsOrdered&) { return lp_cw(k, cw); }
+// (sums_put takes the same four packs: loss_common.h)
+template <typename... W> struct lp_weighted { static constexpr bool value = false; };
+template <typename... T> struct lp_weighted<const float*, T...> { static constexpr bool value = true; };
 
 // 4 consecutive values of one plane: WIDE one 16-byte (fp32) / 8-byte (bf16) access, else `cnt` (1..4) scalar ones
 template <typename ST, bool WIDE>
@@ -143,7 +152,7 @@ template <typename PT, typename RT, bool WIDE, typename... W>
 __global__ void __launch_bounds__(kBlock)
 k_lp_stats(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* __restrict__ mask, float* __restrict__ stats,
            float* __restrict__ sums, int K, int V, int mask_ch, int ref_is_prob, int want_kl, W... cw) {
-  constexpr bool CW = sizeof...(W) != 0;
+  constexpr bool CW = lp_weighted<W...>::value;
   __shared__ float smem[8];
   const int n = blockIdx.y;
   const int64_t v64 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * 4;
@@ -210,8 +219,8 @@ k_lp_stats(const PT* __restrict__ pred, const RT* __restrict__ ref, const float*
   }
   block_sum<2>(acc, smem);
   if (threadIdx.x == 0) {
-    atomic_add_f32(sums + sum_slot(), acc[0]);
-    if (want_kl) atomic_add_f32(sums + 3 * kSumSlots + sum_slot(), acc[1]);
+    sums_put(sums, 0, acc[0], cw...);
+    if (want_kl) sums_put(sums, 3, acc[1], cw...);
   }
 }
 
@@ -220,7 +229,7 @@ __global__ void __launch_bounds__(kBlock)
 k_lp_edge(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* __restrict__ mask,
           const float* __restrict__ stats, float* __restrict__ R, float* __restrict__ sums, int K, Dims d, int mask_ch,
           int ref_is_prob, W... cw) {
-  constexpr bool CW = sizeof...(W) != 0;
+  constexpr bool CW = lp_weighted<W...>::value;
   using T = WTile<DIM>;
   __shared__ float lds[2][T::NH];
   __shared__ float smem[8];
@@ -285,8 +294,8 @@ k_lp_edge(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* 
   }
   block_sum<2>(acc, smem);
   if (threadIdx.x == 0) {
-    atomic_add_f32(sums + kSumSlots + sum_slot(), acc[0]);
-    atomic_add_f32(sums + 2 * kSumSlots + sum_slot(), acc[1]);
+    sums_put(sums, 1, acc[0], cw...);
+    sums_put(sums, 2, acc[1], cw...);
   }
 }
 
@@ -445,15 +454,26 @@ inline bool lp_nk_ok(int64_t N, int64_t K) { return N >= 0 && N < 65536 && K >= 
 inline bool lp_flag_ok(int f) { return f == 0 || f == 1; }
 inline bool lp_aligned(const void* p, int bytes) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % bytes) == 0; }
 
-// w: nothing (the lp entries) or the K class weights in device memory (the cw entries); it selects the kernels' pack
+// w: nothing (the lp entries) or the K class weights in device memory (the cw entries), and behind them a SumsOrdered for the
+// *_fwd_ord entries; it selects the kernels' pack.  `oc` (the ord entries only): the partial buffer's capacity and the host
+// array that receives the workgroup count of every row written.  false: a launch has more workgroups than the buffer holds
+// (nothing was enqueued).
 template <typename PT, typename RT, typename... W>
-void lp_launch_fwd(hipStream_t st, const void* pred, const void* ref, const float* mask, float* stats, float* R, float* sums,
-                   int N, int K, int ndim, Dims d, int mask_ch, int ref_is_prob, int want_edges, int want_kl, W... w) {
+bool lp_launch_fwd(hipStream_t st, const OrdCounts* oc, const void* pred, const void* ref, const float* mask, float* stats, float* R,
+                   float* sums, int N, int K, int ndim, Dims d, int mask_ch, int ref_is_prob, int want_edges, int want_kl, W... w) {
   const int V = (int)d.voxels();
   const PT* p = (const PT*)pred;
   const RT* r = (const RT*)ref;
   const dim3 b(kBlock);
   const dim3 g((unsigned)advchain_blocks(((int64_t)V + 3) / 4, kBlock), (unsigned)N);
+  const bool edges = want_edges && K > 1;
+  const dim3 ge((unsigned)(ndim == 3 ? WTile<3>::count(d) : WTile<2>::count(d)), (unsigned)N);
+  if (oc) {
+    if (!oc->fits(g) || (edges && !oc->fits(ge))) return false;
+    oc->set(0, g);
+    if (want_kl) oc->set(3, g);
+    if (edges) { oc->set(1, ge); oc->set(2, ge); }
+  }
   const bool wide = V % 4 == 0 && lp_aligned(pred, 4 * (int)sizeof(PT)) && lp_aligned(ref, 4 * (int)sizeof(RT)) &&
                     lp_aligned(mask, 16) && lp_aligned(stats, 16);
   if (wide)
@@ -462,14 +482,15 @@ void lp_launch_fwd(hipStream_t st, const void* pred, const void* ref, const floa
   else
     hipLaunchKernelGGL((k_lp_stats<PT, RT, false>), g, b, 0, st, p, r, mask, stats, sums, K, V, mask_ch, ref_is_prob, want_kl,
                        w...);
-  if (want_edges && K > 1) {
+  if (edges) {
     if (ndim == 3)
-      hipLaunchKernelGGL((k_lp_edge<PT, RT, 3>), dim3((unsigned)WTile<3>::count(d), (unsigned)N), b, 0, st, p, r, mask, stats, R,
+      hipLaunchKernelGGL((k_lp_edge<PT, RT, 3>), ge, b, 0, st, p, r, mask, stats, R,
                          sums, K, d, mask_ch, ref_is_prob, w...);
     else
-      hipLaunchKernelGGL((k_lp_edge<PT, RT, 2>), dim3((unsigned)WTile<2>::count(d), (unsigned)N), b, 0, st, p, r, mask, stats, R,
+      hipLaunchKernelGGL((k_lp_edge<PT, RT, 2>), ge, b, 0, st, p, r, mask, stats, R,
                          sums, K, d, mask_ch, ref_is_prob, w...);
   }
+  return true;
 }
 
 template <typename PT, typename RT, typename... W>
@@ -534,17 +555,30 @@ void lp_launch_ref(hipStream_t st, const void* pred, const void* ref, const floa
   const Dims d = lmake_dims(ndim, dims);                                                                       \
   ADVCHAIN_LP_CHECK(d.voxels() < (1ll << 31), "volume too large")
 
-int lp_fwd(const char* who, bool weighted, const void* pred, int pred_bf16, const void* ref, int ref_bf16, const float* mask,
-           float* stats, float* R, float* sums, int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels,
-           int ref_is_prob, int want_edges, int want_kl, const float* class_w, void* stream) {
+// `oc` == nullptr: the lp / cw entries (sums = the 4 x 64 slots).  Otherwise the ord entries: sums = the [4][oc->stride] partials.
+int lp_fwd(const char* who, bool weighted, const OrdCounts* oc, const void* pred, int pred_bf16, const void* ref, int ref_bf16,
+           const float* mask, float* stats, float* R, float* sums, int64_t N, int64_t K, int ndim, const int64_t* dims,
+           int mask_channels, int ref_is_prob, int want_edges, int want_kl, const float* class_w, void* stream) {
   ADVCHAIN_LP_CHECK_COMMON(sums);
+  if (oc) {
+    ADVCHAIN_LP_CHECK(oc->counts && oc->stride >= 1 && oc->stride < (1ll << 31), "bad partial buffer (stride / counts)");
+    for (int r = 0; r < 4; ++r) oc->counts[r] = 0;
+  }
   if (N == 0) return ADVCHAIN_OK;
-  if (weighted)
-    ADVCHAIN_LP_DISPATCH(lp_launch_fwd, pred_bf16, ref_bf16, (hipStream_t)stream, pred, ref, mask, stats, R, sums, (int)N, (int)K,
-                         ndim, d, mask_channels, ref_is_prob, want_edges, want_kl, class_w);
-  else
-    ADVCHAIN_LP_DISPATCH(lp_launch_fwd, pred_bf16, ref_bf16, (hipStream_t)stream, pred, ref, mask, stats, R, sums, (int)N, (int)K,
-                         ndim, d, mask_channels, ref_is_prob, want_edges, want_kl);
+  bool ok = true;
+#define ADVCHAIN_LP_FWD_ARGS                                                                                             \
+  (hipStream_t) stream, oc, pred, ref, mask, stats, R, sums, (int)N, (int)K, ndim, d, mask_channels, ref_is_prob, want_edges, \
+      want_kl
+  if (oc) {
+    const SumsOrdered so{(int)oc->stride};
+    if (weighted) ADVCHAIN_LP_DISPATCH(ok = lp_launch_fwd, pred_bf16, ref_bf16, ADVCHAIN_LP_FWD_ARGS, class_w, so);
+    else ADVCHAIN_LP_DISPATCH(ok = lp_launch_fwd, pred_bf16, ref_bf16, ADVCHAIN_LP_FWD_ARGS, so);
+  } else {
+    if (weighted) ADVCHAIN_LP_DISPATCH(ok = lp_launch_fwd, pred_bf16, ref_bf16, ADVCHAIN_LP_FWD_ARGS, class_w);
+    else ADVCHAIN_LP_DISPATCH(ok = lp_launch_fwd, pred_bf16, ref_bf16, ADVCHAIN_LP_FWD_ARGS);
+  }
+#undef ADVCHAIN_LP_FWD_ARGS
+  ADVCHAIN_LP_CHECK(ok, "the partial buffer is smaller than a launch (size it with advchain_consistency_lp_fwd_partials)");
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
 }
@@ -581,7 +615,7 @@ extern "C" {
 int advchain_consistency_lp_fwd(const void* pred, int pred_bf16, const void* ref, int ref_bf16, const float* mask, float* stats,
                                 float* R, float* sums, int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels,
                                 int ref_is_prob, int want_edges, int want_kl, void* stream) {
-  return lp_fwd("consistency_lp_fwd", false, pred, pred_bf16, ref, ref_bf16, mask, stats, R, sums, N, K, ndim, dims,
+  return lp_fwd("consistency_lp_fwd", false, nullptr, pred, pred_bf16, ref, ref_bf16, mask, stats, R, sums, N, K, ndim, dims,
                 mask_channels, ref_is_prob, want_edges, want_kl, nullptr, stream);
 }
 
@@ -601,11 +635,35 @@ int advchain_consistency_lp_ref_bwd(const void* pred, int pred_bf16, const void*
                 c_mse, c_a, c_b, c_kl, ref_is_prob, N, K, ndim, dims, mask_channels, nullptr, stream);
 }
 
+// The most workgroups a launch of the two entries below (and of lp_fwd / cw_fwd, whose grids they share) has for these
+// arguments: the capacity `stride` of a row of their partial buffer.  Host-only.
+int64_t advchain_consistency_lp_fwd_partials(int64_t N, int64_t K, int ndim, const int64_t* dims, int want_edges) {
+  if (!dims || !ldims_ok(ndim, dims) || !lp_nk_ok(N, K)) return -1;
+  const Dims d = lmake_dims(ndim, dims);
+  if (d.voxels() >= (1ll << 31)) return -1;
+  int64_t w = (int64_t)advchain_blocks((d.voxels() + 3) / 4, kBlock) * N;
+  if (want_edges && K > 1) w = std::max(w, (ndim == 3 ? WTile<3>::count(d) : WTile<2>::count(d)) * N);
+  return w;
+}
+
+// advchain_consistency_lp_fwd / cw_fwd with the sums in a fixed order (deterministic mode): the same kernels, but every
+// workgroup stores its partial of row r at partials[r * stride + workgroup] instead of adding it into a slot, and
+// counts[r] (host, 4 entries) receives the number of cells of row r that were written (0: the row is not part of this
+// evaluation) -- what advchain_consistency_finish_ord adds up.  class_w == NULL: the unweighted loss.
+int advchain_consistency_lp_fwd_ord(const void* pred, int pred_bf16, const void* ref, int ref_bf16, const float* mask, float* stats,
+                                    float* R, float* partials, int64_t stride, int32_t* counts, int64_t N, int64_t K, int ndim,
+                                    const int64_t* dims, int mask_channels, int ref_is_prob, int want_edges, int want_kl,
+                                    const float* class_w, void* stream) {
+  const OrdCounts oc{stride, counts};
+  return lp_fwd("consistency_lp_fwd_ord", class_w != nullptr, &oc, pred, pred_bf16, ref, ref_bf16, mask, stats, R, partials, N, K,
+                ndim, dims, mask_channels, ref_is_prob, want_edges, want_kl, class_w, stream);
+}
+
 // the class-weighted entries: the same kernels with CW = true, for all four storage pairs (fp32-fp32 included)
 int advchain_consistency_cw_fwd(const void* pred, int pred_bf16, const void* ref, int ref_bf16, const float* mask, float* stats,
                                 float* R, float* sums, int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels,
                                 int ref_is_prob, int want_edges, int want_kl, const float* class_w, void* stream) {
-  return lp_fwd("consistency_cw_fwd", true, pred, pred_bf16, ref, ref_bf16, mask, stats, R, sums, N, K, ndim, dims,
+  return lp_fwd("consistency_cw_fwd", true, nullptr, pred, pred_bf16, ref, ref_bf16, mask, stats, R, sums, N, K, ndim, dims,
                 mask_channels, ref_is_prob, want_edges, want_kl, class_w, stream);
 }
 

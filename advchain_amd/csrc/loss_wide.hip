@@ -21,6 +21,7 @@
 //
 // Saved per evaluation: stats 16 V N bytes and R 8 (K - 1) V N bytes; P and D (8 K V N bytes) never exist.
 // Streaming + 3^d stencil: memory-bound, no MFMA.
+#include <algorithm>
 #include "loss_common.h"
 
 namespace advchain {
@@ -41,10 +42,11 @@ __device__ __forceinline__ void wstore(float* __restrict__ p, const float (&o)[V
 }
 
 // VEC voxels per lane (4: 16-byte loads, V % 4 == 0 and 16-byte aligned tensors)
-template <int VEC>
+template <int VEC, class... ORD>
 __global__ void __launch_bounds__(kBlock)
 k_wide_stats(const float* __restrict__ pred, const float* __restrict__ ref, const float* __restrict__ mask,
-             float* __restrict__ stats, float* __restrict__ sums, int K, int V, int mask_ch, int ref_is_prob, int want_kl) {
+             float* __restrict__ stats, float* __restrict__ sums, int K, int V, int mask_ch, int ref_is_prob, int want_kl,
+             ORD... ord) {
   __shared__ float smem[8];
   const int n = blockIdx.y;
   const int v = (blockIdx.x * kBlock + threadIdx.x) * VEC;
@@ -103,16 +105,16 @@ k_wide_stats(const float* __restrict__ pred, const float* __restrict__ ref, cons
   }
   block_sum<2>(acc, smem);
   if (threadIdx.x == 0) {
-    atomic_add_f32(sums + sum_slot(), acc[0]);
-    if (want_kl) atomic_add_f32(sums + 3 * kSumSlots + sum_slot(), acc[1]);
+    sums_put(sums, 0, acc[0], ord...);
+    if (want_kl) sums_put(sums, 3, acc[1], ord...);
   }
 }
 
-template <int DIM>
+template <int DIM, class... ORD>
 __global__ void __launch_bounds__(kBlock)
 k_wide_edge(const float* __restrict__ pred, const float* __restrict__ ref, const float* __restrict__ mask,
             const float* __restrict__ stats, float* __restrict__ R, float* __restrict__ sums, int K, Dims d, int mask_ch,
-            int ref_is_prob) {
+            int ref_is_prob, ORD... ord) {
   using T = WTile<DIM>;
   __shared__ float lds[2][T::NH];
   __shared__ float smem[8];
@@ -171,8 +173,8 @@ k_wide_edge(const float* __restrict__ pred, const float* __restrict__ ref, const
   }
   block_sum<2>(acc, smem);
   if (threadIdx.x == 0) {
-    atomic_add_f32(sums + kSumSlots + sum_slot(), acc[0]);
-    atomic_add_f32(sums + 2 * kSumSlots + sum_slot(), acc[1]);
+    sums_put(sums, 1, acc[0], ord...);
+    sums_put(sums, 2, acc[1], ord...);
   }
 }
 
@@ -270,39 +272,86 @@ using namespace advchain;
 
 static inline bool wide_nk_ok(int64_t N, int64_t K) { return N >= 0 && N < 65536 && K >= 1 && K < 65536; }
 
-extern "C" {
-
-int advchain_consistency_wide_fwd(const float* pred, const float* ref, const float* mask, float* stats, float* R, float* sums,
-                                  int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels, int ref_is_prob,
-                                  int want_edges, int want_kl, void* stream) {
+// advchain_consistency_wide_fwd (ORD empty, oc == nullptr: sums = the 4 x 64 slots) and advchain_consistency_wide_fwd_ord
+// (one SumsOrdered, sums = the [4][oc->stride] partials): the same choice of kernels either way.
+template <class... ORD>
+static int wide_fwd(const OrdCounts* oc, const float* pred, const float* ref, const float* mask, float* stats,
+                    float* R, float* sums, int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels, int ref_is_prob,
+                    int want_edges, int want_kl, void* stream, ORD... ord) {
   ADVCHAIN_CHECK_ARG(pred && ref && stats && sums && dims, "consistency_wide_fwd: null pointer");
   ADVCHAIN_CHECK_ARG(ldims_ok(ndim, dims), "consistency_wide_fwd: bad dims");
   ADVCHAIN_CHECK_ARG(wide_nk_ok(N, K), "consistency_wide_fwd: bad N/K (N < 65536, 1 <= K < 65536)");
   ADVCHAIN_CHECK_ARG(!mask || mask_channels == 1 || mask_channels == K, "consistency_wide_fwd: mask must have 1 or K channels");
   const Dims d = lmake_dims(ndim, dims);
   ADVCHAIN_CHECK_ARG(d.voxels() < (1ll << 31), "consistency_wide_fwd: volume too large");
+  if (oc)
+    for (int r = 0; r < 4; ++r) oc->counts[r] = 0;
   if (N == 0) return ADVCHAIN_OK;
   const int V = (int)d.voxels();
   hipStream_t st = (hipStream_t)stream;
   const dim3 b(kBlock);
   const bool al16 = ((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(ref) | reinterpret_cast<uintptr_t>(mask) |
                       reinterpret_cast<uintptr_t>(stats)) & 15) == 0;
-  if (V % 4 == 0 && al16)
-    hipLaunchKernelGGL(k_wide_stats<4>, dim3(advchain_blocks(V / 4, kBlock), (unsigned)N), b, 0, st, pred, ref, mask, stats,
-                       sums, (int)K, V, mask_channels, ref_is_prob, want_kl);
+  const bool vec4 = V % 4 == 0 && al16;
+  const bool edges = want_edges && K > 1;
+  const dim3 gs(advchain_blocks(vec4 ? V / 4 : V, kBlock), (unsigned)N);
+  const dim3 ge((unsigned)(ndim == 3 ? WTile<3>::count(d) : WTile<2>::count(d)), (unsigned)N);
+  if (oc) {
+    ADVCHAIN_CHECK_ARG(oc->fits(gs) && (!edges || oc->fits(ge)),
+                       "consistency_wide_fwd_ord: the partial buffer is smaller than a launch (advchain_consistency_wide_fwd_partials)");
+    oc->set(0, gs);
+    if (want_kl) oc->set(3, gs);
+    if (edges) { oc->set(1, ge); oc->set(2, ge); }
+  }
+  if (vec4)
+    hipLaunchKernelGGL((k_wide_stats<4, ORD...>), gs, b, 0, st, pred, ref, mask, stats,
+                       sums, (int)K, V, mask_channels, ref_is_prob, want_kl, ord...);
   else
-    hipLaunchKernelGGL(k_wide_stats<1>, dim3(advchain_blocks(V, kBlock), (unsigned)N), b, 0, st, pred, ref, mask, stats,
-                       sums, (int)K, V, mask_channels, ref_is_prob, want_kl);
-  if (want_edges && K > 1) {
+    hipLaunchKernelGGL((k_wide_stats<1, ORD...>), gs, b, 0, st, pred, ref, mask, stats,
+                       sums, (int)K, V, mask_channels, ref_is_prob, want_kl, ord...);
+  if (edges) {
     if (ndim == 3)
-      hipLaunchKernelGGL(k_wide_edge<3>, dim3((unsigned)WTile<3>::count(d), (unsigned)N), b, 0, st, pred, ref, mask, stats, R,
-                         sums, (int)K, d, mask_channels, ref_is_prob);
+      hipLaunchKernelGGL((k_wide_edge<3, ORD...>), ge, b, 0, st, pred, ref, mask, stats, R,
+                         sums, (int)K, d, mask_channels, ref_is_prob, ord...);
     else
-      hipLaunchKernelGGL(k_wide_edge<2>, dim3((unsigned)WTile<2>::count(d), (unsigned)N), b, 0, st, pred, ref, mask, stats, R,
-                         sums, (int)K, d, mask_channels, ref_is_prob);
+      hipLaunchKernelGGL((k_wide_edge<2, ORD...>), ge, b, 0, st, pred, ref, mask, stats, R,
+                         sums, (int)K, d, mask_channels, ref_is_prob, ord...);
   }
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
+}
+
+extern "C" {
+
+int advchain_consistency_wide_fwd(const float* pred, const float* ref, const float* mask, float* stats, float* R, float* sums,
+                                  int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels, int ref_is_prob,
+                                  int want_edges, int want_kl, void* stream) {
+  return wide_fwd<>(nullptr, pred, ref, mask, stats, R, sums, N, K, ndim, dims, mask_channels, ref_is_prob,
+                    want_edges, want_kl, stream);
+}
+
+// The most workgroups a launch of advchain_consistency_wide_fwd(_ord) has for these arguments (aligned16: every tensor is
+// 16-byte aligned): the capacity `stride` of a row of the partial buffer.  Host-only.
+int64_t advchain_consistency_wide_fwd_partials(int64_t N, int64_t K, int ndim, const int64_t* dims, int want_edges, int aligned16) {
+  if (!dims || !ldims_ok(ndim, dims) || !wide_nk_ok(N, K)) return -1;
+  const Dims d = lmake_dims(ndim, dims);
+  if (d.voxels() >= (1ll << 31)) return -1;
+  const int64_t V = d.voxels();
+  int64_t w = (int64_t)advchain_blocks((V % 4 == 0 && aligned16) ? V / 4 : V, kBlock) * N;
+  if (want_edges && K > 1) w = std::max(w, (ndim == 3 ? WTile<3>::count(d) : WTile<2>::count(d)) * N);
+  return w;
+}
+
+// advchain_consistency_wide_fwd with the sums in a fixed order (deterministic mode): partials[r * stride + workgroup] and
+// counts[4] (host) as for advchain_consistency_lp_fwd_ord.
+int advchain_consistency_wide_fwd_ord(const float* pred, const float* ref, const float* mask, float* stats, float* R,
+                                      float* partials, int64_t stride, int32_t* counts, int64_t N, int64_t K, int ndim,
+                                      const int64_t* dims, int mask_channels, int ref_is_prob, int want_edges, int want_kl,
+                                      void* stream) {
+  ADVCHAIN_CHECK_ARG(counts && stride >= 1 && stride < (1ll << 31), "consistency_wide_fwd_ord: bad partial buffer (stride / counts)");
+  const OrdCounts oc{stride, counts};
+  return wide_fwd<SumsOrdered>(&oc, pred, ref, mask, stats, R, partials, N, K, ndim, dims, mask_channels,
+                               ref_is_prob, want_edges, want_kl, stream, SumsOrdered{(int)stride});
 }
 
 int advchain_consistency_wide_bwd(const float* pred, const float* ref, const float* stats, const float* R, const float* mask,

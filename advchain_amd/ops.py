@@ -197,8 +197,11 @@ RIDE_INTERPS = ("bilinear", "trilinear", "linear", "nearest")
 def set_deterministic(on):
     """Process-wide: route the backward formulations whose bits depend on arrival order -- the window scatter's float-atomic
     flush, and the general float-atomic kernels that warps of more than four channels (affine: more than eight), nearest and
-    size-changing warps end in -- through their 64-bit fixed-point twins (include/advchain_hip.h: advchain_set_deterministic,
-    advchain_grid_sample_bwd_det, advchain_affine_warp_bwd_det).  The solver sets it at
+    size-changing warps end in, and the bicubic backward -- through their 64-bit fixed-point twins (include/advchain_hip.h:
+    advchain_set_deterministic, advchain_grid_sample_bwd_det, advchain_affine_warp_bwd_det,
+    advchain_grid_sample_bicubic2d_bwd_det), and the two VALUES that arrive through float atomics in the default mode -- the
+    consistency loss (the *_fwd_ord entries) and the norm behind the 3D step count (field_sumsq) -- through one partial per
+    workgroup and an ordered reduction.  The solver sets it at
     the start of every call from its `deterministic` attribute; two solvers with different settings in one process are fine as
     long as their calls do not interleave (a workspace is sized when it is allocated, for the mode of that moment)."""
     _lib.load().advchain_set_deterministic(1 if on else 0)
@@ -536,6 +539,28 @@ def raw_tp_interp(coef, tables, C, add_identity=False, scale=1.0, want_out=True,
                                                   _stream()),
                "tp_interp_fwd")
     return out
+
+
+def field_sumsq(coef, tables, C):
+    """Sum of the squares of the field that `raw_tp_interp(coef, tables, C)` interpolates, as a 1-element device tensor; the
+    field is not materialised.  It is what the 3D step-count rule (adv_morph.py:159-162) takes the root of: the solver, a
+    sharded `reduce_sumsq` and the frozen plan's check all read it here.  Default mode: workgroup partials arrive in 64 slots
+    through float atomics (last bits vary run to run).  Deterministic mode: one partial per workgroup and one ordered
+    reduction (advchain_tp_interp_sumsq_ordered) -- equal bits for equal inputs, so the count never flips at a threshold."""
+    coef = _dev(coef, "coefficients")
+    if is_deterministic():
+        lib = _lib.load()
+        planes = coef.shape[0] * coef.shape[1]
+        S = _lib.dims_array(tables.S)
+        partials = torch.empty(max(1, lib.advchain_tp_interp_sumsq_partials(S, planes)), device=coef.device, dtype=torch.float32)
+        out = torch.empty(1, device=coef.device, dtype=torch.float32)
+        _lib.check(lib.advchain_tp_interp_sumsq_ordered(_ptr(coef), _ptr(tables.itab), _ptr(tables.ftab), S,
+                                                        _lib.dims_array(tables.g), _lib.dims_array(tables.B), planes, C,
+                                                        _ptr(partials), _ptr(out), _stream()), "tp_interp_sumsq_ordered")
+        return out
+    slots = torch.zeros(64, device=coef.device, dtype=torch.float32)
+    raw_tp_interp(coef, tables, C, want_out=False, sumsq=slots)
+    return slots.sum().reshape(1)
 
 
 def raw_tp_adjoint(gfull, tables, gfull2=None, scale=1.0):
@@ -1014,6 +1039,15 @@ class _GridSampleBicubic(torch.autograd.Function):
         gin = torch.empty_like(inp) if need_in else None
         ggrid = torch.empty_like(grid) if need_grid else None
         N, C = inp.shape[:2]
+        if need_in and is_deterministic():      # grad_in through the int64 image instead of float atomics
+            lib = _lib.load()
+            ws = torch.empty(max(1, lib.advchain_bicubic2d_det_workspace(N, C, _lib.dims_array(inp.shape[2:]))),
+                             device=inp.device, dtype=torch.int32)
+            _lib.check(lib.advchain_grid_sample_bicubic2d_bwd_det(_ptr(_dev(gout, "grad")), _ptr(inp), _ptr(grid), _ptr(gin),
+                                                                  _ptr(ggrid), _ptr(ws), N, C, _lib.dims_array(inp.shape[2:]),
+                                                                  _lib.dims_array(grid.shape[2:]), ctx.padding, _stream()),
+                       "grid_sample_bicubic2d_bwd_det")
+            return gin, ggrid, None
         _lib.check(_lib.load().advchain_grid_sample_bicubic2d_bwd(_ptr(_dev(gout, "grad")), _ptr(inp), _ptr(grid), _ptr(gin), _ptr(ggrid),
                                                                   N, C, _lib.dims_array(inp.shape[2:]), _lib.dims_array(grid.shape[2:]),
                                                                   ctx.padding, _stream()), "grid_sample_bicubic2d_bwd")
@@ -1291,10 +1325,8 @@ class _DemonsField(torch.autograd.Function):
         frozen = plan is not None and plan.is_frozen
         norm_rb = None
         if nsteps_rule:  # 3D: whole-batch Frobenius norm of u / 2^n must not exceed 0.5 (adv_morph.py:159-162)
-            slots = torch.zeros(64, device=vel.device, dtype=torch.float32)
             # pair: the batch is [v; -v] -- the rule is the reference's, over ONE field's batch (both halves agree)
-            raw_tp_interp(s1[:N // 2] if pair else s1, tables, d, want_out=False, sumsq=slots)
-            ss = slots.sum().reshape(1)
+            ss = field_sumsq(s1[:N // 2] if pair else s1, tables, d)
             if reduce_sumsq is not None:
                 ss = reduce_sumsq(ss)
             if frozen:       # the recorded count; the replay checks on the device that the rule still gives it
@@ -1603,6 +1635,26 @@ def demons_field_pair(vel, scale, tables, nsteps_rule, reduce_sumsq=None, opts=N
     return qp, qm
 
 
+def _aligned16(*tensors):
+    return int(all(t is None or t.data_ptr() % 16 == 0 for t in tensors))
+
+
+@functools.lru_cache(maxsize=256)
+def _ordered_stride(family, N, K, shape, *flags):
+    """The family's host-only *_fwd_partials query (per shape: asked once)."""
+    fn = getattr(_lib.load(), "advchain_consistency_%s_partials" % family)
+    return int(fn(N, K, len(shape), _lib.dims_array(shape), *flags))
+
+
+def _ordered_partials(n, what, device):
+    """The [4][stride] partial buffer of a *_fwd_ord entry and the host array that receives the rows' counts.  An ordinary
+    temporary: inside a hip-graph capture it comes from the capture's allocations.  Nothing to clear."""
+    if n < 0:
+        raise ValueError("bad loss shape for %s" % what)
+    stride = max(1, int(n))
+    return torch.empty(4 * stride, device=device, dtype=torch.float32), stride, (ctypes.c_int32 * 4)()
+
+
 class _Consistency(torch.autograd.Function):
     """c_mse * S0 + c_a * SA + c_b * SB + c_kl * SKL  with  S0 = sum((P m - T m)^2), SA/SB = masked edge energies,
     SKL = sum m T' (log T' - log P)  (advchain/common/loss.py:55-79,102-220,223-249).  Differentiable w.r.t. the
@@ -1638,10 +1690,46 @@ class _Consistency(torch.autograd.Function):
         # the slots again) evicts the shared accumulator instead of leaving partial sums for the next evaluation
         sums = torch.empty(4, device=pred.device, dtype=torch.float32)
         value = torch.empty((), device=pred.device, dtype=torch.float32)
-        slots = _persistent_zeros("loss", (4, 64), pred.device)   # per-workgroup partials, 64 slots per sum; zeroed by the finisher
         lib = _lib.load()
         wide = K >= WIDE_LOSS_MIN_K
         stats = None
+        if is_deterministic():
+            # the value in a fixed order: the same kernels store one partial per workgroup, the ordered finisher adds them
+            # (include/advchain_hip.h, the *_fwd_ord entries); everything the backward reads is what the default mode saves
+            args = (N, K, nd, dims, mch, int(ref_is_prob), int(want_edges), int(want_kl), _stream())
+            shape = tuple(pred.shape[2:])
+            fused = False
+            P = D = None
+            if wide:
+                stats = torch.empty((N, 4) + tuple(pred.shape[2:]), device=pred.device, dtype=torch.float32)
+                part, stride, counts = _ordered_partials(_ordered_stride(
+                    "wide_fwd", N, K, shape, int(want_edges), _aligned16(pred, ref, mask, stats)), "consistency_wide_fwd_ord",
+                    pred.device)
+                _lib.check(lib.advchain_consistency_wide_fwd_ord(_ptr(pred), _ptr(ref), _ptr(mask), _ptr(stats), _ptr(R), _ptr(part),
+                                                                 stride, counts, *args), "consistency_wide_fwd_ord")
+            else:
+                nf = _ordered_stride("fused_fwd", N, K, shape, int(mask is not None), mch, int(want_edges),
+                                     _aligned16(pred, ref, mask, R)) if FUSED_LOSS else -2
+                if nf != -2:
+                    part, stride, counts = _ordered_partials(nf, "consistency_fused_fwd_ord", pred.device)
+                    rc = lib.advchain_consistency_fused_fwd_ord(_ptr(pred), _ptr(ref), _ptr(mask), _ptr(R), _ptr(part), stride,
+                                                                counts, *args)
+                    fused = rc != -2
+                    if fused:
+                        _lib.check(rc, "consistency_fused_fwd_ord")
+                if not fused:
+                    P = torch.empty_like(pred)
+                    D = torch.empty_like(pred)
+                    part, stride, counts = _ordered_partials(_ordered_stride(
+                        "fwd", N, K, shape, mch, int(want_edges), _aligned16(pred, ref, mask, P, D, R)), "consistency_fwd_ord",
+                        pred.device)
+                    _lib.check(lib.advchain_consistency_fwd_ord(_ptr(pred), _ptr(ref), _ptr(mask), _ptr(P), _ptr(D), _ptr(R),
+                                                                _ptr(part), stride, counts, *args), "consistency_fwd_ord")
+            _lib.check(lib.advchain_consistency_finish_ord(_ptr(part), stride, counts, _lib.float_array(coef), _ptr(sums),
+                                                           _ptr(value), _stream()), "consistency_finish_ord")
+            return _Consistency._save_fp32(ctx, value, sums, pred, ref, mask, R, P, D, stats, wide, fused, coef, mch,
+                                           ref_is_prob, want_edges)
+        slots = _persistent_zeros("loss", (4, 64), pred.device)   # per-workgroup partials, 64 slots per sum; zeroed by the finisher
         try:
             if wide:
                 # run-time K: per-voxel softmax statistics of both operands instead of P and D
@@ -1670,6 +1758,15 @@ class _Consistency(torch.autograd.Function):
         except BaseException:
             _forget_persistent(slots)
             raise
+        return _Consistency._save_fp32(ctx, value, sums, pred, ref, mask, R, P, D, stats, wide, fused, coef, mch, ref_is_prob,
+                                       want_edges)
+
+    @staticmethod
+    def _save_fp32(ctx, value, sums, pred, ref, mask, R, P, D, stats, wide, fused, coef, mch, ref_is_prob, want_edges):
+        """What the backward of the fp32 families needs -- the same in both modes."""
+        K = pred.shape[1]
+        need_pred, need_ref = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_grad = need_pred or need_ref
         if need_grad:
             if wide:
                 ctx.save_for_backward(pred, ref, R, mask, stats)
@@ -1705,12 +1802,24 @@ class _Consistency(torch.autograd.Function):
             R = torch.empty((N, 2 * (K - 1)) + tuple(pred.shape[2:]), device=pred.device, dtype=torch.float32)
         sums = torch.empty(4, device=pred.device, dtype=torch.float32)
         value = torch.empty((), device=pred.device, dtype=torch.float32)
-        slots = _persistent_zeros("loss", (4, 64), pred.device)
         stats = torch.empty((N, 4) + tuple(pred.shape[2:]), device=pred.device, dtype=torch.float32)
         lib = _lib.load()
         cw = None if class_w is None else class_weights_device(class_w, pred.device)
+        det = is_deterministic()
+        if det:         # the value in a fixed order (see forward)
+            part, stride, counts = _ordered_partials(_ordered_stride("lp_fwd", N, K, tuple(pred.shape[2:]), int(want_edges)),
+                                                     "consistency_lp_fwd_ord", pred.device)
+            _lib.check(lib.advchain_consistency_lp_fwd_ord(
+                _ptr(pred), int(pred.dtype == torch.bfloat16), _ptr(ref), int(ref.dtype == torch.bfloat16), _ptr(mask),
+                _ptr(stats), _ptr(R), _ptr(part), stride, counts, N, K, nd, dims, mch, int(ref_is_prob), int(want_edges),
+                int(want_kl), _ptr(cw), _stream()), "consistency_lp_fwd_ord")
+            _lib.check(lib.advchain_consistency_finish_ord(_ptr(part), stride, counts, _lib.float_array(coef), _ptr(sums),
+                                                           _ptr(value), _stream()), "consistency_finish_ord")
+        slots = None if det else _persistent_zeros("loss", (4, 64), pred.device)
         try:
-            if cw is None:
+            if det:
+                pass
+            elif cw is None:
                 _lib.check(lib.advchain_consistency_lp_fwd(
                     _ptr(pred), int(pred.dtype == torch.bfloat16), _ptr(ref), int(ref.dtype == torch.bfloat16), _ptr(mask),
                     _ptr(stats), _ptr(R), _ptr(slots), N, K, nd, dims, mch, int(ref_is_prob), int(want_edges), int(want_kl),
@@ -1720,8 +1829,9 @@ class _Consistency(torch.autograd.Function):
                     _ptr(pred), int(pred.dtype == torch.bfloat16), _ptr(ref), int(ref.dtype == torch.bfloat16), _ptr(mask),
                     _ptr(stats), _ptr(R), _ptr(slots), N, K, nd, dims, mch, int(ref_is_prob), int(want_edges), int(want_kl),
                     _ptr(cw), _stream()), "consistency_cw_fwd")
-            _lib.check(lib.advchain_consistency_finish(_ptr(slots), _lib.float_array(coef), _ptr(sums), _ptr(value), 1,
-                                                       _stream()), "consistency_finish")
+            if not det:
+                _lib.check(lib.advchain_consistency_finish(_ptr(slots), _lib.float_array(coef), _ptr(sums), _ptr(value), 1,
+                                                           _stream()), "consistency_finish")
         except BaseException:
             _forget_persistent(slots)
             raise

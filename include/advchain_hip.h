@@ -51,17 +51,22 @@ const char* advchain_last_error(void);
  *           atomics -- gets a bit-reproducible twin: the tiles add 64-bit fixed point (2^40 / max|grad_out| of the batch
  *           entry) into an int64 image of grad_in inside the caller's workspace and one more pass converts it.  The
  *           general float-atomic kernels (warps of more than four channels, nearest, size-changing; the affine scatter
- *           of more than eight channels) have twins of the same kind as entries of their own --
- *           advchain_grid_sample_bwd_det, advchain_affine_warp_bwd_det -- which the Python layer calls when the switch
- *           is on.  Every other backward formulation (gather forms, owner-computes scatters, affine tiles) is
- *           deterministic already.
+ *           of more than eight channels) and the bicubic backward have twins of the same kind as entries of their own --
+ *           advchain_grid_sample_bwd_det, advchain_affine_warp_bwd_det, advchain_grid_sample_bicubic2d_bwd_det -- which the
+ *           Python layer calls when the switch is on.  Every other backward formulation (gather forms, owner-computes
+ *           scatters, affine tiles) is deterministic already.  Two VALUES are covered the same way, by entries the Python
+ *           layer calls when the switch is on: the consistency loss (the *_fwd_ord entries + advchain_consistency_finish_ord:
+ *           one partial per workgroup, added in a fixed order, instead of float atomics into 64 slots) and the norm behind the
+ *           3D step count (advchain_tp_interp_sumsq_ordered).  The step count DOES depend on that norm -- a last-bit
+ *           difference at a power-of-two threshold changes the number of squarings and with it every result of the call --
+ *           so bit-reproducible 3D morph chains need the ordered norm.  The supervised losses (seg_loss.hip) always reduce
+ *           in a fixed order.
  * PROCESS-WIDE switch, read when a backward entry is called and by advchain_scatter_workspace (which then returns the larger
  * size: allocate workspaces AFTER setting the mode; a workspace sized in the other mode must not be reused).  Not covered
  * (still float atomics): the overflow list of the LDS-tiled scatter (reflection padding, 3-channel image warps, calls without
  * a displacement bound), nearest-neighbour / size-changing backward THROUGH advchain_grid_sample_bwd ITSELF (call
- * advchain_grid_sample_bwd_det), the bicubic backward, affine samples flagged as degenerate by the gather form (C <= 8), and
- * the VALUE of the consistency loss / of the 3D step-count norm (partial sums arrive in any order; nothing
- * downstream of them but the number itself depends on the order).                                                       */
+ * advchain_grid_sample_bwd_det), the bicubic backward THROUGH advchain_grid_sample_bicubic2d_bwd ITSELF (call its _det
+ * twin), and affine samples flagged as degenerate by the gather form (C <= 8).  The switch is per process, not per call.  */
 void advchain_set_deterministic(int on);
 int advchain_get_deterministic(void);
 
@@ -265,6 +270,25 @@ int advchain_grid_sample_bicubic2d_fwd(const float* in, const float* grid, float
 int advchain_grid_sample_bicubic2d_bwd(const float* grad_out, const float* in, const float* grid, float* grad_in,
                                        float* grad_grid, int64_t N, int64_t C, const int64_t* in_dims,
                                        const int64_t* out_dims, int padding, void* stream);
+/* Deterministic twin of advchain_grid_sample_bicubic2d_bwd (all three paddings, in_dims != out_dims, any C >= 1).
+ * replaces: the same grid_sampler_2d_backward (bicubic), as torch.use_deterministic_algorithms() would want it.
+ * grad_in goes through an int64 fixed-point image with the passes of advchain_grid_sample_bwd_det (clear, max |grad_out| per
+ * batch entry, 64-bit integer deposits, convert): equal bits run to run; a NaN / inf in an entry's grad_out turns that entry's
+ * grad_in into NaN and leaves the other entries alone.  Width of the fixed point: a deposit is grad_out * cx * cy, and for
+ * A = -0.75 the cubic weights satisfy |cx|, |cy| <= 1 (cubic1 falls from 1 to 0 on [0, 1]; cubic2 = A (x - 1)(x - 2)^2 has its
+ * extreme -1/9 at x = 4/3), so a deposit is at most max|grad_out| = 2^bits units; border / reflection padding can fold all 16
+ * taps of an output pixel onto one cell, so a cell receives at most 16 OH OW deposits, and
+ *     bits = min(40, 62 - ceil(log2(16 OH OW)))
+ * keeps every sum below 2^62 (quantum max|grad_out| / 2^bits per deposit).  det_ws:
+ * int32[advchain_bicubic2d_det_workspace(N, C, in_dims)] = 2 N C H W for the image + N maxima padded to a multiple of 4,
+ * 8-byte aligned (an odd C H W is fine: the image is converted with 8-byte loads); host-only size query, independent of the
+ * switch; required when grad_in is asked for.  grad_in is overwritten (no pre-zeroing).  grad_grid is bit for bit what
+ * advchain_grid_sample_bicubic2d_bwd writes: that very kernel is launched for it with grad_in = NULL, and the deposits are
+ * a launch of their own.  Works whatever advchain_get_deterministic() says.                                            */
+int64_t advchain_bicubic2d_det_workspace(int64_t N, int64_t C, const int64_t* in_dims); /* int32 elements */
+int advchain_grid_sample_bicubic2d_bwd_det(const float* grad_out, const float* in, const float* grid, float* grad_in,
+                                           float* grad_grid, int32_t* det_ws, int64_t N, int64_t C, const int64_t* in_dims,
+                                           const int64_t* out_dims, int padding, void* stream);
 /* replaces: F.affine_grid(theta, size, align_corners=True) for the bicubic affine warp (adv_affine.py:297-305): theta
  *           (N,2,3) -> planar grid (N,2,H,W), and its adjoint grad_grid -> grad_theta (deterministic two-stage sum;
  *           workspace: advchain_affine_grid2d_bwd_workspace floats).                                                */
@@ -300,6 +324,15 @@ int advchain_affine_theta_bwd(const float* param, const float* cfg_host, float p
 int advchain_tp_interp_fwd(const float* coef, float* out, const int32_t* itab, const float* ftab, const int64_t* S,
                            const int64_t* g, const int64_t* B, int64_t planes, int64_t C, int ndim, int add_identity,
                            float scale, float* sumsq, float* disp_out, void* stream);
+/* The sum of squares of the call above (out = NULL, sumsq) in a FIXED ORDER (deterministic mode).
+ * replaces: torch.norm(duv_interval) ** 2 of vectorFieldExponentiation3D (adv_morph.py:159-162), a deterministic function of
+ *           its input in the reference.  The kernel advchain_tp_interp_fwd would pick writes one partial per workgroup into
+ *           `partials` (at least advchain_tp_interp_sumsq_partials(S, planes) = ceil(S[1] / 32) * S[0] * planes floats: the most
+ *           workgroups such a launch has; host-only query, -1 for bad sizes; no clearing needed) and one workgroup adds them
+ *           in a fixed order into out[0].  The field is not materialised.  Works whatever the switch says.            */
+int64_t advchain_tp_interp_sumsq_partials(const int64_t* S, int64_t planes); /* floats */
+int advchain_tp_interp_sumsq_ordered(const float* coef, const int32_t* itab, const float* ftab, const int64_t* S, const int64_t* g,
+                                     const int64_t* B, int64_t planes, int64_t C, float* partials, float* out, void* stream);
 /* advchain_gauss_small_pair (forward) + advchain_tp_interp_fwd in ONE launch (round 6) for the paired 2D field [v; -v].
  * replaces: the first two steps of AdvMorph.DemonsCompose -- the Gaussian of the low-resolution velocity (adv_morph.py:377-452,
  *           called at :460-462) and F.interpolate to full size (adv_morph.py:464) -- for forward() / backward() of one solver
@@ -551,6 +584,46 @@ int advchain_consistency_cw_ref_bwd(const void* pred, int pred_bf16, const void*
                                     const float* R /*nullable*/, const float* mask, const float* grad_scale, void* grad_ref,
                                     float c_mse, float c_a, float c_b, float c_kl, int ref_is_prob, int64_t N, int64_t K,
                                     int ndim, const int64_t* dims, int mask_channels, const float* class_w, void* stream);
+
+/* ---- the consistency loss with its sums in a fixed order (deterministic mode) -------------------------------------------
+ * replaces: the same calc_segmentation_consistency / contour_loss / kl_divergence sums (common/loss.py:8-87,102-249), which are
+ *           deterministic functions of their inputs in the reference's CPU path.
+ * Each *_fwd_ord entry is its forward family's entry with `sums` (the 4 x 64 slots) replaced by
+ *   partials : float[4 * stride], row r (0 mse, 1 edge A, 2 edge B, 3 kl) at partials + r * stride.  Every workgroup of a
+ *              launch STORES its partial into its own cell (zeros included): no clearing, no atomics;
+ *   stride   : capacity of a row, at least the family's *_fwd_partials(...) for the same arguments (host-only queries: the
+ *              most workgroups a launch of the family has; `aligned16`: every tensor is 16-byte aligned, which selects the
+ *              vector kernels; -1 for bad sizes; the fused query returns -2 where the fused entry does).  A buffer that is
+ *              too small is an argument error and nothing is enqueued;
+ *   counts   : int32[4] in HOST memory, written by the entry: the number of cells of row r that the launches write
+ *              (0: the row is not part of this evaluation -- no 'kl', no edges).
+ * The same kernels as the default mode's, instantiated with a store in place of the atomic; R / P / D / stats are bit for bit
+ * the default mode's, so every backward entry is used unchanged.  advchain_consistency_lp_fwd_ord covers the lp entry
+ * (class_w == NULL) and the cw entry.  advchain_consistency_finish_ord adds row r's counts[r] cells in a fixed order (lane j of
+ * one wave takes cells j, j + 64, ...; then a fixed tree) into sums[r] and forms value = sum_r coef[r] * sums[r] with the
+ * expression of advchain_consistency_finish.  They work whatever advchain_get_deterministic() says.                    */
+int64_t advchain_consistency_fwd_partials(int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels, int want_edges,
+                                          int aligned16);
+int advchain_consistency_fwd_ord(const float* pred, const float* ref, const float* mask, float* P, float* D, float* R,
+                                 float* partials, int64_t stride, int32_t* counts, int64_t N, int64_t K, int ndim,
+                                 const int64_t* dims, int mask_channels, int ref_is_prob, int want_edges, int want_kl, void* stream);
+int64_t advchain_consistency_fused_fwd_partials(int64_t N, int64_t K, int ndim, const int64_t* dims, int has_mask, int mask_channels,
+                                                int want_edges, int aligned16);
+int advchain_consistency_fused_fwd_ord(const float* pred, const float* ref, const float* mask, float* R, float* partials,
+                                       int64_t stride, int32_t* counts, int64_t N, int64_t K, int ndim, const int64_t* dims,
+                                       int mask_channels, int ref_is_prob, int want_edges, int want_kl, void* stream);
+int64_t advchain_consistency_wide_fwd_partials(int64_t N, int64_t K, int ndim, const int64_t* dims, int want_edges, int aligned16);
+int advchain_consistency_wide_fwd_ord(const float* pred, const float* ref, const float* mask, float* stats, float* R,
+                                      float* partials, int64_t stride, int32_t* counts, int64_t N, int64_t K, int ndim,
+                                      const int64_t* dims, int mask_channels, int ref_is_prob, int want_edges, int want_kl,
+                                      void* stream);
+int64_t advchain_consistency_lp_fwd_partials(int64_t N, int64_t K, int ndim, const int64_t* dims, int want_edges);
+int advchain_consistency_lp_fwd_ord(const void* pred, int pred_bf16, const void* ref, int ref_bf16, const float* mask, float* stats,
+                                    float* R, float* partials, int64_t stride, int32_t* counts, int64_t N, int64_t K, int ndim,
+                                    const int64_t* dims, int mask_channels, int ref_is_prob, int want_edges, int want_kl,
+                                    const float* class_w /*nullable*/, void* stream);
+int advchain_consistency_finish_ord(const float* partials, int64_t stride, const int32_t* counts4_host, const float* coef4_host,
+                                    float* sums, float* value, void* stream);
 
 /* bf16 STORAGE experiment (round 6; BASELINE config 2 names "bf16"): the 2D K = 4 fused loss above (common/loss.py:8-87,
  * 102-220: mse + contour terms on logits) with pred / ref / R / grad_pred stored as bfloat16 (raw 16-bit words, 8-byte aligned)

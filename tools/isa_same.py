@@ -5,8 +5,10 @@
     python tools/isa_same.py old.s new.s [--match k_lp_]
 
 Kernels are paired by their demangled names (c++filt), so a template that gained a trailing, empty parameter pack pairs with
-its earlier self.  Compared: every instruction line with its operands, in order, and the local labels (renumbered per
-function); comments and assembler directives are dropped.  Prints one line per kernel of `old.s` and exits 1 on a kernel
+its earlier self; so does a plain kernel that became a template with nothing but such a pack (`void k<>(...)` pairs with
+`k(...)`: the return type c++filt prints for templates and an empty `<>` are dropped from both names).  Compared: every instruction line with its operands, in order, and the local labels (renumbered per
+function; a kernel's own constants, `__const.<mangled name>.x`, by their last part); comments and assembler directives are
+dropped.  Prints one line per kernel of `old.s` and exits 1 on a kernel
 that differs or has no partner.  Needs no GPU."""
 import argparse
 import re
@@ -30,13 +32,14 @@ def functions(path):
         text = line.split(";")[0].rstrip()
         if not text.strip() or (text.strip().startswith(".") and not text.startswith(".LBB")):
             continue
+        text = re.sub(r"__const\._Z\w+\.", "__const.FN.", text)     # a kernel's own constant: named after its mangled name
         body.append(re.sub(r"\.LBB\d+_", ".LBB_", text))
     return out
 
 
 def demangled(names):
     res = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True)
-    return dict(zip(names, res.stdout.splitlines()))
+    return {n: re.sub(r"^void ", "", d).replace("<>(", "(") for n, d in zip(names, res.stdout.splitlines())}
 
 
 def main():
