@@ -22,6 +22,9 @@ PROTOTYPES = {
     "advchain_grid_sample_fwd_ride": (_I, [_P, _P, _P, _P, _P, _L, _L, _I, _P, _P, _I, _I, _I, _I, _P]),
     "advchain_scatter_workspace": (_L, [_L, _I, _P]),
     "advchain_grid_sample_bwd": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _P, _I, _I, _I, _I, _P]),
+    "advchain_window_stage_workspace": (_L, [_L, _L, _I, _P]),
+    "advchain_grid_sample_bwd_staged": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "advchain_last_bwd_route": (_I, []),
     "advchain_det_warp_workspace": (_L, [_L, _L, _I, _P]),
     "advchain_grid_sample_bwd_det": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _P, _I, _I, _I, _P]),
     "advchain_compose_self_fwd": (_I, [_P, _P, _P, _L, _I, _P, _I, _P, _P]),

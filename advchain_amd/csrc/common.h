@@ -236,6 +236,18 @@ __device__ __forceinline__ void atomic_add_f32(float* p, float v) {
 
 extern "C" void advchain_set_error_(const char* msg);
 
+// advchain_last_bwd_route (include/advchain_hip.h): the launchers of the sampler backward note the formulation they took
+#define ADVCHAIN_ROUTE_NONE 0
+#define ADVCHAIN_ROUTE_GENERAL 1
+#define ADVCHAIN_ROUTE_ROWS 2
+#define ADVCHAIN_ROUTE_GATHER 3
+#define ADVCHAIN_ROUTE_MARCH 4
+#define ADVCHAIN_ROUTE_WINDOW_FLOAT 5
+#define ADVCHAIN_ROUTE_WINDOW_INT64 6
+#define ADVCHAIN_ROUTE_WINDOW_STAGED 7
+#define ADVCHAIN_ROUTE_TILED 8
+extern "C" void advchain_set_route_(int route);
+
 #define ADVCHAIN_CHECK_ARG(cond, msg)      \
   do {                                     \
     if (!(cond)) {                         \

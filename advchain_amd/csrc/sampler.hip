@@ -766,7 +766,8 @@ int advchain_scatter_march_launch(bool self, const float* gout, const float* in,
 // scatter_window.hip
 int advchain_scatter_window_launch(bool self, const float* gout, const float* in, const float* grid, float* gin,
                                    float* ggrid, int64_t N, int64_t C, int ndim, Dims d, int padding, int clamp_grid,
-                                   int halo, int32_t* workspace, hipStream_t st, int32_t* det_ws);
+                                   int halo, int32_t* workspace, hipStream_t st, int32_t* det_ws, int32_t* stage_ws = nullptr);
+int64_t advchain_window_stage_ints(int64_t N, int64_t C, Dims d);
 int advchain_scatter_rows2d_launch(bool self, const float* gout, const float* in, const float* grid, float* gin, float* ggrid,
                                    int64_t N, int64_t C, Dims d, int padding, int clamp_grid, int H, int32_t* workspace,
                                    hipStream_t st, int rm_flags = 0);
@@ -985,10 +986,11 @@ int advchain_grid_sample_fwd_ride(const float* in, const float* grid, float* out
   return advchain_nonzero_mask(ride_out, ride_out, total, stream);
 }
 
-int advchain_grid_sample_bwd(const float* grad_out, const float* in, const float* grid, float* grad_in,
-                             float* grad_grid, int32_t* workspace, int64_t N, int64_t C, int ndim,
-                             const int64_t* in_dims, const int64_t* out_dims, int interp, int padding, int clamp_grid,
-                             int halo, void* stream) {
+// advchain_grid_sample_bwd and advchain_grid_sample_bwd_staged: one routing, `stage_ws` reaches the window scatter
+static int grid_sample_bwd_routed(const float* grad_out, const float* in, const float* grid, float* grad_in,
+                                  float* grad_grid, int32_t* workspace, int64_t N, int64_t C, int ndim,
+                                  const int64_t* in_dims, const int64_t* out_dims, int interp, int padding, int clamp_grid,
+                                  int halo, void* stream, int32_t* stage_ws) {
   ADVCHAIN_CHECK_ARG(grad_out && in && grid, "grid_sample_bwd: null pointer");
   ADVCHAIN_CHECK_ARG(grad_in || grad_grid, "grid_sample_bwd: nothing to compute");
   ADVCHAIN_CHECK_ARG(dims_ok(ndim, in_dims) && dims_ok(ndim, out_dims, 1), "grid_sample_bwd: bad dims");
@@ -1003,26 +1005,59 @@ int advchain_grid_sample_bwd(const float* grad_out, const float* in, const float
     if (ndim == 2 && halo <= -2) {   // exact bound of a few pixels: whole-row owner-computes scatter (scatter_march.hip)
       const int rr = advchain_scatter_rows2d_launch(false, grad_out, in, grid, grad_in, grad_grid, N, C, id, padding, clamp_grid,
                                                     -halo, workspace, (hipStream_t)stream);
-      if (rr != ADVCHAIN_ERR_UNSUPPORTED) return rr;
+      if (rr != ADVCHAIN_ERR_UNSUPPORTED) { advchain_set_route_(ADVCHAIN_ROUTE_ROWS); return rr; }
     }
     // small displacement bound: gather form (adjoint_gather.hip); otherwise the LDS-tiled owner-computes scatter
     const int rc = advchain_warp_adjoint_gather_launch(grad_out, in, grid, grad_in, grad_grid, N, C, ndim, id, padding,
                                                        clamp_grid, workspace, halo, (hipStream_t)stream);
-    if (rc != ADVCHAIN_ERR_UNSUPPORTED) return rc;
+    if (rc != ADVCHAIN_ERR_UNSUPPORTED) { advchain_set_route_(ADVCHAIN_ROUTE_GATHER); return rc; }
     if (ndim == 3 && halo <= -2) {   // exact bound of 2..4 voxels: owner-computes march, no global atomics
       const int rm = advchain_scatter_march_launch(false, grad_out, in, grid, grad_in, grad_grid, N, C, id, padding, clamp_grid,
                                                    -halo, workspace, (hipStream_t)stream);
-      if (rm != ADVCHAIN_ERR_UNSUPPORTED) return rm;
+      if (rm != ADVCHAIN_ERR_UNSUPPORTED) { advchain_set_route_(ADVCHAIN_ROUTE_MARCH); return rm; }
     }
     const int rw = advchain_scatter_window_launch(false, grad_out, in, grid, grad_in, grad_grid, N, C, ndim, id, padding,
-                                                  clamp_grid, halo, nullptr, (hipStream_t)stream, workspace);   // source-tiled window
+                                                  clamp_grid, halo, nullptr, (hipStream_t)stream, workspace, stage_ws);   // source-tiled window (notes its own route)
     if (rw != ADVCHAIN_ERR_UNSUPPORTED) return rw;
+    advchain_set_route_(ADVCHAIN_ROUTE_TILED);
     return advchain_scatter_tiled_launch(false, grad_out, in, grid, grad_in, grad_grid, N, C, ndim, id, padding,
                                          clamp_grid, workspace, 0, halo < 0 ? -halo : halo, (hipStream_t)stream);
   }
   if (workspace && grad_in) advchain_zero_async(grad_in, sizeof(float) * N * C * id.voxels(), (hipStream_t)stream);
+  advchain_set_route_(ADVCHAIN_ROUTE_GENERAL);
   return ndim == 3 ? launch_grid_sample_bwd<3>(grad_out, in, grid, grad_in, grad_grid, N, C, id, od, interp, padding, clamp_grid, (hipStream_t)stream)
                    : launch_grid_sample_bwd<2>(grad_out, in, grid, grad_in, grad_grid, N, C, id, od, interp, padding, clamp_grid, (hipStream_t)stream);
+}
+
+int advchain_grid_sample_bwd(const float* grad_out, const float* in, const float* grid, float* grad_in,
+                             float* grad_grid, int32_t* workspace, int64_t N, int64_t C, int ndim,
+                             const int64_t* in_dims, const int64_t* out_dims, int interp, int padding, int clamp_grid,
+                             int halo, void* stream) {
+  return grid_sample_bwd_routed(grad_out, in, grid, grad_in, grad_grid, workspace, N, C, ndim, in_dims, out_dims, interp, padding,
+                                clamp_grid, halo, stream, nullptr);
+}
+
+// Host-only size query: the staging buffer of the staged deterministic window scatter (2D, C in {1, 2, 4}); 0 where that form
+// does not exist (3D, other channel counts) -- such calls pass stage_ws = NULL.
+int64_t advchain_window_stage_workspace(int64_t N, int64_t C, int ndim, const int64_t* dims) {
+  if (!dims || !dims_ok(ndim, dims) || N < 0 || N >= 65536 || C < 1) return -1;
+  if (ndim != 2 || (C != 1 && C != 2 && C != 4)) return 0;
+  return advchain_window_stage_ints(N, C, make_dims(ndim, dims));
+}
+
+// advchain_grid_sample_bwd with a staging buffer for the window scatter: same checks, same routing (rows scatter -> gather form
+// -> window).  The window route takes the staged form -- stage kernel + merge kernel, bit for bit the int64 twin's results --
+// in deterministic mode, 2D, with a non-null stage_ws; a null stage_ws is advchain_grid_sample_bwd itself.
+int advchain_grid_sample_bwd_staged(const float* grad_out, const float* in, const float* grid, float* grad_in,
+                                    float* grad_grid, int32_t* workspace, int64_t N, int64_t C, int ndim,
+                                    const int64_t* in_dims, const int64_t* out_dims, int interp, int padding, int clamp_grid,
+                                    int halo, void* stream, int32_t* stage_ws) {
+  ADVCHAIN_CHECK_ARG(!stage_ws || (workspace && grad_in), "grid_sample_bwd_staged: stage_ws needs workspace and grad_in");
+  ADVCHAIN_CHECK_ARG(!stage_ws || (((uintptr_t)stage_ws) & 15) == 0, "grid_sample_bwd_staged: stage_ws must be 16-byte aligned");
+  ADVCHAIN_CHECK_ARG(!stage_ws || (ndim == 2 && (C == 1 || C == 2 || C == 4)),
+                     "grid_sample_bwd_staged: stage_ws is for 2D warps of 1, 2 or 4 channels (advchain_window_stage_workspace)");
+  return grid_sample_bwd_routed(grad_out, in, grid, grad_in, grad_grid, workspace, N, C, ndim, in_dims, out_dims, interp, padding,
+                                clamp_grid, halo, stream, stage_ws);
 }
 
 int64_t advchain_det_warp_workspace(int64_t N, int64_t C, int ndim, const int64_t* in_dims) {

@@ -41,14 +41,30 @@ constexpr int kWinT = 32;               // sample tile edge
 constexpr int kWinCells = 8192;         // LDS window budget in cells (all channels together): 32 KiB
 constexpr int kWinCellsC4 = 12288;      // four channels: 48 KiB (2048 cells per channel = 45 x 45 capped stretched 32 x 32 tiles)
 
+// Staged form of the deterministic 2D scatter (advchain_grid_sample_bwd_staged): a workgroup of k_scatter_window2d launched with
+// a WinStage does not flush -- it stores its window as it stands (32-bit cells at the tile's scale) in a slot of its own and a
+// header next to it, and k_window_merge2d, one workgroup per 32 x 32 tile of grad_in, sums what the slots hold for its pixels in
+// 64-bit fixed point IN REGISTERS: the values and the roundings of the int64 twin (win_global_add<true>, k_det_convert), and no
+// int64 image, no clear, no maxima pass, no conversion pass and no global atomic.
+//   header: [bx0, by0, ww, wh (the capped window), bx1, by1 (the box is bx0..bx1 x by0..by1), bits of the tile's max |grad_out|,
+//            flags: 1 = a non-finite grad_out, 2 = a valid corner outside the capped window]
+constexpr int kWinHead = 8;
+struct WinStage {
+  int32_t* head;    // [N][tiles][kWinHead]
+  int32_t* cells;   // [N][tiles][C * cells_per_ch]: channel c of a window of ww x wh cells starts at c * ww * wh
+};
+__device__ __forceinline__ WinStage win_stage_of(const WinStage& s) { return s; }
+
 // SELF : in == grid == phi (C == 2); the coordinate-path gradient is added to the same tensor (atomics: other tiles
 //        deposit there too).  Otherwise GG: grad_grid is written with plain stores.
-template <int PAD, int C, bool SELF, bool GG, bool DET = false>
+// STG: empty, or one WinStage (the staged form: !SELF, DET = false -- nothing of the entry's scale is known yet)
+template <int PAD, int C, bool SELF, bool GG, bool DET = false, class... STG>
 __global__ void __launch_bounds__(kBlock)
 k_scatter_window2d(const float* __restrict__ gout, const float* __restrict__ in, const float* __restrict__ grid,
                    float* __restrict__ gin, float* __restrict__ ggrid, Dims d, int n2, int clamp_grid,
                    int32_t* __restrict__ ws, unsigned long long* __restrict__ acc64 = nullptr,
-                   const float* __restrict__ maxn = nullptr) {
+                   const float* __restrict__ maxn = nullptr, STG... stg) {
+  constexpr bool STAGE = sizeof...(STG) > 0;
   constexpr int kCells2 = C == 4 ? kWinCellsC4 : kWinCells;
   __shared__ int win[kCells2];
   if (ws && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) ws[3] = -1;   // no max|result| from this launch
@@ -73,6 +89,7 @@ k_scatter_window2d(const float* __restrict__ gout, const float* __restrict__ in,
   bool live[SPT], px[SPT], py[SPT];
   int bx0 = 1 << 30, bx1 = -(1 << 30), by0 = 1 << 30, by1 = -(1 << 30);
   float gmax = 0.f;
+  bool bad = false, outside = false;   // (STAGE) a non-finite grad_out; a valid corner outside the capped window
 #pragma unroll
   for (int j = 0; j < SPT; ++j) {
     const int sy = ty * kWinT + ly0 + 8 * j;
@@ -90,6 +107,7 @@ k_scatter_window2d(const float* __restrict__ gout, const float* __restrict__ in,
       const float g = gon[(int64_t)c * V + s];     // unconditional (s = 0 for a dead sample): no branch around the load
       go[j][c] = live[j] ? g : 0.f;
       gmax = fmaxf(gmax, fabsf(go[j][c]));
+      if constexpr (STAGE) bad = bad || !(fabsf(go[j][c]) <= 3.0e38f);     // (the test of k_det_absmax)
     }
     if (live[j]) {
       if (t[j].x.v0 || t[j].x.v1) { bx0 = min(bx0, t[j].x.i0 + (t[j].x.v0 ? 0 : 1)); bx1 = max(bx1, t[j].x.i0 + (t[j].x.v1 ? 1 : 0)); }
@@ -107,11 +125,16 @@ k_scatter_window2d(const float* __restrict__ gout, const float* __restrict__ in,
   if ((threadIdx.x & 63) == 0) {
     red[0][wave] = bx0; red[1][wave] = bx1; red[2][wave] = by0; red[3][wave] = by1; red[4][wave] = __float_as_int(gmax);
   }
+  if constexpr (STAGE) {
+    const bool wave_bad = __ballot(bad) != 0;
+    if ((threadIdx.x & 63) == 0) red[5][wave] = wave_bad;
+  }
   __syncthreads();
 #pragma unroll
   for (int w = 0; w < kBlock / 64; ++w) {
     bx0 = min(bx0, red[0][w]); bx1 = max(bx1, red[1][w]); by0 = min(by0, red[2][w]); by1 = max(by1, red[3][w]);
     gmax = fmaxf(gmax, __int_as_float(red[4][w]));
+    if constexpr (STAGE) bad = bad || red[5][w] != 0;
   }
   // window = box, capped to the LDS budget (keeps the low corner; what falls outside uses global atomics)
   int ww = max(bx1 - bx0 + 1, 0), wh = max(by1 - by0 + 1, 0);
@@ -160,6 +183,8 @@ k_scatter_window2d(const float* __restrict__ gout, const float* __restrict__ in,
           int* cell = win + cell0 + (cy ? ww : 0) + cx;
 #pragma unroll
           for (int c = 0; c < C; ++c) atomicAdd(cell + c * cells, fix_round(ws * fix_in(go[j][c], fs)));
+        } else if constexpr (STAGE) {
+          outside = true;           // left to k_window_merge2d, which rounds it at the entry's scale as the twin does
         } else {
           const int64_t dst = vox0 + (cy ? d.s2 : 0) + cx;
 #pragma unroll
@@ -178,7 +203,27 @@ k_scatter_window2d(const float* __restrict__ gout, const float* __restrict__ in,
       }
     }
   }
+  if constexpr (STAGE) {
+    const bool wave_out = __ballot(outside) != 0;
+    if ((threadIdx.x & 63) == 0) red[6][wave] = wave_out;
+  }
   __syncthreads();
+
+  // ---- 3. (staged form) the window as it stands and its header, plain stores
+  if constexpr (STAGE) {
+    const WinStage sg = win_stage_of(stg...);
+    const int64_t slot = (int64_t)n * gridDim.x + blockIdx.x;
+    int32_t* sc = sg.cells + slot * kCells2;
+    for (int i = threadIdx.x; i < C * cells; i += kBlock) sc[i] = win[i];
+    if (threadIdx.x == 0) {
+      int flags = bad ? 1 : 0;
+#pragma unroll
+      for (int w = 0; w < kBlock / 64; ++w) flags |= red[6][w] != 0 ? 2 : 0;
+      int32_t* h = sg.head + slot * kWinHead;
+      h[0] = bx0; h[1] = by0; h[2] = ww; h[3] = wh; h[4] = bx1; h[5] = by1; h[6] = __float_as_int(gmax); h[7] = flags;
+    }
+    return;
+  }
 
   // ---- 3. flush the non-zero cells (rows of the window are runs of consecutive addresses)
   for (int i = threadIdx.x; i < C * cells; i += kBlock) {
@@ -187,6 +232,162 @@ k_scatter_window2d(const float* __restrict__ gout, const float* __restrict__ in,
     const int c = i / cells, r = i - c * cells;
     const int wy = r / ww, wx = r - wy * ww;
     win_global_add<DET>(ginn, accn, (int64_t)c * V + (by0 + wy) * d.s2 + (bx0 + wx), fix_out((float)a, fs), sdet);
+  }
+}
+
+// The second launch of the staged form: one workgroup per 32 x 32 tile of grad_in pixels of one batch entry (thread <-> pixels
+// (lx, ly0 + 8 j), the layout of the sample tiles).
+//   scale   the entry's max |grad_out| from the tile headers (+inf if a tile saw a non-finite value): what k_det_absmax gives
+//           -- the tiles cover every sample of the entry, a dead sample counts as 0;
+//   cells   for every source tile whose capped window meets the rectangle, the staged cells of the intersection (runs of
+//           consecutive ints per window row), each non-zero cell as the 64-bit fixed point the twin's flush adds;
+//   capped  for a source tile that left valid corners outside its capped window and whose box meets the rectangle: its samples
+//           are walked again, the taps rebuilt, and exactly the corners the stage kernel left out are added as the twin adds
+//           them (64-bit integer atomics in LDS);
+//   store   fix_out of the integer sum, every pixel: grad_in is not zero-filled.
+// Integer sums: the order of the tiles and of the corners is free.  The headers are read 256 at a time and the ones that
+// matter compacted into LDS.
+template <int PAD, int C>
+__global__ void __launch_bounds__(kBlock)
+k_window_merge2d(const float* __restrict__ gout, const float* __restrict__ grid, float* __restrict__ gin, Dims d, int n2,
+                 int clamp_grid, WinStage sg) {
+  constexpr int kCells2 = C == 4 ? kWinCellsC4 : kWinCells;
+  constexpr int SPT = kWinT * kWinT / kBlock;
+  __shared__ unsigned long long cap[C * kWinT * kWinT];     // corners outside capped windows (rarely touched)
+  __shared__ int list[kBlock][kWinHead];
+  __shared__ int nlist;
+  __shared__ float wm[kBlock / 64];
+  const int V = (int)d.voxels();
+  const int T = gridDim.x, n = blockIdx.y;
+  const int rx0 = (blockIdx.x % n2) * kWinT, ry0 = (blockIdx.x / n2) * kWinT;
+  const int lx = threadIdx.x & 31, ly0 = threadIdx.x >> 5;
+  const int px = rx0 + lx;
+  const int32_t* hn = sg.head + (int64_t)n * T * kWinHead;
+  const int32_t* cn = sg.cells + (int64_t)n * T * kCells2;
+  const float* gn = grid + (int64_t)n * 2 * V;
+  const float* gon = gout + (int64_t)n * C * V;
+
+  // ---- scale of the entry
+  float m = 0.f;
+  bool bad = false;
+  for (int t = threadIdx.x; t < T; t += kBlock) {
+    m = fmaxf(m, __int_as_float(hn[t * kWinHead + 6]));
+    bad = bad || (hn[t * kWinHead + 7] & 1) != 0;
+  }
+  if (bad) m = __int_as_float(0x7f800000);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < kBlock / 64; ++w) m = fmaxf(m, wm[w]);
+  const FixScale sdet = fix_scale(m, kDetBits);
+
+  long long sum[SPT][C];
+#pragma unroll
+  for (int j = 0; j < SPT; ++j)
+#pragma unroll
+    for (int c = 0; c < C; ++c) sum[j][c] = 0;
+  bool used_cap = false;       // (the same in every thread)
+
+  for (int t0 = 0; t0 < T; t0 += kBlock) {
+    __syncthreads();           // the list of the previous round has been consumed
+    if (threadIdx.x == 0) nlist = 0;
+    __syncthreads();
+    if (t0 + (int)threadIdx.x < T) {
+      const int t = t0 + threadIdx.x;
+      const int4 a = *reinterpret_cast<const int4*>(hn + t * kWinHead), b = *reinterpret_cast<const int4*>(hn + t * kWinHead + 4);
+      const int bx0 = a.x, by0 = a.y, ww = a.z, wh = a.w, bx1 = b.x, by1 = b.y;
+      const bool meets = ww > 0 && wh > 0 && bx0 < rx0 + kWinT && bx0 + ww > rx0 && by0 < ry0 + kWinT && by0 + wh > ry0;
+      const bool walk = (b.w & 2) != 0 && bx0 < rx0 + kWinT && bx1 >= rx0 && by0 < ry0 + kWinT && by1 >= ry0;
+      if (meets || walk) {
+        int* e = list[atomicAdd(&nlist, 1)];
+        e[0] = bx0; e[1] = by0; e[2] = ww; e[3] = wh; e[4] = b.z; e[5] = t; e[6] = (meets ? 1 : 0) | (walk ? 2 : 0);
+      }
+    }
+    __syncthreads();
+    const int nl = nlist;
+    for (int k = 0; k < nl; ++k) {
+      const int bx0 = list[k][0], by0 = list[k][1], ww = list[k][2], wh = list[k][3], tile = list[k][5], what = list[k][6];
+      if (what & 1) {
+        const FixScale fs = fix_scale(__int_as_float(list[k][4]), 20);
+        const int32_t* sc = cn + (int64_t)tile * kCells2;
+        const int cells = ww * wh;
+        const int wx = px - bx0;
+        const bool okx = wx >= 0 && wx < ww;
+        int a[SPT][C];
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) {        // every load first, at an address that is valid whatever the pixel
+          const int wy = ry0 + ly0 + 8 * j - by0;
+          const bool ok = okx && wy >= 0 && wy < wh;
+          const int cell = ok ? wy * ww + wx : 0;
+#pragma unroll
+          for (int c = 0; c < C; ++c) {
+            const int v = sc[c * cells + cell];
+            a[j][c] = ok ? v : 0;
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < SPT; ++j)
+#pragma unroll
+          for (int c = 0; c < C; ++c) {
+            const long long q = __float2ll_rn(fix_in(fix_out((float)a[j][c], fs) * sdet.mul, sdet));   // (win_global_add<true>)
+            sum[j][c] += a[j][c] != 0 ? q : 0ll;                                                      // (the flush skips zeros)
+          }
+      }
+      if (what & 2) {
+        if (!used_cap) {
+          for (int i = threadIdx.x; i < C * kWinT * kWinT; i += kBlock) cap[i] = 0ull;
+          used_cap = true;
+          __syncthreads();
+        }
+        const int sx = (tile % n2) * kWinT + lx;
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) {
+          const int sy = (tile / n2) * kWinT + ly0 + 8 * j;
+          if (!(sx < d.s2 && sy < d.s1)) continue;
+          const int s = sy * d.s2 + sx;
+          float gx = gn[s], gy = gn[V + s];
+          if (clamp_grid) { gx = clamp_unit(gx); gy = clamp_unit(gy); }
+          Taps<2, PAD> t;
+          t.build(gx, gy, 0.f, d);
+          float go[C];
+#pragma unroll
+          for (int c = 0; c < C; ++c) go[c] = gon[(int64_t)c * V + s];
+          const int wx0 = t.x.i0 - bx0, wy0 = t.y.i0 - by0;
+          const bool inx[2] = {wx0 >= 0 && wx0 < ww, wx0 + 1 >= 0 && wx0 + 1 < ww};
+          const bool iny[2] = {wy0 >= 0 && wy0 < wh, wy0 + 1 >= 0 && wy0 + 1 < wh};
+#pragma unroll
+          for (int cy = 0; cy < 2; ++cy)
+#pragma unroll
+            for (int cx = 0; cx < 2; ++cx) {
+              if (!t.ok(0, cy, cx) || (inx[cx] && iny[cy])) continue;
+              const int qx = t.x.i0 + cx - rx0, qy = t.y.i0 + cy - ry0;
+              if (qx < 0 || qx >= kWinT || qy < 0 || qy >= kWinT) continue;     // another workgroup's pixel
+              const float w = t.w(0, cy, cx);
+#pragma unroll
+              for (int c = 0; c < C; ++c)
+                atomicAdd(cap + c * kWinT * kWinT + qy * kWinT + qx,
+                          (unsigned long long)__float2ll_rn(fix_in((w * go[c]) * sdet.mul, sdet)));
+            }
+        }
+      }
+    }
+  }
+  if (used_cap) __syncthreads();
+
+  // ---- store (k_det_convert)
+  float* ginn = gin + (int64_t)n * C * V;
+#pragma unroll
+  for (int j = 0; j < SPT; ++j) {
+    const int py = ry0 + ly0 + 8 * j;
+    if (!(px < d.s2 && py < d.s1)) continue;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      long long q = sum[j][c];
+      if (used_cap) q += (long long)cap[c * kWinT * kWinT + (ly0 + 8 * j) * kWinT + lx];
+      ginn[(int64_t)c * V + py * d.s2 + px] = fix_out((float)q, sdet);
+    }
   }
 }
 
@@ -445,11 +646,13 @@ using namespace advchain;
 // see scatter_tiled.hip).
 // det_ws (deterministic mode): the caller's advchain_scatter_workspace buffer; its tail holds the int64 image of grad_in and
 // the per-entry maxima -- three more launches (clear, maxima, convert), no float atomic between tiles.
+// stage_ws (deterministic mode, 2D, not SELF): advchain_window_stage_workspace ints -- the staged form instead: the stage
+// instantiation of k_scatter_window2d and k_window_merge2d, nothing cleared, no global atomic.
 // Returns ADVCHAIN_ERR_UNSUPPORTED for what the kernels do not cover (the caller keeps the owner-computes tiles).
 extern "C" int advchain_get_deterministic(void);
 int advchain_scatter_window_launch(bool self, const float* gout, const float* in, const float* grid, float* gin,
                                    float* ggrid, int64_t N, int64_t C, int ndim, Dims d, int padding, int clamp_grid,
-                                   int halo, int32_t* workspace, hipStream_t st, int32_t* det_ws) {
+                                   int halo, int32_t* workspace, hipStream_t st, int32_t* det_ws, int32_t* stage_ws) {
   static const bool off = getenv("ADVCHAIN_NO_WINDOW_SCATTER") != nullptr;   // A/B knob
   static const int min3 = 2;   // measured optimum (was a tuning knob until round 4)
   if (off || padding == PAD_REFLECTION) return ADVCHAIN_ERR_UNSUPPORTED;
@@ -458,6 +661,28 @@ int advchain_scatter_window_launch(bool self, const float* gout, const float* in
   if (ndim == 3 && (halo < 0 ? -halo : halo) < min3) return ADVCHAIN_ERR_UNSUPPORTED;
   const bool det = advchain_get_deterministic() != 0 && det_ws != nullptr;
   const int64_t V = d.voxels();
+  if (det && !self && ndim == 2 && stage_ws != nullptr) {   // staged form: two launches, no int64 image
+    const int n2 = (d.s2 + kWinT - 1) / kWinT, n1 = (d.s1 + kWinT - 1) / kWinT;
+    const int64_t tiles = (int64_t)n1 * n2;
+    const WinStage sg{stage_ws, stage_ws + N * tiles * kWinHead};
+    const dim3 g((unsigned)tiles, (unsigned)N), b(kBlock);
+    unsigned long long* const no_acc = nullptr;
+    const float* const no_max = nullptr;
+#define GO_ST(PAD_, C_) \
+  do { \
+    if (ggrid) hipLaunchKernelGGL((k_scatter_window2d<PAD_, C_, false, true, false, WinStage>), g, b, 0, st, gout, in, grid, gin, ggrid, d, n2, clamp_grid, workspace, no_acc, no_max, sg); \
+    else hipLaunchKernelGGL((k_scatter_window2d<PAD_, C_, false, false, false, WinStage>), g, b, 0, st, gout, in, grid, gin, ggrid, d, n2, clamp_grid, workspace, no_acc, no_max, sg); \
+    hipLaunchKernelGGL((k_window_merge2d<PAD_, C_>), g, b, 0, st, gout, grid, gin, d, n2, clamp_grid, sg); \
+  } while (0)
+#define GO_STC(PAD_) \
+  do { if (C == 1) GO_ST(PAD_, 1); else if (C == 2) GO_ST(PAD_, 2); else GO_ST(PAD_, 4); } while (0)
+    if (padding == PAD_BORDER) GO_STC(PAD_BORDER); else GO_STC(PAD_ZEROS);
+#undef GO_STC
+#undef GO_ST
+    ADVCHAIN_LAUNCH_CHECK();
+    advchain_set_route_(ADVCHAIN_ROUTE_WINDOW_STAGED);
+    return ADVCHAIN_OK;
+  }
   unsigned long long* acc64 = nullptr;
   float* maxn = nullptr;
   if (det) {
@@ -525,5 +750,12 @@ int advchain_scatter_window_launch(bool self, const float* gout, const float* in
                        maxn, gin, per_n);
   }
   ADVCHAIN_LAUNCH_CHECK();
+  advchain_set_route_(det ? ADVCHAIN_ROUTE_WINDOW_INT64 : ADVCHAIN_ROUTE_WINDOW_FLOAT);
   return ADVCHAIN_OK;
+}
+
+// int32 elements of the staging buffer of the staged form: a header and a window slot per sample tile and batch entry
+int64_t advchain_window_stage_ints(int64_t N, int64_t C, Dims d) {
+  const int64_t tiles = (int64_t)((d.s2 + kWinT - 1) / kWinT) * ((d.s1 + kWinT - 1) / kWinT);
+  return N * tiles * ((C == 4 ? kWinCellsC4 : kWinCells) + kWinHead);
 }

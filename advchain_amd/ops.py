@@ -192,6 +192,18 @@ FUSE_2D = True        # the leading sub-pixel squarings of a 2D chain in one lau
 COMPOSITE = True      # a paired 2D DemonsCompose direction as ONE C call (demons_compose.cpp: same launches); False: A/B tests
 RIDE_MASK = True      # the solver's validity mask rides through the data's warps (one launch for both); False: A/B tests
 RIDE_INTERPS = ("bilinear", "trilinear", "linear", "nearest")
+WINDOW_STAGED = True  # deterministic mode, 2D: the window scatter stages its windows and a merge kernel sums them (no int64 image:
+                      # scatter_window.hip); False: the int64 twin, bit for bit the same results.  Read at every call: tests and
+                      # tools compare the two forms in one process
+WINDOW_STAGED_CHANNELS = (1, 2, 4)   # the channel counts that take the staged form (measured: profiles/r14/window_staged)
+
+# advchain_last_bwd_route (include/advchain_hip.h: ADVCHAIN_ROUTE_*)
+BWD_ROUTES = ("none", "general", "rows", "gather", "march", "window_float", "window_int64", "window_staged", "tiled")
+
+
+def last_bwd_route():
+    """Which formulation the last raw_grid_sample_bwd of this thread ended in (a host-side note of the launcher)."""
+    return BWD_ROUTES[_lib.load().advchain_last_bwd_route()]
 
 
 def set_deterministic(on):
@@ -244,6 +256,16 @@ def raw_grid_sample_bwd(gout, inp, grid, interp, padding, clamp_grid, need_gin, 
     ws = _scatter_workspace(N, inp.shape[2:], inp.device) if tiled else None
     gin = (torch.empty_like(inp) if tiled else torch.zeros_like(inp)) if need_gin else None
     ggrid = torch.empty_like(grid) if need_ggrid else None
+    if (tiled and WINDOW_STAGED and nd == 2 and C in WINDOW_STAGED_CHANNELS and is_deterministic()
+            and not _general_warp_kernel(C, interp, inp.shape[2:], grid.shape[2:])):
+        lib = _lib.load()
+        n = lib.advchain_window_stage_workspace(N, C, nd, _lib.dims_array(inp.shape[2:]))
+        stage = torch.empty(max(4, n), device=inp.device, dtype=torch.int32)       # (not initialised: the stage kernel fills what the merge reads)
+        _lib.check(lib.advchain_grid_sample_bwd_staged(_ptr(gout), _ptr(inp), _ptr(grid), _ptr(gin), _ptr(ggrid), _ptr(ws),
+                                                       N, C, nd, _lib.dims_array(inp.shape[2:]),
+                                                       _lib.dims_array(grid.shape[2:]), interp, padding, int(clamp_grid),
+                                                       int(halo), _stream(), _ptr(stage)), "grid_sample_bwd_staged")
+        return gin, ggrid
     _lib.check(_lib.load().advchain_grid_sample_bwd(_ptr(gout), _ptr(inp), _ptr(grid), _ptr(gin), _ptr(ggrid), _ptr(ws),
                                                     N, C, nd, _lib.dims_array(inp.shape[2:]),
                                                     _lib.dims_array(grid.shape[2:]), interp, padding, int(clamp_grid),

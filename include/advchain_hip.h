@@ -122,6 +122,38 @@ int advchain_grid_sample_bwd(const float* grad_out, const float* in, const float
  * grad_in is overwritten (no pre-zeroing); grad_grid is bit for bit what advchain_grid_sample_bwd's general kernel writes.
  * Works whatever advchain_get_deterministic() says -- the switch is consulted by the Python layer, not here.  Four launches
  * (clear, maxima, scatter, convert), all kernels.                                                                    */
+/* advchain_grid_sample_bwd with a staging buffer for its source-tiled window scatter: the same checks and the same routing
+ * (whole-row scatter -> gather form -> window scatter -> tiles).
+ * replaces: the same grid_sampler_2d_backward.  In deterministic mode the window route of advchain_grid_sample_bwd clears an
+ *           int64 image of grad_in, takes a maximum of grad_out per entry, flushes its LDS windows with 64-bit integer atomics
+ *           and converts the image.  With `stage_ws` (int32[advchain_window_stage_workspace(N, C, ndim, in_dims)], 16-byte
+ *           aligned, not initialised) and ndim == 2 it takes the STAGED form instead: the window kernel stores every tile's
+ *           window (32-bit cells at the tile's scale) and a header in a slot of its own, and a merge kernel -- one workgroup
+ *           per 32 x 32 tile of grad_in -- takes the entry's maximum from the headers, sums the staged cells that cover its
+ *           pixels as 64-bit fixed point in registers and stores every pixel.  Two launches, no clear, no global atomic;
+ *           grad_in and grad_grid are bit for bit those of the int64 twin, for any field (the corners a tile's capped window
+ *           leaves out are rebuilt by the merge kernel and rounded as the twin rounds them).
+ * The staged form is taken only in deterministic mode; stage_ws == NULL, ndim == 3 or the default mode give
+ * advchain_grid_sample_bwd itself.  The size query is host-only and independent of the switch: tiles * (8 + 8192) ints per
+ * entry (tiles of 32 x 32 samples; 12288 for C == 4), 0 where the form does not exist (3D, C not in {1, 2, 4}), -1 for bad
+ * arguments.  advchain_scatter_workspace keeps its sizes.                                                                 */
+int64_t advchain_window_stage_workspace(int64_t N, int64_t C, int ndim, const int64_t* in_dims); /* int32 elements */
+int advchain_grid_sample_bwd_staged(const float* grad_out, const float* in, const float* grid, float* grad_in,
+                                    float* grad_grid, int32_t* workspace, int64_t N, int64_t C, int ndim,
+                                    const int64_t* in_dims, const int64_t* out_dims, int interp, int padding, int clamp_grid,
+                                    int halo, void* stream, int32_t* stage_ws);
+/* The formulation the last advchain_grid_sample_bwd / advchain_grid_sample_bwd_staged call of THIS THREAD ended in, noted on the
+ * host by the launcher (nothing on the device): tests and tools use it to show which kernel a case ran.                   */
+#define ADVCHAIN_ROUTE_NONE 0
+#define ADVCHAIN_ROUTE_GENERAL 1        /* the general float-atomic kernel */
+#define ADVCHAIN_ROUTE_ROWS 2           /* 2D whole-row owner-computes scatter */
+#define ADVCHAIN_ROUTE_GATHER 3         /* gather-form adjoint */
+#define ADVCHAIN_ROUTE_MARCH 4          /* 3D owner-computes march */
+#define ADVCHAIN_ROUTE_WINDOW_FLOAT 5   /* window scatter, float-atomic flush */
+#define ADVCHAIN_ROUTE_WINDOW_INT64 6   /* window scatter, int64 image (deterministic mode) */
+#define ADVCHAIN_ROUTE_WINDOW_STAGED 7  /* window scatter, staged windows + merge (deterministic mode, 2D) */
+#define ADVCHAIN_ROUTE_TILED 8          /* LDS-tiled owner-computes scatter */
+int advchain_last_bwd_route(void);
 int64_t advchain_det_warp_workspace(int64_t N, int64_t C, int ndim, const int64_t* in_dims); /* int32 elements */
 int advchain_grid_sample_bwd_det(const float* grad_out, const float* in, const float* grid, float* grad_in,
                                  float* grad_grid, int32_t* det_ws, int64_t N, int64_t C, int ndim,
