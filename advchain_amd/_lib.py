@@ -98,6 +98,13 @@ PROTOTYPES = {
     "advchain_jacobian_det2d_fwd": (_I, [_P, _P, _L, _P, _P]),
     "advchain_jacobian_det2d_bwd": (_I, [_P, _P, _P, _L, _P, _P]),
     "advchain_expo_start": (_I, [_P, _P, _F, _L, _I, _P, _P]),
+    "advchain_image_diff3d_fwd": (_I, [_P, _P, _P, _P, _L, _L, _P, _P]),
+    "advchain_image_diff3d_bwd": (_I, [_P, _P, _P, _P, _L, _L, _P, _P]),
+    "advchain_jacobian_det_fwd": (_I, [_P, _P, _L, _I, _P, _I, _P]),
+    "advchain_jacobian_det_bwd": (_I, [_P, _P, _P, _P, _L, _I, _P, _I, _P]),
+    "advchain_jacobian_det_workspace": (_L, [_L, _I, _P]),
+    "advchain_jacobian_stats_workspace": (_L, [_L, _I, _P]),
+    "advchain_jacobian_stats": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _P, _I, _P]),
     "advchain_sumsq_ordered": (_I, [_P, _L, _P, _P, _P]),
     "advchain_bicubic2d_det_workspace": (_L, [_L, _L, _P]),
     "advchain_grid_sample_bicubic2d_bwd_det": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _P, _P, _I, _P]),

@@ -41,6 +41,35 @@ def calculate_jacobian_determinant(data, type='displacement'):
     return ops.jacobian_det2d(data)
 
 
+_JACOBIAN_TYPES = ['displacement', 'positions']
+
+
+def calculate_image_diff3D(images):
+    """(dx, dy, dz) of a (N,C,S0,S1,S2) batch: the stencil of calculate_image_diff on every axis; x runs along the last axis,
+    z along the first.  Not in the reference (its helper asserts 2D).  advchain_image_diff3d_fwd / _bwd."""
+    assert len(images.size()) == 5, 'only support 3D version, NCDHW'
+    return ops.image_diff3d(images)
+
+
+def calculate_jacobian_determinant3D(data, type='displacement'):
+    """Determinant of the 3 x 3 Jacobian of a (N,3,S0,S1,S2) field per voxel -> (N,1,S0,S1,S2); channel 0 is the component
+    along the last axis.  'displacement': J = I + D f.  'positions': `data` is a sampling grid in normalised coordinates
+    (align_corners=True) and J is in voxel units (the identity grid gives 1).  advchain_jacobian_det_fwd / _bwd."""
+    assert len(data.size()) == 5 and data.size(1) == 3, 'only support 3D version, and transformation format is NCDHW'
+    assert type in _JACOBIAN_TYPES, 'only support {} but found: {}'.format(_JACOBIAN_TYPES, type)
+    return ops.jacobian_det(data, positions=(type == 'positions'))
+
+
+def jacobian_folding_stats(data, type='displacement'):
+    """Does the (N,2,H,W) or (N,3,S0,S1,S2) field fold?  Per batch entry, without the determinant map: a named tuple (neg,
+    nonpos, min, max) of device tensors -- the counts of det < 0 and of not (det > 0) (exact zeros and NaN count) and the
+    extrema of the determinants that are numbers.  advchain_jacobian_stats."""
+    assert len(data.size()) in (4, 5) and data.size(1) == len(data.size()) - 2, \
+        'only support (N,2,H,W) and (N,3,D,H,W) transformations'
+    assert type in _JACOBIAN_TYPES, 'only support {} but found: {}'.format(_JACOBIAN_TYPES, type)
+    return ops.jacobian_stats(data, positions=(type == 'positions'))
+
+
 def integrate_by_add(basegrid, dxy):
     """basegrid += dxy in place; returns basegrid itself (adv_morph.py:103-113)."""
     basegrid += dxy
@@ -315,6 +344,22 @@ class AdvMorph(AdvTransformBase):
         dxy = self.DemonsCompose(duv=duv)
         perm = (0, 2, 3, 1) if self.spatial_dims == 2 else (0, 2, 3, 4, 1)
         return dxy, dxy.permute(*perm) - self.base_grid.permute(*perm)
+
+    def _sampled_grid(self, inverse):
+        if self.param is None:
+            self.param = self.init_parameters()
+        return self._field(-1.0 if inverse else +1.0)
+
+    def jacobian_determinant(self, inverse=False):
+        """det J, in voxel units, of the map forward() samples with (inverse=True: backward()'s) -> (N,1,...): the grid of the
+        current parameters clamped to [-1, 1] (the clamp is applied by the kernel as it loads, as the sampler does).
+        Differentiable with respect to `param` when it requires grad."""
+        return ops.jacobian_det(self._sampled_grid(inverse), positions=True, clamp=True)
+
+    def folding_stats(self, inverse=False):
+        """(neg, nonpos, min, max) per batch entry of jacobian_determinant(inverse), without the map and without a read-back."""
+        with torch.no_grad():
+            return ops.jacobian_stats(self._sampled_grid(inverse), positions=True, clamp=True)
 
     @property
     def displacement(self):

@@ -28,6 +28,7 @@ PER_FILE_FLAGS = {
     "adjoint_fused2d.hip": ["-fno-slp-vectorize"],      # (the same code generation as the per-squaring gather form: bit-identical results)
     "fields.hip": ["-fno-slp-vectorize"],
     "deform_diff.hip": ["-ffp-contract=off"],           # one rounding per ATen op of the reference (bitwise forwards)
+    "jacobian.hip": ["-ffp-contract=off"],              # the same stencils and determinant: map and statistics agree bitwise
 }
 if os.environ.get("ADVCHAIN_BUILD_SLP_EVERYWHERE"):     # A/B knob: the compiler default for every source
     PER_FILE_FLAGS = {}

@@ -4,6 +4,7 @@ Every operator requires CUDA(ROCm) fp32 tensors and the built ``libadvchain_hip.
 PyTorch / CPU fallback -- a CPU tensor or a missing library raises.  PyTorch is used for device
 memory (``torch.empty``), the current stream and the autograd tape only.
 """
+import collections
 import ctypes
 import functools
 import os
@@ -2195,6 +2196,126 @@ class _JacobianDet2D(torch.autograd.Function):
 def jacobian_det2d(field):
     _check_planes(field, "calculate_jacobian_determinant")
     return _JacobianDet2D.apply(field)
+
+
+# ---- 3D differences, the Jacobian determinant in 2D / 3D and its folding statistics (jacobian.hip) ----
+JACOBIAN_COLS = 62           # output columns of one wave (diff_stencil.h: kCols)
+JACOBIAN_ROWS_MIN = 4        # rows of one wave's strip: 32, halved down to this while the launch has few waves
+JACOBIAN_ROWS_MAX = 32
+JACOBIAN_POSITIONS, JACOBIAN_CLAMP = 1, 2        # mode bits of include/advchain_hip.h
+
+JacobianStats = collections.namedtuple("JacobianStats", ["neg", "nonpos", "min", "max"])
+
+
+def _check_axes(x, what):
+    """Every spatial axis of at least 2 elements, as `_check_planes`: the one-sided stencils index element 1."""
+    for ax in range(x.dim() - 1, 1, -1):
+        if x.shape[ax] < 2:
+            raise IndexError("%s: index 1 is out of bounds for dimension %d with size %d" % (what, ax, x.shape[ax]))
+
+
+def _jacobian_mode(positions, clamp):
+    if clamp and not positions:
+        raise ValueError("clamp=True clamps a sampling grid to [-1, 1]: it needs positions=True")
+    return (JACOBIAN_POSITIONS if positions else 0) | (JACOBIAN_CLAMP if clamp else 0)
+
+
+class _ImageDiff3D(torch.autograd.Function):
+    """(N,C,S0,S1,S2) -> (dx along S2, dy along S1, dz along S0), the stencil of calculate_image_diff on every axis."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = _dev(x, "images")
+        N, C = x.shape[:2]
+        dx, dy, dz = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+        _lib.check(_lib.load().advchain_image_diff3d_fwd(_ptr(x), _ptr(dx), _ptr(dy), _ptr(dz), N, C,
+                                                         _lib.dims_array(x.shape[2:]), _stream()), "image_diff3d_fwd")
+        ctx.set_materialize_grads(False)
+        ctx.shape = tuple(x.shape)
+        return dx, dy, dz
+
+    @staticmethod
+    def backward(ctx, gdx, gdy, gdz):
+        grads = [None if g is None else _dev(g, "grad") for g in (gdx, gdy, gdz)]
+        first = next((g for g in grads if g is not None), None)
+        if first is None:
+            return None
+        N, C = ctx.shape[:2]
+        gin = torch.empty(ctx.shape, device=first.device, dtype=torch.float32)
+        _lib.check(_lib.load().advchain_image_diff3d_bwd(_ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(gin), N, C,
+                                                         _lib.dims_array(ctx.shape[2:]), _stream()), "image_diff3d_bwd")
+        return gin
+
+
+@_on_tensor_device
+def image_diff3d(x):
+    """(dx, dy, dz) of a (N,C,S0,S1,S2) fp32 GPU tensor: x runs along the last axis, z along the first."""
+    assert x.dim() == 5, 'image_diff3d takes (N,C,S0,S1,S2)'
+    _check_axes(x, "image_diff3d")
+    return _ImageDiff3D.apply(x)
+
+
+class _JacobianDet(torch.autograd.Function):
+    """(N,d,...) field -> (N,1,...) determinant, d = 2 or 3; only the field is saved, the backward recomputes."""
+
+    @staticmethod
+    def forward(ctx, field, mode):
+        field = _dev(field, "data")
+        N, nd = field.shape[0], field.dim() - 2
+        det = torch.empty((N, 1) + tuple(field.shape[2:]), device=field.device, dtype=torch.float32)
+        _lib.check(_lib.load().advchain_jacobian_det_fwd(_ptr(field), _ptr(det), N, nd, _lib.dims_array(field.shape[2:]), mode,
+                                                         _stream()), "jacobian_det_fwd")
+        ctx.save_for_backward(field)
+        ctx.mode = mode
+        return det
+
+    @staticmethod
+    def backward(ctx, g):
+        field, = ctx.saved_tensors
+        g = _dev(g, "grad")
+        N, nd = field.shape[0], field.dim() - 2
+        lib, dims = _lib.load(), _lib.dims_array(field.shape[2:])
+        n_ws = int(lib.advchain_jacobian_det_workspace(N, nd, dims))
+        ws = torch.empty(n_ws, device=field.device, dtype=torch.float32) if n_ws > 0 else None
+        gfield = torch.empty_like(field)
+        _lib.check(lib.advchain_jacobian_det_bwd(_ptr(g), _ptr(field), _ptr(gfield), _ptr(ws), N, nd, dims, ctx.mode, _stream()),
+                   "jacobian_det_bwd")
+        return gfield, None
+
+
+def _check_field(field, what):
+    assert field.dim() in (4, 5) and field.shape[1] == field.dim() - 2, \
+        '%s takes a (N,2,H,W) or (N,3,S0,S1,S2) field, got %s' % (what, tuple(field.shape))
+    _check_axes(field, what)
+
+
+@_on_tensor_device
+def jacobian_det(field, positions=False, clamp=False):
+    """Determinant of the Jacobian of a 2D or 3D field per voxel, (N,1,...).  Displacement: J = I + D f.  positions=True: the
+    field is a sampling grid in normalised coordinates (align_corners=True) and J is in voxel units; clamp=True clamps it to
+    [-1, 1] as it is read (the grid a clamped warp samples).  Channel 0 runs along the last axis."""
+    _check_field(field, "jacobian_det")
+    return _JacobianDet.apply(field, _jacobian_mode(positions, clamp))
+
+
+@_on_tensor_device
+def jacobian_stats(field, positions=False, clamp=False):
+    """Folding statistics of `jacobian_det(field, ...)` per batch entry without the map: JacobianStats(neg, nonpos, min, max)
+    -- int64 counts of det < 0 and of not (det > 0) (zeros and NaN count), fp32 extrema over the determinants that are numbers.
+    Four device tensors of N elements; nothing is read back."""
+    _check_field(field, "jacobian_stats")
+    mode = _jacobian_mode(positions, clamp)
+    field = _dev(field.detach(), "data")
+    N, nd = field.shape[0], field.dim() - 2
+    neg = torch.empty(N, device=field.device, dtype=torch.int64)
+    nonpos = torch.empty(N, device=field.device, dtype=torch.int64)
+    mn = torch.empty(N, device=field.device, dtype=torch.float32)
+    mx = torch.empty(N, device=field.device, dtype=torch.float32)
+    lib, dims = _lib.load(), _lib.dims_array(field.shape[2:])
+    ws = torch.empty(max(int(lib.advchain_jacobian_stats_workspace(N, nd, dims)), 4), device=field.device, dtype=torch.float32)
+    _lib.check(lib.advchain_jacobian_stats(_ptr(field), _ptr(neg), _ptr(nonpos), _ptr(mn), _ptr(mx), _ptr(ws), N, nd, dims, mode,
+                                           _stream()), "jacobian_stats")
+    return JacobianStats(neg, nonpos, mn, mx)
 
 
 def raw_expo_start(duv, inv):

@@ -734,6 +734,44 @@ int advchain_expo_start(const float* duv, float* phi0, float inv, int64_t N, int
 #define ADVCHAIN_SUMSQ_PARTIALS 1024
 int advchain_sumsq_ordered(const float* x, int64_t n, float* partials, float* out, void* stream);
 
+/* ---- Jacobian determinant and folding statistics in 2D and 3D (jacobian.hip) ------------------------------------------------
+ * Not in the reference (its helpers assert 2D displacement fields).  Fields are (N, ndim, dims), fp32, contiguous; `dims` is
+ * the spatial sizes in memory order, every one at least 2; channel c is the component along the axis dims[ndim - 1 - c] (channel
+ * 0 runs along the last axis: the convention of the sampling grids).  D_j is the stencil of calculate_image_diff along axis j.
+ * `mode`:  0                                        displacement: J_ij = delta_ij + D_j f_i
+ *          ADVCHAIN_JACOBIAN_POSITIONS              the field is a sampling grid q in normalised [-1, 1] coordinates,
+ *                                                   align_corners=True: J_ij = ((S_i - 1) / 2) D_j q_i, in voxel units (the
+ *                                                   identity grid gives J = I)
+ *          ADVCHAIN_JACOBIAN_POSITIONS | _CLAMP     q clamped to [-1, 1] as it is loaded -- what grid_sample(clamp_grid=True)
+ *                                                   samples; the gradient passes where -1 <= q <= 1 (torch.clamp)
+ * (the clamp without positions is refused.)  The file is compiled without contraction; the map and the statistics evaluate the
+ * determinant with one device function, so the statistics are those of the map bit for bit.                               */
+#define ADVCHAIN_JACOBIAN_POSITIONS 1
+#define ADVCHAIN_JACOBIAN_CLAMP 2
+/* in (N,C,S0,S1,S2) -> dx (along S2), dy (along S1), dz (along S0): 4 B read + 12 B written per element.                    */
+int advchain_image_diff3d_fwd(const float* in, float* dx, float* dy, float* dz, int64_t N, int64_t C, const int64_t* dims,
+                              void* stream);
+/* its adjoint in gather form: grad_in = Dx^T grad_dx + Dy^T grad_dy + Dz^T grad_dz; any of the three may be NULL (zero), not all. */
+int advchain_image_diff3d_bwd(const float* grad_dx, const float* grad_dy, const float* grad_dz, float* grad_in, int64_t N,
+                              int64_t C, const int64_t* dims, void* stream);
+/* det (N,1,dims) of field (N,ndim,dims), ndim 2 or 3.  ndim == 2 with mode 0 IS advchain_jacobian_det2d_fwd.                */
+int advchain_jacobian_det_fwd(const float* field, float* det, int64_t N, int ndim, const int64_t* dims, int mode, void* stream);
+/* grad f_i = s_i sum_j D_j^T (grad_det cof_ij), cofactors recomputed from `field` at the neighbours (gather form, no atomics:
+ * two calls give the same bits).  `workspace`: advchain_jacobian_det_workspace floats, or NULL when that is 0 -- it is 0 for
+ * every shape today (nothing is staged).  ndim == 2 with mode 0 IS advchain_jacobian_det2d_bwd.                             */
+int advchain_jacobian_det_bwd(const float* grad_det, const float* field, float* grad_field, float* workspace, int64_t N,
+                              int ndim, const int64_t* dims, int mode, void* stream);
+int64_t advchain_jacobian_det_workspace(int64_t N, int ndim, const int64_t* dims); /* floats; host-only query */
+/* One pass over the field, no determinant map.  Per batch entry n: neg[n] = #(det < 0), nonpos[n] = #(!(det > 0)) -- exact zeros
+ * and NaN count, so a broken field cannot look clean; min[n], max[n] over the determinants that are numbers (NaN ignored; +inf
+ * and -inf when there is none).  Every wave writes one partial into `workspace` (advchain_jacobian_stats_workspace floats,
+ * 16-byte aligned; host-only query, -1 for bad sizes; no clearing needed) and one workgroup per entry folds them: integer sums
+ * and min / max, no atomics -- bit-reproducible, and every output is written by a kernel of this call (no memset node under
+ * capture).                                                                                                                 */
+int64_t advchain_jacobian_stats_workspace(int64_t N, int ndim, const int64_t* dims); /* floats */
+int advchain_jacobian_stats(const float* field, int64_t* neg, int64_t* nonpos, float* min, float* max, float* workspace,
+                            int64_t N, int ndim, const int64_t* dims, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
