@@ -42,6 +42,10 @@ PROTOTYPES = {
     "advchain_band_reduce_rows_dense": (_I, [_P, _P, _P, _P, _P, _L, _L, _L, _L, _F, _P]),
     "advchain_bias_field_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _F, _I, _F, _P]),
     "advchain_bias_field_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _F, _I, _F, _P]),
+    "advchain_bias_rows_per_wg": (_I, [_P, _L]),
+    "advchain_bias_field_fwd_rows": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _F, _I, _F, _I, _P]),
+    "advchain_bias_field_bwd_rows": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _F, _I, _F, _I, _P]),
+    "advchain_bias_field_bwd_reduced": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _F, _I, _F, _P, _P, _L, _I, _P]),
     "advchain_gauss_axis": (_I, [_P, _P, _P, _L, _L, _I, _P, _I, _P, _I, _I, _F, _P]),
     "advchain_gauss_axis_generic": (_I, [_P, _P, _L, _I, _P, _I, _P, _I, _F, _P]),
     "advchain_max_displacement": (_I, [_P, _P, _L, _I, _P, _P]),

@@ -759,14 +759,17 @@ __device__ __forceinline__ float bias_value(float L, int use_log, float eps, flo
   return 1.f + fminf(fmaxf(b, -eps), eps);   // adv_bias.py:352-353
 }
 
-// grid = (i1 chunks, S0, N)
+// The bias kernels take their i1 rows per workgroup at run time (`rows` in {4, 8, 16, 32}, bias_rows_rule below): with the
+// kTpChunk = 32 of the interpolation kernels a 32 x 256 x 256 launch was 256 workgroups, one a CU (16.4 us; 14.4 us with two).
+// A voxel's value depends on its row's blend and its column's band, not on the workgroup that computes it: same bits.
+// grid = (ceil(S1 / rows), S0, N)
 template <int VEC>
 __global__ void __launch_bounds__(kBlock)
 k_bias_fwd(const float* __restrict__ cp, const float* __restrict__ data, float* __restrict__ out,
-           float* __restrict__ field, BandTables T, Dims full, int C, float eps, int use_log, float cp_scale) {
+           float* __restrict__ field, BandTables T, Dims full, int C, float eps, int use_log, float cp_scale, int rows) {
   __shared__ float lds[kTpMaxLds];
   const int n = blockIdx.z, i0 = blockIdx.y;
-  const int i1b = blockIdx.x * kTpChunk, i1e = min(i1b + kTpChunk, full.s1);
+  const int i1b = blockIdx.x * rows, i1e = min(i1b + rows, full.s1);
   const int64_t G = (int64_t)T.a[0].g * T.a[1].g * T.a[2].g;
   const int V = (int)full.voxels();
   tp_rows<VEC>(cp + (int64_t)n * G, T, full, i0, i1b, i1e, lds, [&](int i1, int x, const float (&val)[VEC]) {
@@ -792,17 +795,43 @@ k_bias_fwd(const float* __restrict__ cp, const float* __restrict__ data, float* 
   });
 }
 
-// gL = dLoss/dL (full res, one channel); gdata optional.  grid = (i1 chunks, S0, N)
-template <int VEC>
+// gL = dLoss/dL (full res, one channel); gdata optional.  grid = (ceil(S1 / rows), S0, N)
+//
+// RED (advchain_bias_field_bwd_reduced): gL is not written.  The workgroup owns whole rows, so it keeps them in an LDS slab
+// [rows][S2 + 1] (the pitch of k_band_reduce_rows_dense) and reduces them along x itself: t1[row][k] = sum_j x[lo[k] + j] *
+// Wd[k][j], one fma chain per (row, k) in ascending j -- the sums of k_band_reduce_rows_dense in its order, so the same bits,
+// without the 4 V bytes written and read back in between and without that launch.  The dense table and lo[] are requested
+// with the first loads of the kernel and put into LDS after tp_rows' last barrier.  Dynamic LDS: Wd[g2 * WB] (rounded up to
+// 4 floats), then the slab.  VEC = 4 only.
+constexpr int kBiasRedWq = kBrMaxW / 4 / kBlock;      // float4 of the dense table per thread at most
+template <int VEC, bool RED>
 __global__ void __launch_bounds__(kBlock)
 k_bias_bwd(const float* __restrict__ cp, const float* __restrict__ data, const float* __restrict__ gout,
            float* __restrict__ gL, float* __restrict__ gdata, BandTables T, Dims full, int C, float eps, int use_log,
-           float cp_scale) {
+           float cp_scale, int rows, float* __restrict__ t1, const float* __restrict__ wd, const int* __restrict__ lo_g, int WB) {
   __shared__ float lds[kTpMaxLds];
+  extern __shared__ __attribute__((aligned(16))) float red_lds[];
+  __shared__ int lo_s[64];
   const int n = blockIdx.z, i0 = blockIdx.y;
-  const int i1b = blockIdx.x * kTpChunk, i1e = min(i1b + kTpChunk, full.s1);
+  const int i1b = blockIdx.x * rows, i1e = min(i1b + rows, full.s1);
   const int64_t G = (int64_t)T.a[0].g * T.a[1].g * T.a[2].g;
   const int V = (int)full.voxels();
+  const int g2 = T.a[2].g;
+  const int nw = RED ? g2 * WB : 0;
+  const int pitch = full.s2 + 1;
+  float* Wd = red_lds;
+  float* slab = red_lds + ((nw + 3) & ~3);
+  const bool wvec = (nw & 3) == 0 && (reinterpret_cast<uintptr_t>(wd) & 15) == 0;
+  float4 wq[kBiasRedWq];
+  int lo_r = 0;
+  if constexpr (RED) {
+#pragma unroll
+    for (int u = 0; u < kBiasRedWq; ++u) {
+      const int idx = threadIdx.x + kBlock * u;
+      wq[u] = wvec && 4 * idx < nw ? *reinterpret_cast<const float4*>(wd + 4 * idx) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if (threadIdx.x < g2) lo_r = lo_g[threadIdx.x];
+  }
   tp_rows<VEC>(cp + (int64_t)n * G, T, full, i0, i1b, i1e, lds, [&](int i1, int x, const float (&val)[VEC]) {
     const int v = (i0 * full.s1 + i1) * full.s2 + x;
     float b[VEC], e[VEC], sgo[VEC];
@@ -821,13 +850,53 @@ k_bias_bwd(const float* __restrict__ cp, const float* __restrict__ data, const f
       for (int q = 0; q < VEC; ++q) { sgo[q] += go[q] * dv[q]; go[q] *= b[q]; }
       if (gdata) store_vec<VEC>(gdata + o, go);
     }
-    if (gL) {
+    if (RED || gL) {
       float gl[VEC];
 #pragma unroll
       for (int q = 0; q < VEC; ++q) gl[q] = pass[q] ? sgo[q] * (use_log ? e[q] : 1.f) * cp_scale : 0.f;
-      store_vec<VEC>(gL + (int64_t)n * V + v, gl);
+      if constexpr (RED) {
+        float* dst = slab + (i1 - i1b) * pitch + x;      // (rows are S2 + 1 apart: dword stores)
+#pragma unroll
+        for (int q = 0; q < VEC; ++q) dst[q] = gl[q];
+      } else {
+        store_vec<VEC>(gL + (int64_t)n * V + v, gl);
+      }
     }
   });
+  if constexpr (RED) {
+    // (tp_rows ends with a barrier: the slab is complete)
+    if (wvec) {
+#pragma unroll
+      for (int u = 0; u < kBiasRedWq; ++u) {
+        const int idx = threadIdx.x + kBlock * u;
+        if (4 * idx < nw) *reinterpret_cast<float4*>(Wd + 4 * idx) = wq[u];
+      }
+    } else {
+      for (int i = threadIdx.x; i < nw; i += kBlock) Wd[i] = wd[i];
+    }
+    if (threadIdx.x < g2) lo_s[threadIdx.x] = lo_r;
+    __syncthreads();
+    const int nrow = i1e - i1b, S2 = full.s2;
+    for (int e = threadIdx.x; e < nrow * g2; e += kBlock) {
+      const int r = e % nrow, k = e / nrow;
+      const float* x = slab + r * pitch;
+      const float* w = Wd + k * WB;
+      const int lo = lo_s[k];
+      float a = 0.f;
+      int j = 0;
+      // sixteen taps requested before the first is used: one chain, ascending j, the LDS round trips overlap.  A tap beyond
+      // the row (lo + j >= S2) carries weight 0 in Wd; its index is clamped into the row as in k_band_reduce_rows_dense.
+      for (; j + 16 <= WB; j += 16) {
+        float xv[16], cv[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) { xv[u] = x[min(lo + j + u, S2 - 1)]; cv[u] = w[j + u]; }
+#pragma unroll
+        for (int u = 0; u < 16; ++u) a = fmaf(xv[u], cv[u], a);
+      }
+      for (; j < WB; ++j) a = fmaf(x[min(lo + j, S2 - 1)], w[j], a);
+      t1[(((int64_t)n * full.s0 + i0) * full.s1 + i1b + r) * g2 + k] = a;
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1702,24 +1771,82 @@ int advchain_band_reduce_rows_dense(const float* in, const float* in2, float* ou
   return ADVCHAIN_OK;
 }
 
-int advchain_bias_field_fwd(const float* cp, const float* data, float* out, float* field, const int32_t* itab,
-                            const float* ftab, const int64_t* S, const int64_t* g, const int64_t* B, int64_t N,
-                            int64_t C, float eps, int use_log, float cp_scale, void* stream) {
+// i1 rows per workgroup of the bias kernels: the largest of 32, 16, 8, 4 that still gives the launch kBiasMinWg workgroups (two
+// on each of 256 CUs), else 4.  Measured (profiles/r16/bias_rows): a workgroup's prologue -- the row tables, and per thread the
+// start and the weights of its four columns, 20 vector loads -- costs as much as about seven rows of the forward's epilogue, so
+// fewer rows a workgroup is more prologue per byte: at 32 x 256 x 256 the forward takes 16.3 / 14.4 / 16.6 / 25.7 us at 32 / 16 /
+// 8 / 4 rows (256 / 512 / 1024 / 2048 workgroups), at 4 x 128 x 128 x 64 30.8 / 49.4 / 91.7 / 174.7 us (2048 .. 16384).  One
+// workgroup a CU is the only grid that more workgroups beat.
+constexpr int64_t kBiasMinWg = 512;
+static int bias_rows_rule(int64_t S0, int64_t S1, int64_t N) {
+  for (int rows = 32; rows > 4; rows /= 2)
+    if (((S1 + rows - 1) / rows) * S0 * N >= kBiasMinWg) return rows;
+  return 4;
+}
+static inline bool bias_rows_ok(int rows) { return rows == 0 || rows == 4 || rows == 8 || rows == 16 || rows == 32; }
+
+// Host-only: the rows per workgroup that rows_per_wg = 0 stands for in the entries below.  S: 3 entries (2D: a leading 1).
+int advchain_bias_rows_per_wg(const int64_t* S, int64_t N) {
+  if (!S || N < 0 || N >= 65536 || S[0] < 1 || S[1] < 1 || S[2] < 1) return -1;
+  return bias_rows_rule(S[0], S[1], N);
+}
+
+int advchain_bias_field_fwd_rows(const float* cp, const float* data, float* out, float* field, const int32_t* itab,
+                                 const float* ftab, const int64_t* S, const int64_t* g, const int64_t* B, int64_t N,
+                                 int64_t C, float eps, int use_log, float cp_scale, int rows_per_wg, void* stream) {
   ADVCHAIN_CHECK_ARG(cp && field && itab && ftab && (!data || out), "bias_field_fwd: null pointer");
+  ADVCHAIN_CHECK_ARG(S && g && B, "bias_field_fwd: null dims");
   ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && C >= 1, "bias_field_fwd: bad N/C");
+  ADVCHAIN_CHECK_ARG(bias_rows_ok(rows_per_wg), "bias_field_fwd: rows_per_wg must be 0, 4, 8, 16 or 32");
   BandTables T;
   ADVCHAIN_CHECK_ARG(unpack_tables(itab, ftab, S, g, B, T), "bias_field_fwd: bad band tables");
   if (N == 0) return ADVCHAIN_OK;
   Dims full{(int)S[0], (int)S[1], (int)S[2]};
   ADVCHAIN_CHECK_ARG(full.voxels() < (1ll << 31), "bias_field_fwd: volume too large");
   ADVCHAIN_CHECK_ARG(T.a[2].g <= kTpMaxLds, "bias_field_fwd: too many control points per row");
-  dim3 grid((unsigned)((full.s1 + kTpChunk - 1) / kTpChunk), (unsigned)full.s0, (unsigned)N);
+  const int rows = rows_per_wg ? rows_per_wg : bias_rows_rule(S[0], S[1], N);
+  ADVCHAIN_CHECK_ARG(S[0] < 65536 && (S[1] + rows - 1) / rows < (1ll << 31), "bias_field_fwd: grid too large");
+  dim3 grid((unsigned)((full.s1 + rows - 1) / rows), (unsigned)full.s0, (unsigned)N);
   if (full.s2 % 4 == 0 && ((reinterpret_cast<uintptr_t>(data) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(field)) & 15) == 0)
     hipLaunchKernelGGL(k_bias_fwd<4>, grid, dim3(kBlock), 0, (hipStream_t)stream, cp, data, out, field, T, full, (int)C, eps,
-                       use_log, cp_scale);
+                       use_log, cp_scale, rows);
   else
     hipLaunchKernelGGL(k_bias_fwd<1>, grid, dim3(kBlock), 0, (hipStream_t)stream, cp, data, out, field, T, full, (int)C, eps,
-                       use_log, cp_scale);
+                       use_log, cp_scale, rows);
+  ADVCHAIN_LAUNCH_CHECK();
+  return ADVCHAIN_OK;
+}
+
+int advchain_bias_field_fwd(const float* cp, const float* data, float* out, float* field, const int32_t* itab,
+                            const float* ftab, const int64_t* S, const int64_t* g, const int64_t* B, int64_t N,
+                            int64_t C, float eps, int use_log, float cp_scale, void* stream) {
+  return advchain_bias_field_fwd_rows(cp, data, out, field, itab, ftab, S, g, B, N, C, eps, use_log, cp_scale, 0, stream);
+}
+
+int advchain_bias_field_bwd_rows(const float* cp, const float* data, const float* grad_out, float* grad_L, float* grad_data,
+                                 const int32_t* itab, const float* ftab, const int64_t* S, const int64_t* g,
+                                 const int64_t* B, int64_t N, int64_t C, float eps, int use_log, float cp_scale,
+                                 int rows_per_wg, void* stream) {
+  ADVCHAIN_CHECK_ARG(cp && data && grad_out && itab && ftab && (grad_L || grad_data), "bias_field_bwd: null pointer");
+  ADVCHAIN_CHECK_ARG(S && g && B, "bias_field_bwd: null dims");
+  ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && C >= 1, "bias_field_bwd: bad N/C");
+  ADVCHAIN_CHECK_ARG(bias_rows_ok(rows_per_wg), "bias_field_bwd: rows_per_wg must be 0, 4, 8, 16 or 32");
+  BandTables T;
+  ADVCHAIN_CHECK_ARG(unpack_tables(itab, ftab, S, g, B, T), "bias_field_bwd: bad band tables");
+  if (N == 0) return ADVCHAIN_OK;
+  Dims full{(int)S[0], (int)S[1], (int)S[2]};
+  ADVCHAIN_CHECK_ARG(full.voxels() < (1ll << 31), "bias_field_bwd: volume too large");
+  ADVCHAIN_CHECK_ARG(T.a[2].g <= kTpMaxLds, "bias_field_bwd: too many control points per row");
+  const int rows = rows_per_wg ? rows_per_wg : bias_rows_rule(S[0], S[1], N);
+  ADVCHAIN_CHECK_ARG(S[0] < 65536 && (S[1] + rows - 1) / rows < (1ll << 31), "bias_field_bwd: grid too large");
+  dim3 grid((unsigned)((full.s1 + rows - 1) / rows), (unsigned)full.s0, (unsigned)N);
+  if (full.s2 % 4 == 0 && ((reinterpret_cast<uintptr_t>(data) | reinterpret_cast<uintptr_t>(grad_out) |
+                            reinterpret_cast<uintptr_t>(grad_L) | reinterpret_cast<uintptr_t>(grad_data)) & 15) == 0)
+    hipLaunchKernelGGL((k_bias_bwd<4, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, cp, data, grad_out, grad_L, grad_data, T,
+                       full, (int)C, eps, use_log, cp_scale, rows, (float*)nullptr, (const float*)nullptr, (const int*)nullptr, 0);
+  else
+    hipLaunchKernelGGL((k_bias_bwd<1, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, cp, data, grad_out, grad_L, grad_data, T,
+                       full, (int)C, eps, use_log, cp_scale, rows, (float*)nullptr, (const float*)nullptr, (const int*)nullptr, 0);
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
 }
@@ -1728,22 +1855,44 @@ int advchain_bias_field_bwd(const float* cp, const float* data, const float* gra
                             const int32_t* itab, const float* ftab, const int64_t* S, const int64_t* g,
                             const int64_t* B, int64_t N, int64_t C, float eps, int use_log, float cp_scale,
                             void* stream) {
-  ADVCHAIN_CHECK_ARG(cp && data && grad_out && itab && ftab && (grad_L || grad_data), "bias_field_bwd: null pointer");
-  ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && C >= 1, "bias_field_bwd: bad N/C");
+  return advchain_bias_field_bwd_rows(cp, data, grad_out, grad_L, grad_data, itab, ftab, S, g, B, N, C, eps, use_log, cp_scale, 0,
+                                      stream);
+}
+
+// advchain_bias_field_bwd + the innermost pass of the adjoint (advchain_band_reduce_rows_dense over grad_L, scale 1) in one
+// launch: t1 (N, 1, S0, S1, g2) instead of grad_L; wd / lo / WB as for that entry.  The same bits as the two calls.
+// ADVCHAIN_ERR_UNSUPPORTED (-2), nothing enqueued: t1 == NULL, the shapes advchain_band_reduce_rows_dense refuses (S2 % 4,
+// S2 > 1024, g2 > 64, g2 * WB > 4096, an operand that is not 16-byte aligned), or the dense table plus a slab of 4 rows beyond
+// kBiasRedLds.  The LDS budget: kBiasRedLds = 48 KiB of dynamic LDS for the table and the slab of `rows` rows of S2 + 1 floats
+// -- with the 8 KiB blend buffer and the row tables a workgroup stays below 64 KiB; `rows` is halved until it fits (the
+// largest cfg-2 case, 32 x 257 x 4 B + 4 KiB, does at every value).
+constexpr size_t kBiasRedLds = 48 * 1024;
+int advchain_bias_field_bwd_reduced(const float* cp, const float* data, const float* grad_out, float* t1, float* grad_data,
+                                    const int32_t* itab, const float* ftab, const int64_t* S, const int64_t* g,
+                                    const int64_t* B, int64_t N, int64_t C, float eps, int use_log, float cp_scale,
+                                    const float* wd, const int32_t* lo, int64_t WB, int rows_per_wg, void* stream) {
+  ADVCHAIN_CHECK_ARG(cp && data && grad_out && itab && ftab && wd && lo, "bias_field_bwd_reduced: null pointer");
+  ADVCHAIN_CHECK_ARG(S && g && B, "bias_field_bwd_reduced: null dims");
+  ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && C >= 1 && WB >= 1, "bias_field_bwd_reduced: bad N/C/WB");
+  ADVCHAIN_CHECK_ARG(bias_rows_ok(rows_per_wg), "bias_field_bwd_reduced: rows_per_wg must be 0, 4, 8, 16 or 32");
   BandTables T;
-  ADVCHAIN_CHECK_ARG(unpack_tables(itab, ftab, S, g, B, T), "bias_field_bwd: bad band tables");
+  ADVCHAIN_CHECK_ARG(unpack_tables(itab, ftab, S, g, B, T), "bias_field_bwd_reduced: bad band tables");
+  if (!t1) return ADVCHAIN_ERR_UNSUPPORTED;
+  const bool aligned = ((reinterpret_cast<uintptr_t>(data) | reinterpret_cast<uintptr_t>(grad_out) |
+                         reinterpret_cast<uintptr_t>(grad_data)) & 15) == 0;
+  if (S[2] % 4 != 0 || S[2] > 1024 || g[2] > 64 || g[2] * WB > kBrMaxW || !aligned) return ADVCHAIN_ERR_UNSUPPORTED;
+  const size_t wbytes = (size_t)((g[2] * WB + 3) / 4 * 4) * sizeof(float);
+  int rows = rows_per_wg ? rows_per_wg : bias_rows_rule(S[0], S[1], N);
+  while (rows > 4 && wbytes + (size_t)rows * (S[2] + 1) * sizeof(float) > kBiasRedLds) rows /= 2;
+  const size_t lds = wbytes + (size_t)rows * (S[2] + 1) * sizeof(float);
+  if (lds > kBiasRedLds) return ADVCHAIN_ERR_UNSUPPORTED;
   if (N == 0) return ADVCHAIN_OK;
   Dims full{(int)S[0], (int)S[1], (int)S[2]};
-  ADVCHAIN_CHECK_ARG(full.voxels() < (1ll << 31), "bias_field_bwd: volume too large");
-  ADVCHAIN_CHECK_ARG(T.a[2].g <= kTpMaxLds, "bias_field_bwd: too many control points per row");
-  dim3 grid((unsigned)((full.s1 + kTpChunk - 1) / kTpChunk), (unsigned)full.s0, (unsigned)N);
-  if (full.s2 % 4 == 0 && ((reinterpret_cast<uintptr_t>(data) | reinterpret_cast<uintptr_t>(grad_out) |
-                            reinterpret_cast<uintptr_t>(grad_L) | reinterpret_cast<uintptr_t>(grad_data)) & 15) == 0)
-    hipLaunchKernelGGL(k_bias_bwd<4>, grid, dim3(kBlock), 0, (hipStream_t)stream, cp, data, grad_out, grad_L, grad_data, T,
-                       full, (int)C, eps, use_log, cp_scale);
-  else
-    hipLaunchKernelGGL(k_bias_bwd<1>, grid, dim3(kBlock), 0, (hipStream_t)stream, cp, data, grad_out, grad_L, grad_data, T,
-                       full, (int)C, eps, use_log, cp_scale);
+  ADVCHAIN_CHECK_ARG(full.voxels() < (1ll << 31), "bias_field_bwd_reduced: volume too large");
+  ADVCHAIN_CHECK_ARG(S[0] < 65536 && (S[1] + rows - 1) / rows < (1ll << 31), "bias_field_bwd_reduced: grid too large");
+  dim3 grid((unsigned)((full.s1 + rows - 1) / rows), (unsigned)full.s0, (unsigned)N);
+  hipLaunchKernelGGL((k_bias_bwd<4, true>), grid, dim3(kBlock), lds, (hipStream_t)stream, cp, data, grad_out, (float*)nullptr,
+                     grad_data, T, full, (int)C, eps, use_log, cp_scale, rows, t1, wd, (const int*)lo, (int)WB);
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
 }

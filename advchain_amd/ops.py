@@ -197,6 +197,7 @@ WINDOW_STAGED = True  # deterministic mode, 2D: the window scatter stages its wi
                       # scatter_window.hip); False: the int64 twin, bit for bit the same results.  Read at every call: tests and
                       # tools compare the two forms in one process
 WINDOW_STAGED_CHANNELS = (1, 2, 4)   # the channel counts that take the staged form (measured: profiles/r14/window_staged)
+BIAS_REDUCED = True   # the bias backward reduces its rows along x itself (advchain_bias_field_bwd_reduced); False: the two launches
 
 # advchain_last_bwd_route (include/advchain_hip.h: ADVCHAIN_ROUTE_*)
 BWD_ROUTES = ("none", "general", "rows", "gather", "march", "window_float", "window_int64", "window_staged", "tiled")
@@ -588,14 +589,26 @@ def field_sumsq(coef, tables, C):
 
 def raw_tp_adjoint(gfull, tables, gfull2=None, scale=1.0):
     """W^T applied along every axis: (N,C,S...) -> (N,C,g...).  First pass may fuse (a - b) * scale."""
+    return _tp_adjoint_passes(gfull, tables, gfull2, scale, (2, 1, 0))
+
+
+def raw_tp_adjoint_from_t1(t1, tables):
+    """The remaining axis passes of raw_tp_adjoint from t1 (N,C,S0,S1,g2 / N,C,S1,g2), the result of its innermost pass."""
+    return _tp_adjoint_passes(t1, tables, None, 1.0, (1, 0))
+
+
+def _tp_adjoint_passes(gfull, tables, gfull2, scale, axes):
     lib = _lib.load()
     N, C = gfull.shape[:2]
     S, g, B = list(tables.S), list(tables.g), list(tables.B)
     Sa, ga, Ba = _lib.dims_array(S), _lib.dims_array(g), _lib.dims_array(B)
     cur, cur2 = gfull, gfull2
     shape = list(S)
-    first = True
     for ax in (2, 1, 0):
+        if ax not in axes:
+            shape[ax] = g[ax]             # (already reduced)
+    first = 2 in axes
+    for ax in axes:
         if S[ax] == 1 and g[ax] == 1:
             continue
         outer = N * C
@@ -619,7 +632,7 @@ def raw_tp_adjoint(gfull, tables, gfull2=None, scale=1.0):
                                                      Sa, ga, Ba, ax, outer, inner, float(scale) if first else 1.0,
                                                      _stream()), "band_reduce_axis")
         cur, cur2, first = out, None, False
-    if first:  # degenerate: nothing to reduce
+    if first and 2 in axes:  # degenerate: nothing to reduce
         cur = (gfull - gfull2 if gfull2 is not None else gfull) * scale
     return cur
 
@@ -1266,8 +1279,21 @@ class _BiasApply(torch.autograd.Function):
         if gout is None or not (need_cp or need_data):
             return None, None, None, None, None, None
         N, C = data.shape[:2]
-        gL = torch.empty((N, 1) + tuple(data.shape[2:]), device=data.device, dtype=torch.float32) if need_cp else None
         gdata = torch.empty_like(data) if need_data else None
+        dense = getattr(tables, "dense_inner", None)
+        if need_cp and BIAS_REDUCED and dense is not None:
+            # the x pass of the adjoint inside the backward: one launch, no full-resolution gradient of the field in memory
+            wd, lo, WB = dense
+            t1 = torch.empty((N, 1) + tuple(data.shape[2:-1]) + (int(tables.g[2]),), device=data.device, dtype=torch.float32)
+            rc = _lib.load().advchain_bias_field_bwd_reduced(_ptr(cp), _ptr(data), _ptr(_dev(gout, "grad")), _ptr(t1),
+                                                             _ptr(gdata), _ptr(tables.itab), _ptr(tables.ftab),
+                                                             _lib.dims_array(tables.S), _lib.dims_array(tables.g),
+                                                             _lib.dims_array(tables.B), N, C, eps, use_log, cp_scale,
+                                                             _ptr(wd), _ptr(lo), WB, 0, _stream())
+            if rc != -2:
+                _lib.check(rc, "bias_field_bwd_reduced")
+                return raw_tp_adjoint_from_t1(t1, tables).reshape(cp.shape), gdata, None, None, None, None
+        gL = torch.empty((N, 1) + tuple(data.shape[2:]), device=data.device, dtype=torch.float32) if need_cp else None
         _lib.check(_lib.load().advchain_bias_field_bwd(_ptr(cp), _ptr(data), _ptr(_dev(gout, "grad")), _ptr(gL),
                                                        _ptr(gdata), _ptr(tables.itab), _ptr(tables.ftab),
                                                        _lib.dims_array(tables.S), _lib.dims_array(tables.g),

@@ -406,6 +406,29 @@ int advchain_bias_field_bwd(const float* cp, const float* data, const float* gra
                             const int32_t* itab, const float* ftab, const int64_t* S, const int64_t* g,
                             const int64_t* B, int64_t N, int64_t C, float eps, int use_log, float cp_scale,
                             void* stream);
+/* The two entries above with the i1 rows a workgroup takes as an argument: rows_per_wg in {4, 8, 16, 32}, or 0 for the
+ * library's rule, advchain_bias_rows_per_wg(S, N) (host-only; S: 3 entries, 2D a leading 1; -1 for bad arguments) -- the
+ * largest of the four values that still gives the launch 512 workgroups, else 4.  The entries above pass 0.  Every output bit
+ * is the same whatever the value.                                                                                            */
+int advchain_bias_rows_per_wg(const int64_t* S, int64_t N);
+int advchain_bias_field_fwd_rows(const float* cp, const float* data, float* out, float* field, const int32_t* itab,
+                                 const float* ftab, const int64_t* S, const int64_t* g, const int64_t* B, int64_t N,
+                                 int64_t C, float eps, int use_log, float cp_scale, int rows_per_wg, void* stream);
+int advchain_bias_field_bwd_rows(const float* cp, const float* data, const float* grad_out, float* grad_L, float* grad_data,
+                                 const int32_t* itab, const float* ftab, const int64_t* S, const int64_t* g,
+                                 const int64_t* B, int64_t N, int64_t C, float eps, int use_log, float cp_scale,
+                                 int rows_per_wg, void* stream);
+/* advchain_bias_field_bwd and the innermost pass of the adjoint over grad_L (advchain_band_reduce_rows_dense, scale 1) in one
+ * launch: grad_L is never written; t1 (N, 1, S0, S1, g2) is what that pass would have produced from it, bit for bit (the
+ * remaining axes: advchain_band_reduce_axis).  wd / lo / WB: the densified innermost bands, as for
+ * advchain_band_reduce_rows_dense.  grad_data may be NULL.  Returns ADVCHAIN_ERR_UNSUPPORTED (-2), nothing enqueued, when
+ * t1 is NULL, for the shapes advchain_band_reduce_rows_dense refuses (S2 % 4 != 0, S2 > 1024, g2 > 64, g2 * WB > 4096, data /
+ * grad_out / grad_data not 16-byte aligned), or when the dense table and a slab of 4 rows of S2 + 1 floats exceed 48 KiB of
+ * LDS (rows_per_wg is halved until table and slab fit): issue the two calls then.                                            */
+int advchain_bias_field_bwd_reduced(const float* cp, const float* data, const float* grad_out, float* t1, float* grad_data,
+                                    const int32_t* itab, const float* ftab, const int64_t* S, const int64_t* g,
+                                    const int64_t* B, int64_t N, int64_t C, float eps, int use_log, float cp_scale,
+                                    const float* wd, const int32_t* lo, int64_t WB, int rows_per_wg, void* stream);
 
 /* ---- separable Gaussian ----------------------------------------------------------------
  * replaces: depthwise nn.Conv{2,3}d with the normalised 9^d Gaussian (sigma=1), zero padding,
