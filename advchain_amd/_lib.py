@@ -97,6 +97,9 @@ PROTOTYPES = {
     "advchain_contour_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _I, _P]),
     "advchain_contour_bwd": (_I, [_P, _P, _P, _P, _L, _L, _I, _P, _I, _P]),
     "advchain_one_hot": (_I, [_P, _P, _L, _L, _L, _P]),
+    "advchain_dice_workspace": (_L, [_L, _L, _I, _P]),
+    "advchain_dice_fwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _F, _F, _F, _P]),
+    "advchain_dice_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _F, _F, _P]),
     "advchain_image_diff2d_fwd": (_I, [_P, _P, _P, _L, _L, _P, _P]),
     "advchain_image_diff2d_bwd": (_I, [_P, _P, _P, _L, _L, _P, _P]),
     "advchain_jacobian_det2d_fwd": (_I, [_P, _P, _L, _P, _P]),

@@ -1,5 +1,6 @@
 """Segmentation losses (reference: advchain/common/loss.py): the consistency loss (loss.py:8-249) and the supervised
-``contour_loss`` / ``One_Hot`` / ``cross_entropy_2D`` (loss.py:102-220, 252-326, on csrc/seg_loss.hip).
+``contour_loss`` / ``One_Hot`` / ``cross_entropy_2D`` (loss.py:102-220, 252-326, on csrc/seg_loss.hip); ``dice_loss`` /
+``dice_ce_loss`` / ``cross_entropy_3D`` (not in the reference; csrc/seg_dice.hip) complete the supervised loss of a 2D or 3D step.
 
 'mse', 'contour' and 'kl' all run in the fused HIP kernels (:func:`advchain_amd.ops.consistency_sums`:
 softmax + mask + squared error + KL sum + 3^d edge stencils in two launches forward, one backward per operand that
@@ -231,3 +232,71 @@ def cross_entropy_2D(input, target, weight=None, size_average=True):
         raise ValueError("cross_entropy_2D expects 4-D input (N,C,H,W), got %d-D" % input.dim())
     _require_gpu(target, "target")
     return ops.cross_entropy_2d(input, target, weight=weight, size_average=size_average)
+
+
+def cross_entropy_3D(input, target, weight=None, size_average=True):
+    """:func:`cross_entropy_2D` for volumes: input (N,C,D,H,W) fp32 or bf16 logits; target (N,D,H,W) int64 labels (-100 is ignored
+    but still counted in N*D*H*W) or (N,C,D,H,W) soft targets.  The same kernels (they only use the plane size)."""
+    if isinstance(input, torch.Tensor) and input.dim() != 5:
+        raise ValueError("cross_entropy_3D expects 5-D input (N,C,D,H,W), got %d-D" % input.dim())
+    _require_gpu(input, "input")
+    _require_gpu(target, "target")
+    return ops.cross_entropy_3d(input, target, weight=weight, size_average=size_average)
+
+
+def _dice_arguments(name, input, target, weight, ignore_background, smooth, factors=()):
+    """The host-side checks of the Dice losses, before any device work (a CPU caller sees the same ValueErrors)."""
+    if not isinstance(input, torch.Tensor) or input.dim() not in (4, 5):
+        raise ValueError("%s expects 4-D (N,C,H,W) or 5-D (N,C,D,H,W) logits" % name)
+    K = input.size(1)
+    if K > MAX_CLASSES:
+        raise NotImplementedError("%s takes at most %d classes, got %d" % (name, MAX_CLASSES, K))
+    smooth = float(smooth)
+    if not math.isfinite(smooth) or smooth < 0:
+        raise ValueError("%s: smooth must be finite and >= 0, got %r" % (name, smooth))
+    for f in factors:
+        if not math.isfinite(float(f)):
+            raise ValueError("%s: dice_weight and ce_weight must be finite, got %r" % (name, f))
+    if ignore_background and K == 1:
+        raise ValueError("%s: no class left (1 class, ignore_background=True)" % name)
+    if weight is not None:
+        if isinstance(weight, torch.Tensor):
+            n = weight.numel()
+        elif hasattr(weight, "__len__"):
+            n = len(weight)
+        else:
+            raise ValueError("%s: weight must be a tensor, list or array with one number per class" % name)
+        if n != K:
+            raise ValueError("%s: weight has the wrong length: %d entries for %d classes" % (name, n, K))
+    _require_gpu(input, "input")
+    _require_gpu(target, "target")
+
+
+def dice_loss(input, target, weight=None, ignore_background=False, batch_dice=False, smooth=1e-5):
+    """Soft Dice loss of logits (not in the reference; csrc/seg_dice.hip).  input: (N,K,H,W) or (N,K,D,H,W) fp32 or bf16 logits,
+    read as they are, the softmax over K runs inside the kernel (float16 is refused); target: (N,dims) int64 labels or a
+    (N,K,dims) fp32 soft target.  With p = softmax(input), t the one-hot labels or the soft target, and sums over the counted
+    voxels of batch entry n (batch_dice: over the whole batch, N -> 1)
+
+        I_nk = sum p_k t_k,  P_nk = sum p_k,  T_nk = sum t_k,  dice_nk = (2 I_nk + smooth) / (P_nk + T_nk + smooth)
+        loss = 1 - (1/N) sum_n sum_k omega_k dice_nk,   omega_k = w_k / sum of the counted w_j
+
+    A voxel labelled -100 is left out of every sum (its gradient is zero); any other label outside [0, K) makes the value
+    NaN.  weight: K numbers (tensor, list or array; constants), normalised on the device over the counted classes -- class 0
+    is not counted with ignore_background.  smooth == 0 with a class that is empty on both sides (no probability mass counted
+    and no target) gives NaN.  Returns an fp32 scalar, bitwise reproducible; gradients for the logits (their dtype, computed in
+    fp32 and rounded once) and for a soft target (fp32); labels get none."""
+    _dice_arguments("dice_loss", input, target, weight, ignore_background, smooth)
+    return ops.dice_loss(input, target, weight=weight, ignore_background=ignore_background, batch_dice=batch_dice,
+                         smooth=smooth, dice_weight=1.0, ce_weight=0.0)
+
+
+def dice_ce_loss(input, target, weight=None, ignore_background=False, batch_dice=False, smooth=1e-5, dice_weight=1.0,
+                 ce_weight=1.0):
+    """ce_weight * CE + dice_weight * :func:`dice_loss` in one pass over the logits (the nnU-Net / MONAI default loss).  CE
+    is what ``cross_entropy_2D(input, target, weight, size_average=True)`` computes, for 2D and 3D input: the weights enter it
+    as weight / sum(weight) * K, a voxel labelled -100 contributes 0 but is counted in N * voxels, and ignore_background
+    does not touch it.  Everything else as in :func:`dice_loss`."""
+    _dice_arguments("dice_ce_loss", input, target, weight, ignore_background, smooth, (dice_weight, ce_weight))
+    return ops.dice_loss(input, target, weight=weight, ignore_background=ignore_background, batch_dice=batch_dice,
+                         smooth=smooth, dice_weight=dice_weight, ce_weight=ce_weight)

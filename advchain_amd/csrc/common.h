@@ -156,6 +156,23 @@ __device__ __forceinline__ float lane_prev_f(float v) {   // lane i <- lane i-1
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, false));
 }
 
+// Sum over the wave on the DPP path: six dependent VALU operations instead of the six LDS round trips of wave_sum() (seg_dice.hip
+// reduces three values per class).  Lanes pair up inside their quad, their half row and their row of 16 (every lane of a row
+// then holds the row's sum), then lane 15 / 31 of a row is broadcast into the rows above it: a fixed order, and the total is
+// valid in LANE 63 only.  Every lane of the wave must be active.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float dpp_add(float v) {
+  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
+}
+__device__ __forceinline__ float wave_sum_lane63(float v) {
+  v = dpp_add<0xB1, 0xf>(v);         // quad_perm [1,0,3,2]
+  v = dpp_add<0x4E, 0xf>(v);         // quad_perm [2,3,0,1]
+  v = dpp_add<0x141, 0xf>(v);        // row_half_mirror
+  v = dpp_add<0x140, 0xf>(v);        // row_mirror
+  v = dpp_add<0x142, 0xa>(v);        // row_bcast:15 into rows 1 and 3
+  return dpp_add<0x143, 0xc>(v);     // row_bcast:31 into rows 2 and 3
+}
+
 // Per-workgroup partial sums go to one of kSumSlots accumulators (slot = workgroup id mod kSumSlots): thousands of
 // atomics on ONE address serialise at ~10 ns each on MI355X; the consumer adds the slots up.
 constexpr int kSumSlots = 64;

@@ -2074,6 +2074,111 @@ def cross_entropy_2d(x, target, weight=None, size_average=True):
     return _CrossEntropy2D.apply(x, labels, soft, weight, denom)
 
 
+@_on_tensor_device
+def cross_entropy_3d(x, target, weight=None, size_average=True):
+    """cross_entropy_2D for (N,K,D,H,W) logits: the kernels only use the plane size, so the volume runs as the (N,K,D,H*W)
+    view of itself (no copy, no kernel for the view or its gradient).  target: (N,D,H,W) int64 labels or a (N,K,D,H,W) soft
+    target."""
+    x = _dev_logits(x, "input")
+    if x.dim() != 5:
+        raise ValueError("cross_entropy_3D takes 5-D input (N,C,D,H,W), got %d-D" % x.dim())
+    if not isinstance(target, torch.Tensor) or not target.is_cuda:
+        raise _lib.AdvchainHipError("target must be a CUDA/ROCm tensor: the advchain_amd kernels have no CPU path")
+    N, K, D, H, W = x.shape
+    if target.dim() == 4:
+        if tuple(target.shape) != (N, D, H, W):
+            raise ValueError("label target must be (N,D,H,W) = %s, got %s" % ((N, D, H, W), tuple(target.shape)))
+        target = target.contiguous().view(N, D, H * W)
+    elif target.dim() == 5:
+        if target.shape != x.shape:
+            raise ValueError("soft target must have the input's shape %s, got %s" % (tuple(x.shape), tuple(target.shape)))
+        target = (target if target.dtype == torch.float32 else target.float()).contiguous().view(N, K, D, H * W)
+    else:
+        raise NotImplementedError("cross_entropy_3D: target must be (N,D,H,W) labels or (N,C,D,H,W) soft targets")
+    return cross_entropy_2d(x.view(N, K, D, H * W), target, weight=weight, size_average=size_average)
+
+
+# ---- soft Dice and fused Dice + cross entropy (csrc/seg_dice.hip) --------------------------------------------------------
+
+class _Dice(torch.autograd.Function):
+    """dice_w * soft Dice + ce_w * cross entropy of (N,K,dims) logits (include/advchain_hip.h: advchain_dice_fwd).
+    Differentiable w.r.t. the logits and a soft target; three launches forward, one backward."""
+
+    @staticmethod
+    def forward(ctx, x, labels, soft, weight, cfg):
+        flags, smooth, dice_w, ce_w = cfg
+        N, K = x.shape[:2]
+        sp = tuple(x.shape[2:])
+        dims = _lib.dims_array(sp)
+        lib = _lib.load()
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[2]
+        lse = torch.empty((N,) + sp, device=x.device, dtype=torch.float32) if need else None
+        coef = torch.empty((N, K, 2), device=x.device, dtype=torch.float32) if need else None
+        n = lib.advchain_dice_workspace(N, K, len(sp), dims)
+        if n < 0:
+            raise ValueError("bad loss shape: N=%d, K=%d, dims=%s" % (N, K, sp))
+        ws = torch.empty(int(n), device=x.device, dtype=torch.float32)
+        value = torch.empty((), device=x.device, dtype=torch.float32)
+        _lib.check(lib.advchain_dice_fwd(_ptr(x), int(x.dtype == torch.bfloat16), _ptr(labels), _ptr(soft), _ptr(weight),
+                                         _ptr(lse), _ptr(coef), _ptr(ws), _ptr(value), N, K, len(sp), dims, flags, smooth,
+                                         dice_w, ce_w, _stream()), "dice_fwd")
+        if need:
+            ctx.save_for_backward(x, labels, soft, weight, lse, coef)
+        ctx.cfg = cfg
+        return value
+
+    @staticmethod
+    def backward(ctx, gloss):
+        x, labels, soft, weight, lse, coef = ctx.saved_tensors
+        _, _, dice_w, ce_w = ctx.cfg
+        N, K = x.shape[:2]
+        sp = tuple(x.shape[2:])
+        gs = _dev(gloss.reshape(1), "grad")
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gt = torch.empty_like(soft) if (soft is not None and ctx.needs_input_grad[2]) else None
+        if gx is None and gt is None:
+            return None, None, None, None, None
+        _lib.check(_lib.load().advchain_dice_bwd(_ptr(x), int(x.dtype == torch.bfloat16), _ptr(labels), _ptr(soft), _ptr(weight),
+                                                 _ptr(lse), _ptr(coef), _ptr(gs), _ptr(gx), _ptr(gt), N, K, len(sp),
+                                                 _lib.dims_array(sp), dice_w, ce_w, _stream()), "dice_bwd")
+        return gx, None, gt, None, None
+
+
+@_on_tensor_device
+def dice_loss(x, target, weight=None, ignore_background=False, batch_dice=False, smooth=1e-5, dice_weight=1.0, ce_weight=0.0):
+    """dice_weight * soft Dice + ce_weight * cross entropy (size_average) on the HIP kernels; ce_weight == 0 is the pure Dice
+    loss.  x (N,K,H,W) or (N,K,D,H,W) fp32 / bf16 logits; target: int64 labels (N,dims) (-100: left out of the Dice sums) or a
+    soft target of x's shape; weight: K class weights (tensor, list or array) or None.  Returns an fp32 scalar."""
+    x = _dev_logits(x, "input")
+    if x.dim() not in (4, 5):
+        raise ValueError("dice_loss takes 4-D (N,C,H,W) or 5-D (N,C,D,H,W) input, got %d-D" % x.dim())
+    if not isinstance(target, torch.Tensor) or not target.is_cuda:
+        raise _lib.AdvchainHipError("target must be a CUDA/ROCm tensor: the advchain_amd kernels have no CPU path")
+    N, K = x.shape[:2]
+    labels = soft = None
+    if target.dim() == x.dim() - 1:
+        labels = _dev_labels(target, "target")
+        if tuple(labels.shape) != (N,) + tuple(x.shape[2:]):
+            raise ValueError("label target must be %s, got %s" % ((N,) + tuple(x.shape[2:]), tuple(labels.shape)))
+    elif target.dim() == x.dim():
+        soft = _dev(target if target.dtype == torch.float32 else target.float(), "target")
+        if soft.shape != x.shape:
+            raise ValueError("soft target must have the input's shape %s, got %s" % (tuple(x.shape), tuple(soft.shape)))
+    else:
+        raise NotImplementedError("dice_loss: target must be (N,dims) labels or (N,C,dims) soft targets")
+    if weight is not None:
+        if isinstance(weight, torch.Tensor):
+            weight = weight.detach().to(device=x.device, dtype=torch.float32)
+        else:
+            weight = torch.as_tensor(weight, dtype=torch.float32).to(x.device)
+        weight = weight.reshape(-1).contiguous()
+        if weight.numel() != K:
+            raise ValueError("weight must have %d entries, got %d" % (K, weight.numel()))
+    _same_device(x, labels, soft, weight)
+    flags = (1 if ignore_background else 0) | (2 if batch_dice else 0)
+    return _Dice.apply(x, labels, soft, weight, (flags, float(smooth), float(dice_weight), float(ce_weight)))
+
+
 class _Contour(torch.autograd.Function):
     """Edge energy of u = sum_{c in S}(input_c - T_c) (advchain/common/loss.py:102-220, Q14).  Differentiable w.r.t. the
     prediction and a soft target; the mask is a constant."""

@@ -730,6 +730,34 @@ int advchain_contour_bwd(const float* R, const float* grad_scale, float* grad_in
  *           out (N, depth, V) fp32, planar; a label outside [0, depth) gives a NaN column.                                   */
 int advchain_one_hot(const int64_t* labels, float* out, int64_t N, int64_t depth, int64_t V, void* stream);
 
+/* ---- soft Dice and fused Dice + cross entropy, 2D and 3D (seg_dice.hip) ---------------------------------------------------
+ * Not in the reference.  logits (N,K,dims) fp32 (logits_bf16 = 0) or bf16 (1, raw 16-bit words), ndim = 2 or 3, 1 <= K <= 65535,
+ * N <= 65535; exactly one of labels (N,dims) int64 and soft (N,K,dims) fp32; p = softmax over K, inside the kernel.  A voxel
+ * labelled -100 is left out of every Dice sum; any other label outside [0,K) makes the value NaN (labels are only compared
+ * with class indices).  Over the counted voxels of entry n (with ADVCHAIN_DICE_BATCH over every entry, N -> 1 below):
+ *   I_nk = sum p_k t_k, P_nk = sum p_k, T_nk = sum t_k, D_nk = P_nk + T_nk + smooth, dice_nk = (2 I_nk + smooth) / D_nk,
+ *   value = dice_w (1 - 1/N sum_nk omega_k dice_nk) + ce_w CE,   omega_k = w_k / sum of the counted w_j
+ * with w = weight (K floats, device) or 1, class 0 not counted under ADVCHAIN_DICE_IGNORE_BACKGROUND, and CE the cross entropy
+ * of advchain_ce2d_fwd with denom = N * voxels (weight / sum(weight) * K; -100 contributes 0).  ce_w == 0: pure Dice, no CE
+ * work.  smooth == 0 with a class empty on both sides gives NaN.  Per-workgroup partials go to `workspace`
+ * (advchain_dice_workspace floats, 16-byte aligned; host-only query, -1 for bad sizes; no clearing needed) and are added in
+ * a fixed order: no float atomics, no host read-back, every output written by a kernel -- bitwise reproducible, capturable.
+ * Three launches.  lse (N*voxels floats: log-sum-exp per voxel) and coef (N*K*2 floats: A_nk = -2 c omega_k / D_nk,
+ * B_nk = c omega_k (2 I_nk + smooth) / D_nk^2, c = 1/N or 1 for batch Dice) are kept for the backward; either may be NULL. */
+#define ADVCHAIN_DICE_IGNORE_BACKGROUND 1
+#define ADVCHAIN_DICE_BATCH 2
+int64_t advchain_dice_workspace(int64_t N, int64_t K, int ndim, const int64_t* dims); /* floats */
+int advchain_dice_fwd(const void* logits, int logits_bf16, const int64_t* labels, const float* soft, const float* weight,
+                      float* lse, float* coef, float* workspace, float* value, int64_t N, int64_t K, int ndim,
+                      const int64_t* dims, int flags, float smooth, float dice_w, float ce_w, void* stream);
+/* its gradient, one launch: with g_k = A_nk t_k + B_nk, grad_logits_k = gs [dice_w p_k (g_k - sum_j g_j p_j) + ce_w CE'] (the
+ *           logits' dtype, computed in fp32 and rounded once; the Dice part is zero at ignored voxels) and, for a soft target,
+ *           grad_soft_k = gs [dice_w (A_nk p_k + B_nk) + ce_w / (N voxels) w_k (lse - x_k)] (fp32); either may be NULL (not
+ *           both); gs = *grad_scale (device scalar, NULL = 1); dice_w, ce_w as in the forward.                              */
+int advchain_dice_bwd(const void* logits, int logits_bf16, const int64_t* labels, const float* soft, const float* weight,
+                      const float* lse, const float* coef, const float* grad_scale, void* grad_logits, float* grad_soft,
+                      int64_t N, int64_t K, int ndim, const int64_t* dims, float dice_w, float ce_w, void* stream);
+
 /* ---- deformation helpers (deform_diff.hip) -----------------------------------------------------------------------------
  * The module-level helpers of adv_morph.py that users call to inspect or regularise a deformation.  H and W at least 2 (the
  * reference raises IndexError at 1), N < 65536.  Forwards round once per ATen op of the reference, in its order (no
