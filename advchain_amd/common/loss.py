@@ -16,7 +16,7 @@ import torch
 
 from .. import ops
 
-MAX_CLASSES = 65535   # the C ABI's range (include/advchain_hip.h): up to 16 classes run csrc/loss.hip, more csrc/loss_wide.hip
+MAX_CLASSES = 65535   # the C ABI's range (include/advchain_hip.h): up to 16 classes run csrc/loss.hip, more csrc/loss_lp.hip
                       # (a bf16 operand: csrc/loss_lp.hip for every class count)
 
 

@@ -1,5 +1,5 @@
-// Pieces shared by the consistency-loss translation units (loss.hip: K <= 16 in registers; loss_wide.hip: run-time K;
-// loss_ref.hip: the gradient w.r.t. the reference).
+// Pieces shared by the consistency-loss translation units (loss.hip: K <= 16 in registers; loss_lp.hip: run-time K, typed
+// loads; loss_ref.hip: the gradient w.r.t. the reference).
 #pragma once
 #include "common.h"
 
@@ -66,7 +66,7 @@ struct OrdCounts {
   void set(int row, dim3 g) const { counts[row] = (int32_t)((int64_t)g.x * g.y * g.z); }
 };
 
-// ---- the run-time-K kernels (loss_wide.hip, loss_ref.hip) ----
+// ---- the run-time-K kernels (loss_lp.hip, loss_ref.hip) ----
 
 // running max / sum of exp(x - max): ONE exp per element (the other factor of the usual two is exp(0))
 __device__ __forceinline__ void online_step(float x, float& mx, float& s) {
@@ -111,11 +111,11 @@ struct WTile {
 };
 
 // The two 3^d stencils of one output from an LDS tile (`corner`: index of the output's (-1,-1,-1) neighbour), taps in the
-// order of loss.hip's kernels.  FLIP: the adjoint (tap a reads the voxel at u - (a - 1)).
+// order of loss.hip's kernels.
 // (3D, measured: a thread's four outputs are a column along z, and sharing the in-plane sums of its six planes -- 54 LDS
 // reads per stencil instead of 4 x 27 -- costs 192 VGPRs and was slower in the forward and no faster in the backward than
 // this form at 4 x 20 x 128 x 128 x 64: not kept, LESSONS 79.)
-template <int DIM, bool FLIP>
+template <int DIM>
 __device__ __forceinline__ void tile_stencil(const float* __restrict__ bufa, const float* __restrict__ bufb, int corner,
                                              float& ga, float& gb) {
   using T = WTile<DIM>;
@@ -128,13 +128,52 @@ __device__ __forceinline__ void tile_stencil(const float* __restrict__ bufa, con
       for (int a2 = 0; a2 < 3; ++a2) {
         float wa, wb;
         stencil_w<DIM>(a0, a1, a2, wa, wb);
-        const int p0 = DIM == 3 ? (FLIP ? 2 - a0 : a0) : 0;
-        const int q = corner + (p0 * T::HY + (FLIP ? 2 - a1 : a1)) * T::HX + (FLIP ? 2 - a2 : a2);
+        const int q = corner + ((DIM == 3 ? a0 : 0) * T::HY + a1) * T::HX + a2;
         sa += wa * bufa[q];
         sb += wb * bufb[q];
       }
   ga = sa;
   gb = sb;
+}
+
+// The adjoints of the two stencils (tap a reads the voxel at u - (a - 1)), without the taps whose weight is zero (the
+// [1, 0, -1] factor: 3 of 9 taps in 2D, 9 of 27 in 3D, per stencil): a third fewer LDS reads.
+template <int DIM>
+__device__ __forceinline__ void adjoint_stencil(const float* __restrict__ bufa, const float* __restrict__ bufb, int corner,
+                                                float& ga, float& gb) {
+  using T = WTile<DIM>;
+  float sa = 0.f, sb = 0.f;
+#pragma unroll
+  for (int a0 = (DIM == 3 ? 0 : 1); a0 < (DIM == 3 ? 3 : 2); ++a0)
+#pragma unroll
+    for (int a1 = 0; a1 < 3; ++a1)
+#pragma unroll
+      for (int a2 = 0; a2 < 3; ++a2) {
+        float wa, wb;
+        stencil_w<DIM>(a0, a1, a2, wa, wb);
+        const int q = corner + ((DIM == 3 ? 2 - a0 : 0) * T::HY + (2 - a1)) * T::HX + (2 - a2);
+        if (wa != 0.f) sa += wa * bufa[q];
+        if (wb != 0.f) sb += wb * bufb[q];
+      }
+  ga = sa;
+  gb = sb;
+}
+
+// the R_k tile and its halo into one pair of LDS buffers (zero outside the volume: R is zero there)
+template <int DIM>
+__device__ __forceinline__ void stage_R(float (*buf)[WTile<DIM>::NH], const float* __restrict__ Ra, const float* __restrict__ Rb,
+                                        const int (&hv)[WTile<DIM>::SLOTS]) {
+  using T = WTile<DIM>;
+#pragma unroll
+  for (int j = 0; j < T::SLOTS; ++j) {
+    const int e = threadIdx.x + j * kBlock;
+    const int c = max(hv[j], 0);
+    const float ra = Ra[c], rb = Rb[c];          // unconditional loads from a clamped index: all in flight together
+    if (e < T::NH) {
+      buf[0][e] = hv[j] >= 0 ? ra : 0.f;
+      buf[1][e] = hv[j] >= 0 ? rb : 0.f;
+    }
+  }
 }
 
 static inline bool ldims_ok(int ndim, const int64_t* s) {

@@ -1,5 +1,5 @@
-// Segmentation-consistency loss ('mse' + 'contour' + 'kl') for logits stored in bf16 (a model under autocast), run-time class
-// count, gfx950.
+// Segmentation-consistency loss ('mse' + 'contour' + 'kl') for a RUN-TIME class count and logits stored in fp32 or bf16 (a model
+// under autocast), gfx950.
 //
 //   advchain_consistency_lp_fwd / lp_bwd / lp_ref_bwd <- calc_segmentation_consistency + contour_loss + kl_divergence,
 //                                                        advchain/common/loss.py:8-87,102-220,223-249 (Q13, Q14) and what
@@ -8,32 +8,50 @@
 //   advchain_consistency_cw_fwd / cw_bwd / cw_ref_bwd <- the same with class weights w_k (a parameter the reference documents
 //                                                        and raises on): the same kernels with a trailing weight argument
 //
-// The mathematics and the arithmetic are those of loss_wide.hip (forward, prediction side) and loss_ref.hip (reference side);
-// see their headers for the notation.  What differs is the STORAGE: each logit operand is read as fp32 or as bf16 (raw 16-bit
-// words), independently -- bf16 -> fp32 is exact, so the forward is the fp32 loss of the upcast operands -- and each gradient
-// is written in its operand's type, computed in fp32 and rounded once (to nearest even) at the store.  stats, R, the slot sums
-// and the mask stay fp32.  Every K >= 1 runs here: with a bf16 operand the K <= 16 register kernels of loss.hip are not used.
+//   advchain_consistency_wide_fwd / wide_bwd          <- the lp entries for two fp32 operands (the fp32 loss from 17 classes on)
 //
-//   k_lp_stats     k_wide_stats with typed loads.  A lane owns 4 consecutive voxels in either access form -- 16-byte fp32 /
-//                  8-byte bf16 loads when V % 4 == 0 and every pointer allows it, else scalar loads of the same 4 voxels -- so
-//                  the order of every sum, and with it the value, does not depend on the alignment of a tensor.
-//   k_lp_edge      k_wide_edge with typed loads.
-//   k_lp_bwd       the tile of k_wide_bwd.  k_wide_bwd parks the probability-space gradient g_k in grad_pred between its two
-//                  sweeps; a bf16 grad_pred would round g_k before p_k (g_k - dot) cancels.  CHOSEN HERE: the second sweep
-//                  RECOMPUTES g_k (same code, same operands: the same bits) instead of re-reading it, so the only store of an
-//                  element is the final, rounded one and no scratch exists.  Cost against k_wide_bwd, per element: one more
-//                  adjoint stencil pair (12 LDS reads in 2D, 36 in 3D), one more read of R through the halo (8 bytes x
-//                  halo / tile = 1.29 in 2D, 1.99 in 3D) and one more barrier per class; saved: the 4-byte store and the 4-byte
-//                  re-read of the parked g_k.  An fp32 scratch from the caller would have cost 4 K V N bytes of memory, 8 bytes
-//                  of traffic per element and a workspace entry in the C ABI.  Measured at 32 x 20 x 256 x 256: 349 us with a bf16
-//                  output, 420 us with an fp32 one, against 418 us of k_wide_bwd (profiles/r10/bf16_loss/summary.md).
-//   k_lp_ref_grad  the run-time form of k_loss_ref_grad (statistics always from `stats`: the lp forward saves them for every
-//                  K), with the same recomputing second sweep for h_k.  ref_is_prob: one sweep, -g_k is the gradient.
+// Same mathematics as loss.hip (see its header; the reference side: loss_ref.hip); what differs is that nothing here is sized
+// by K.  loss.hip keeps a softmax row per voxel in registers (K <= 16) or materialises P and D; here the class axis is MARCHED,
+// and each logit operand is read as fp32 or as bf16 (raw 16-bit words), independently -- bf16 -> fp32 is exact, so the forward
+// is the fp32 loss of the upcast operands -- and each gradient is written in its operand's type, computed in fp32 and rounded
+// once (to nearest even) at the store.  stats, R, the slot sums and the mask stay fp32.  Every K >= 1 runs here: with a bf16
+// operand or class weights the K <= 16 register kernels of loss.hip are not used.
 //
+//   k_lp_stats     one streaming pass with a running max / sum of exp over the K planes leaves the softmax statistics of
+//                  both operands, 16 bytes per voxel: stats (N, 4, V) = max_pred, 1 / sum_pred, max_ref, 1 / sum_ref.  With
+//                  them every class plane is independent: P_k(v) = exp(pred_k(v) - max(v)) * inv(v), the arithmetic of
+//                  loss.hip's kernels.  A second sweep over k adds up the 'mse' and 'kl' sums.  A lane owns 4 consecutive
+//                  voxels in either access form -- 16-byte fp32 / 8-byte bf16 loads when V % 4 == 0 and every pointer allows
+//                  it, else scalar loads of the same 4 voxels -- so the order of every sum, and with it the value, does not
+//                  depend on the alignment of a tensor.
+//   k_lp_edge      a workgroup owns a spatial tile (2D 64 x 8, 3D 32 x 8 x 4 outputs) and marches over the classes 1..K-1:
+//                  D_k = P_k - T_k on the tile and a one-voxel halo goes into LDS (two buffers, one barrier per class), the
+//                  3^d stencils read it there.  The statistics of a thread's halo voxels stay in its registers over the march.
+//                  Writes R (kept for the backward) and the two edge energies.
+//   k_lp_bwd       the same tile, two sweeps over the classes.  g_k = gs (c_mse 2 m^2 D_k + c_a A^T R_A + c_b B^T R_B) (R_k
+//                  tile + halo through LDS) is the probability-space gradient; the first sweep leaves dot = sum_k g_k P_k and
+//                  sum_k m_k T'_k in registers, the second stores grad_k = P_k (g_k - dot) + kl part.  An fp32 grad_pred
+//                  PARKS g_k between the sweeps: the first sweep stores it, the second is the Jacobian in place and a thread
+//                  re-reads only what it wrote itself.  A bf16 grad_pred would round the parked g_k before p_k (g_k - dot)
+//                  cancels, so there the second sweep RECOMPUTES g_k instead of re-reading it: the only store of an element
+//                  is the final, rounded one and no scratch exists.  Cost of recomputing against parking, per element: one
+//                  more adjoint stencil pair (12 LDS reads in 2D, 36 in 3D), one more read of R through the halo (8 bytes x
+//                  halo / tile = 1.29 in 2D, 1.99 in 3D) and one more barrier per class; saved: the 4-byte store and the
+//                  4-byte re-read of the parked g_k (2 + 2 in bf16, were parking possible).  An fp32 scratch from the caller
+//                  would have cost 4 K V N bytes of memory, 8 bytes of traffic per element and a workspace entry in the C
+//                  ABI.  Measured with an fp32 output, recomputing against parking: 434 against 418 us at 32 x 20 x 256 x 256,
+//                  1704 against 1272 us at 4 x 20 x 128 x 128 x 64, where recomputing runs 178 VGPRs and 2 waves per SIMD
+//                  (profiles/r18/loss_fold/summary.md); with a bf16 output recomputing takes 349 us at the 2D shape
+//                  (profiles/r10/bf16_loss/summary.md).
+//   k_lp_ref_grad  the run-time form of k_loss_ref_grad (statistics always from `stats`: the forward saves them for every
+//                  K), with a recomputing second sweep for h_k in every storage type.  ref_is_prob: one sweep, -g_k is the
+//                  gradient.  (Two fp32 operands without weights: ops takes advchain_consistency_ref_bwd, loss_ref.hip, which
+//                  parks h_k in grad_ref and is faster -- 299 against 438 us, 980 against 1716 us at the shapes above.)
+//
+// Saved per evaluation: stats 16 V N bytes and R 8 (K - 1) V N bytes; P and D (8 K V N bytes) never exist.
 // The tile kernels read one value per lane and plane (a wave reads 64 consecutive values of a tile row: 128 contiguous bytes
-// in bf16) at any alignment; only k_lp_stats has a vector form.  The adjoint stencils skip the zero-weight taps (as
-// loss_ref.hip does).  No atomics on the gradients and no shared accumulator: bit-reproducible.  Streaming + 3^d stencil:
-// memory-bound, no MFMA.
+// in bf16) at any alignment; only k_lp_stats has a vector form.  The adjoint stencils skip the zero-weight taps.  No atomics
+// on the gradients and no shared accumulator: bit-reproducible.  Streaming + 3^d stencil: memory-bound, no MFMA.
 #include <stdio.h>
 #include <algorithm>
 
@@ -105,45 +123,6 @@ __device__ __forceinline__ void st4(float* __restrict__ p, int cnt, const float 
 #pragma unroll
     for (int q = 0; q < 4; ++q)
       if (q < cnt) p[q] = x[q];
-  }
-}
-
-// tile_stencil<DIM, true> without the taps whose weight is zero (the [1, 0, -1] factor: 3 of 9 taps in 2D, 9 of 27 in 3D)
-template <int DIM>
-__device__ __forceinline__ void lp_adjoint_stencil(const float* __restrict__ bufa, const float* __restrict__ bufb, int corner,
-                                                   float& ga, float& gb) {
-  using T = WTile<DIM>;
-  float sa = 0.f, sb = 0.f;
-#pragma unroll
-  for (int a0 = (DIM == 3 ? 0 : 1); a0 < (DIM == 3 ? 3 : 2); ++a0)
-#pragma unroll
-    for (int a1 = 0; a1 < 3; ++a1)
-#pragma unroll
-      for (int a2 = 0; a2 < 3; ++a2) {
-        float wa, wb;
-        stencil_w<DIM>(a0, a1, a2, wa, wb);
-        const int q = corner + ((DIM == 3 ? 2 - a0 : 0) * T::HY + (2 - a1)) * T::HX + (2 - a2);
-        if (wa != 0.f) sa += wa * bufa[q];
-        if (wb != 0.f) sb += wb * bufb[q];
-      }
-  ga = sa;
-  gb = sb;
-}
-
-// the R_k tile and its halo into one pair of LDS buffers (zero outside the volume: R is zero there)
-template <int DIM>
-__device__ __forceinline__ void lp_stage_R(float (*buf)[WTile<DIM>::NH], const float* __restrict__ Ra,
-                                           const float* __restrict__ Rb, const int (&hv)[WTile<DIM>::SLOTS]) {
-  using T = WTile<DIM>;
-#pragma unroll
-  for (int j = 0; j < T::SLOTS; ++j) {
-    const int e = threadIdx.x + j * kBlock;
-    const int c = max(hv[j], 0);
-    const float ra = Ra[c], rb = Rb[c];          // unconditional loads from a clamped index: all in flight together
-    if (e < T::NH) {
-      buf[0][e] = hv[j] >= 0 ? ra : 0.f;
-      buf[1][e] = hv[j] >= 0 ? rb : 0.f;
-    }
   }
 }
 
@@ -274,7 +253,7 @@ k_lp_edge(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* 
 #pragma unroll
     for (int j = 0; j < T::OUTS; ++j) {
       float ga, gb;
-      tile_stencil<DIM, false>(buf, buf, oc[j], ga, gb);
+      tile_stencil<DIM>(buf, buf, oc[j], ga, gb);
       if (ov[j] >= 0) {
         const float m = om[j];
         const float ea = ga * m, eb = gb * m;
@@ -299,15 +278,18 @@ k_lp_edge(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* 
   }
 }
 
-// grad_pred.  Sweep 0 leaves dot = sum_k g_k P_k and sum_k m_k T'_k in registers and stores nothing; sweep 1 recomputes g_k and
-// stores P_k (g_k - dot) + the 'kl' part, rounded once.  The barrier between the sweeps: with an even K the last class of
-// sweep 0 and the first staged class of sweep 1 use the same LDS buffer.
+// grad_pred.  Sweep 0 leaves dot = sum_k g_k P_k and sum_k m_k T'_k in registers; sweep 1 stores P_k (g_k - dot) + the 'kl'
+// part.  Between the two, g_k is PARKED in an fp32 grad_pred (stored by sweep 0, re-read by the thread that wrote it) and
+// RECOMPUTED for a bf16 one, which would round it: sweep 0 then stores nothing and the only store of an element is the final,
+// rounded one.  The barrier between the recomputing sweeps: with an even K the last class of sweep 0 and the first staged
+// class of sweep 1 use the same LDS buffer.
 template <typename PT, typename RT, int DIM, typename... W>
 __global__ void __launch_bounds__(kBlock)
 k_lp_bwd(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* __restrict__ stats, const float* __restrict__ R,
          const float* __restrict__ mask, const float* __restrict__ gscale, PT* __restrict__ gpred, float c_mse, float c_a,
          float c_b, float c_kl, int ref_is_prob, int K, Dims d, int mask_ch, W... cw) {
   constexpr bool CW = sizeof...(W) != 0;
+  constexpr bool PARK = sizeof(PT) == 4;
   using T = WTile<DIM>;
   __shared__ float lds[2][2][T::NH];
   const T tile(d);
@@ -333,7 +315,7 @@ k_lp_bwd(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* _
     klS[j] = 0.f;
   }
   const bool edges = R != nullptr;
-  for (int sweep = 0; sweep < 2; ++sweep) {
+  for (int sweep = 0; sweep < (PARK ? 1 : 2); ++sweep) {
     if (sweep) __syncthreads();
     for (int k = 0; k < K; ++k) {
       const int64_t plane = ((int64_t)n * K + k) * V;
@@ -341,7 +323,7 @@ k_lp_bwd(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* _
       float (*buf)[T::NH] = lds[k & 1];
       if (edges && k >= 1) {
         const float* Ra = R + ((int64_t)n * 2 * (K - 1) + 2 * (k - 1)) * V;
-        lp_stage_R<DIM>(buf, Ra, Ra + V, hv);
+        stage_R<DIM>(buf, Ra, Ra + V, hv);
         __syncthreads();     // (the other buffer is written next: one barrier per class)
       }
 #pragma unroll
@@ -354,13 +336,16 @@ k_lp_bwd(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* _
         float g = c_mse * 2.f * m * m * (p - t);
         if (edges && k >= 1) {
           float ta, tb;                 // A^T R_A, B^T R_B (R is zero outside the volume)
-          lp_adjoint_stencil<DIM>(buf[0], buf[1], oc[j], ta, tb);
+          adjoint_stencil<DIM>(buf[0], buf[1], oc[j], ta, tb);
           g += c_a * ta + c_b * tb;
         }
         if constexpr (CW) g *= wk;
         g *= gs;
         const float wm = CW ? wk * m : m;     // 'kl' takes w_k m_k where the unweighted loss takes m_k
         if (sweep == 0) {
+          if constexpr (PARK) {
+            if (ov[j] >= 0) gpred[plane + c] = g;
+          }
           dot[j] += g * p;
           if (c_kl != 0.f) klS[j] += wm * kl_prob(t, ref_is_prob);
         } else if (ov[j] >= 0) {
@@ -368,6 +353,29 @@ k_lp_bwd(const PT* __restrict__ pred, const RT* __restrict__ ref, const float* _
           if (c_kl != 0.f) o += gs * c_kl * (p * klS[j] - wm * kl_prob(t, ref_is_prob));   // 'kl': gs c_kl (P_j sum_k m_k T'_k - m_j T'_j)
           st1<PT>(gpred + plane + c, o);
         }
+      }
+    }
+  }
+  if constexpr (PARK) {
+    // second sweep over the parked g_k: the softmax Jacobian in place (every thread re-reads only its own stores)
+    for (int k = 0; k < K; ++k) {
+      const int64_t plane = ((int64_t)n * K + k) * V;
+      const float wk = lp_cw(k, cw...);
+#pragma unroll
+      for (int j = 0; j < T::OUTS; ++j) {
+        if (ov[j] < 0) continue;
+        const int c = ov[j];
+        const float xp = ld1<PT>(pred + plane + c);
+        const float p = mul_nc(ADVCHAIN_SM_EXP(xp - omp[j]), oip[j]);
+        float o = p * (gpred[plane + c] - dot[j]);
+        if (c_kl != 0.f) {   // 'kl': gs c_kl (P_j sum_k m_k T'_k - m_j T'_j)
+          const float xr = ld1<RT>(ref + plane + c);
+          const float t = ref_is_prob ? xr : mul_nc(ADVCHAIN_SM_EXP(xr - omr[j]), oir[j]);
+          const float m = (mask && mask_ch > 1) ? mask[((int64_t)n * mask_ch + k) * V + c] : om[j];
+          const float wm = CW ? wk * m : m;
+          o += gs * c_kl * (p * klS[j] - wm * kl_prob(t, ref_is_prob));
+        }
+        gpred[plane + c] = o;
       }
     }
   }
@@ -419,7 +427,7 @@ k_lp_ref_grad(const PT* __restrict__ pred, const RT* __restrict__ ref, const flo
       float (*buf)[T::NH] = lds[k & 1];
       if (edges && k >= 1) {
         const float* Ra = R + ((int64_t)n * 2 * (K - 1) + 2 * (k - 1)) * V;
-        lp_stage_R<DIM>(buf, Ra, Ra + V, hv);
+        stage_R<DIM>(buf, Ra, Ra + V, hv);
         __syncthreads();     // (the other buffer is written next: one barrier per class)
       }
 #pragma unroll
@@ -433,7 +441,7 @@ k_lp_ref_grad(const PT* __restrict__ pred, const RT* __restrict__ ref, const flo
         float g = c_mse * 2.f * m * m * (p - t);
         if (edges && k >= 1) {
           float ta, tb;                 // A^T R_A, B^T R_B
-          lp_adjoint_stencil<DIM>(buf[0], buf[1], oc[j], ta, tb);
+          adjoint_stencil<DIM>(buf[0], buf[1], oc[j], ta, tb);
           g += c_a * ta + c_b * tb;
         }
         if constexpr (CW) g *= wk;
@@ -681,6 +689,36 @@ int advchain_consistency_cw_ref_bwd(const void* pred, int pred_bf16, const void*
                                     const int64_t* dims, int mask_channels, const float* class_w, void* stream) {
   return lp_bwd("consistency_cw_ref_bwd", true, true, pred, pred_bf16, ref, ref_bf16, stats, R, mask, grad_scale, grad_ref,
                 c_mse, c_a, c_b, c_kl, ref_is_prob, N, K, ndim, dims, mask_channels, class_w, stream);
+}
+
+// the fp32 entries of the run-time-K loss (the unweighted fp32 loss from 17 classes on): the lp entries with both operands fp32
+int advchain_consistency_wide_fwd(const float* pred, const float* ref, const float* mask, float* stats, float* R, float* sums,
+                                  int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels, int ref_is_prob,
+                                  int want_edges, int want_kl, void* stream) {
+  return lp_fwd("consistency_wide_fwd", false, nullptr, pred, 0, ref, 0, mask, stats, R, sums, N, K, ndim, dims, mask_channels,
+                ref_is_prob, want_edges, want_kl, nullptr, stream);
+}
+
+int advchain_consistency_wide_bwd(const float* pred, const float* ref, const float* stats, const float* R, const float* mask,
+                                  const float* grad_scale, float* grad_pred, float c_mse, float c_a, float c_b, float c_kl,
+                                  int ref_is_prob, int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels,
+                                  void* stream) {
+  return lp_bwd("consistency_wide_bwd", false, false, pred, 0, ref, 0, stats, R, mask, grad_scale, grad_pred, c_mse, c_a, c_b,
+                c_kl, ref_is_prob, N, K, ndim, dims, mask_channels, nullptr, stream);
+}
+
+// (aligned16 is accepted and ignored: the grid does not depend on the alignment of a tensor)
+int64_t advchain_consistency_wide_fwd_partials(int64_t N, int64_t K, int ndim, const int64_t* dims, int want_edges, int) {
+  return advchain_consistency_lp_fwd_partials(N, K, ndim, dims, want_edges);
+}
+
+int advchain_consistency_wide_fwd_ord(const float* pred, const float* ref, const float* mask, float* stats, float* R,
+                                      float* partials, int64_t stride, int32_t* counts, int64_t N, int64_t K, int ndim,
+                                      const int64_t* dims, int mask_channels, int ref_is_prob, int want_edges, int want_kl,
+                                      void* stream) {
+  const OrdCounts oc{stride, counts};
+  return lp_fwd("consistency_wide_fwd_ord", false, &oc, pred, 0, ref, 0, mask, stats, R, partials, N, K, ndim, dims,
+                mask_channels, ref_is_prob, want_edges, want_kl, nullptr, stream);
 }
 
 }  // extern "C"

@@ -14,10 +14,10 @@
 // log T_k - log P_k comes from the logits and the softmax statistics, (x_r - max_r + log inv_r) - (x_p - max_p + log inv_p),
 // never from the log of a probability.  With ref_is_prob the reference's softmax is never evaluated.
 //
-//   k_loss_ref_grad<DIM, 0>        run-time K (< 65536).  The tile scheme of k_wide_bwd (loss_wide.hip): a workgroup owns a
+//   k_loss_ref_grad<DIM, 0>        run-time K (< 65536).  The tile scheme of k_lp_bwd (loss_lp.hip): a workgroup owns a
 //                                  spatial tile, the R_k tile + one-voxel halo goes through two LDS buffers (one barrier per
 //                                  class), flipped stencils read it there (zero-weight taps skipped).  Softmax statistics
-//                                  of the outputs: from `stats` (saved by the wide forward) or, when nothing saved them
+//                                  of the outputs: from `stats` (saved by a run-time-K forward) or, when nothing saved them
 //                                  (K <= 16), from a prologue sweep over the classes (running max / sum, one exp per
 //                                  element).  First sweep: h_k goes into grad_ref, sum_j T_j h_j stays in registers.  Second
 //                                  sweep: the Jacobian in place -- a thread re-reads only what it stored itself.
@@ -31,46 +31,6 @@
 #include "loss_common.h"
 
 namespace advchain {
-
-// the R_k tile and its halo into one pair of LDS buffers (zero outside the volume: R is zero there)
-template <int DIM>
-__device__ __forceinline__ void stage_R(float (*buf)[WTile<DIM>::NH], const float* __restrict__ Ra, const float* __restrict__ Rb,
-                                        const int (&hv)[WTile<DIM>::SLOTS]) {
-  using T = WTile<DIM>;
-#pragma unroll
-  for (int j = 0; j < T::SLOTS; ++j) {
-    const int e = threadIdx.x + j * kBlock;
-    const int c = max(hv[j], 0);
-    const float ra = Ra[c], rb = Rb[c];          // unconditional loads from a clamped index: all in flight together
-    if (e < T::NH) {
-      buf[0][e] = hv[j] >= 0 ? ra : 0.f;
-      buf[1][e] = hv[j] >= 0 ? rb : 0.f;
-    }
-  }
-}
-
-// tile_stencil<DIM, true> without the taps whose weight is zero (the [1, 0, -1] factor: 3 of 9 taps in 2D, 9 of 27 in 3D, per
-// stencil): a third fewer LDS reads.  (loss_wide.hip keeps the full form: its results must not move by a bit.)
-template <int DIM>
-__device__ __forceinline__ void adjoint_stencil(const float* __restrict__ bufa, const float* __restrict__ bufb, int corner,
-                                                float& ga, float& gb) {
-  using T = WTile<DIM>;
-  float sa = 0.f, sb = 0.f;
-#pragma unroll
-  for (int a0 = (DIM == 3 ? 0 : 1); a0 < (DIM == 3 ? 3 : 2); ++a0)
-#pragma unroll
-    for (int a1 = 0; a1 < 3; ++a1)
-#pragma unroll
-      for (int a2 = 0; a2 < 3; ++a2) {
-        float wa, wb;
-        stencil_w<DIM>(a0, a1, a2, wa, wb);
-        const int q = corner + ((DIM == 3 ? 2 - a0 : 0) * T::HY + (2 - a1)) * T::HX + (2 - a2);
-        if (wa != 0.f) sa += wa * bufa[q];
-        if (wb != 0.f) sb += wb * bufb[q];
-      }
-  ga = sa;
-  gb = sb;
-}
 
 template <int DIM, int KR>
 __global__ void __launch_bounds__(kBlock)

@@ -185,7 +185,7 @@ ADAPTIVE_HALO = os.environ.get("ADVCHAIN_NO_ADAPTIVE_HALO") is None   # measure 
 PAIR_FIELDS = os.environ.get("ADVCHAIN_NO_PAIR_FIELDS") is None       # a solver step integrates field(+v) and field(-v) as one batch
 TILED_SCATTER = True  # LDS-tiled owner-computes scatter (False: global-atomic kernels; for A/B tests)
 FUSED_LOSS = True     # the consistency loss straight from the logits (no P / D intermediates); False: A/B tests
-WIDE_LOSS_MIN_K = 17  # class counts from here on take the run-time-K loss kernels (loss_wide.hip: any K < 65536, no P / D); below:
+WIDE_LOSS_MIN_K = 17  # class counts from here on take the run-time-K loss kernels (loss_lp.hip: any K < 65536, no P / D); below:
                       # the K <= 16 kernels of loss.hip, unchanged.  Tests and tools lower it to compare the two implementations
 REF_GRAD_REG_MAX_K = 4  # the gradient w.r.t. the reference (loss_ref.hip) keeps K = 2..this many classes in registers (at most 4);
                       # 0: the run-time-K form for every class count.  Tests and tools lower it to compare the two forms
@@ -1708,9 +1708,10 @@ class _Consistency(torch.autograd.Function):
     """c_mse * S0 + c_a * SA + c_b * SB + c_kl * SKL  with  S0 = sum((P m - T m)^2), SA/SB = masked edge energies,
     SKL = sum m T' (log T' - log P)  (advchain/common/loss.py:55-79,102-220,223-249).  Differentiable w.r.t. the
     prediction logits (one launch of the forward family's own backward entry) and w.r.t. the reference (one launch of
-    advchain_consistency_ref_bwd, csrc/loss_ref.hip, whichever forward family ran); each is launched only when its operand
-    needs a gradient.  A reference given as probabilities (ref_is_prob) enters 'mse' and 'contour' as it is and 'kl' through a
-    where() that cuts the graph: with 'kl' alone its gradient is None and nothing is launched.  The mask is a constant.
+    advchain_consistency_ref_bwd, csrc/loss_ref.hip, for two fp32 operands without weights; the lp / cw family's own ref_bwd
+    entry otherwise); each is launched only when its operand needs a gradient.  A reference given as probabilities
+    (ref_is_prob) enters 'mse' and 'contour' as it is and 'kl' through a where() that cuts the graph: with 'kl' alone its
+    gradient is None and nothing is launched.  The mask is a constant.
     class_w (a tuple of K floats, or None): constant class weights inside S0, SA/SB (object classes) and SKL -- the cw entries
     of csrc/loss_lp.hip for every K and either storage type; None runs the unweighted families."""
 
@@ -1719,13 +1720,13 @@ class _Consistency(torch.autograd.Function):
         pred, ref = _dev_logits(pred, "pred"), _dev_logits(ref, "reference")
         if class_w is not None and len(class_w) != pred.shape[1]:
             raise ValueError("class_w must have %d entries (one per class), got %d" % (pred.shape[1], len(class_w)))
-        if class_w is not None or pred.dtype != torch.float32 or ref.dtype != torch.float32:
-            if isinstance(mask, torch.Tensor) and mask.dtype in (torch.bfloat16, torch.float16, torch.float64):
-                mask = mask.float()           # (small: the kernels read an fp32 mask)
-            mask = None if mask is None else _dev(mask, "mask")
-            return _Consistency._forward_lp(ctx, pred, ref, mask, coef, ref_is_prob, want_edges, class_w)
+        typed = class_w is not None or pred.dtype != torch.float32 or ref.dtype != torch.float32
+        if typed and isinstance(mask, torch.Tensor) and mask.dtype in (torch.bfloat16, torch.float16, torch.float64):
+            mask = mask.float()           # (small: the kernels read an fp32 mask)
         mask = None if mask is None else _dev(mask, "mask")
         N, K = pred.shape[:2]
+        if typed or K >= WIDE_LOSS_MIN_K:      # run-time K: per-voxel softmax statistics of both operands instead of P and D
+            return _Consistency._forward_lp(ctx, pred, ref, mask, coef, ref_is_prob, want_edges, class_w)
         nd = pred.dim() - 2
         dims = _lib.dims_array(pred.shape[2:])
         mch = 1 if mask is None else mask.shape[1]
@@ -1740,8 +1741,6 @@ class _Consistency(torch.autograd.Function):
         sums = torch.empty(4, device=pred.device, dtype=torch.float32)
         value = torch.empty((), device=pred.device, dtype=torch.float32)
         lib = _lib.load()
-        wide = K >= WIDE_LOSS_MIN_K
-        stats = None
         if is_deterministic():
             # the value in a fixed order: the same kernels store one partial per workgroup, the ordered finisher adds them
             # (include/advchain_hip.h, the *_fwd_ord entries); everything the backward reads is what the default mode saves
@@ -1749,77 +1748,57 @@ class _Consistency(torch.autograd.Function):
             shape = tuple(pred.shape[2:])
             fused = False
             P = D = None
-            if wide:
-                stats = torch.empty((N, 4) + tuple(pred.shape[2:]), device=pred.device, dtype=torch.float32)
-                part, stride, counts = _ordered_partials(_ordered_stride(
-                    "wide_fwd", N, K, shape, int(want_edges), _aligned16(pred, ref, mask, stats)), "consistency_wide_fwd_ord",
-                    pred.device)
-                _lib.check(lib.advchain_consistency_wide_fwd_ord(_ptr(pred), _ptr(ref), _ptr(mask), _ptr(stats), _ptr(R), _ptr(part),
-                                                                 stride, counts, *args), "consistency_wide_fwd_ord")
-            else:
-                nf = _ordered_stride("fused_fwd", N, K, shape, int(mask is not None), mch, int(want_edges),
-                                     _aligned16(pred, ref, mask, R)) if FUSED_LOSS else -2
-                if nf != -2:
-                    part, stride, counts = _ordered_partials(nf, "consistency_fused_fwd_ord", pred.device)
-                    rc = lib.advchain_consistency_fused_fwd_ord(_ptr(pred), _ptr(ref), _ptr(mask), _ptr(R), _ptr(part), stride,
-                                                                counts, *args)
-                    fused = rc != -2
-                    if fused:
-                        _lib.check(rc, "consistency_fused_fwd_ord")
-                if not fused:
-                    P = torch.empty_like(pred)
-                    D = torch.empty_like(pred)
-                    part, stride, counts = _ordered_partials(_ordered_stride(
-                        "fwd", N, K, shape, mch, int(want_edges), _aligned16(pred, ref, mask, P, D, R)), "consistency_fwd_ord",
-                        pred.device)
-                    _lib.check(lib.advchain_consistency_fwd_ord(_ptr(pred), _ptr(ref), _ptr(mask), _ptr(P), _ptr(D), _ptr(R),
-                                                                _ptr(part), stride, counts, *args), "consistency_fwd_ord")
-            _lib.check(lib.advchain_consistency_finish_ord(_ptr(part), stride, counts, _lib.float_array(coef), _ptr(sums),
-                                                           _ptr(value), _stream()), "consistency_finish_ord")
-            return _Consistency._save_fp32(ctx, value, sums, pred, ref, mask, R, P, D, stats, wide, fused, coef, mch,
-                                           ref_is_prob, want_edges)
-        slots = _persistent_zeros("loss", (4, 64), pred.device)   # per-workgroup partials, 64 slots per sum; zeroed by the finisher
-        try:
-            if wide:
-                # run-time K: per-voxel softmax statistics of both operands instead of P and D
-                stats = torch.empty((N, 4) + tuple(pred.shape[2:]), device=pred.device, dtype=torch.float32)
-                _lib.check(lib.advchain_consistency_wide_fwd(_ptr(pred), _ptr(ref), _ptr(mask), _ptr(stats), _ptr(R), _ptr(slots),
-                                                             N, K, nd, dims, mch, int(ref_is_prob), int(want_edges),
-                                                             int(want_kl), _stream()), "consistency_wide_fwd")
-                fused = False
-                P = D = None
-            else:
-                # f2 fused: one marching kernel straight from the logits, nothing saved but R (K = 2..4, rows of 4j <= 256 voxels)
-                rc = lib.advchain_consistency_fused_fwd(_ptr(pred), _ptr(ref), _ptr(mask), _ptr(R), _ptr(slots), N, K, nd, dims, mch,
-                                                        int(ref_is_prob), int(want_edges), int(want_kl), _stream()) if FUSED_LOSS else -2
+            nf = _ordered_stride("fused_fwd", N, K, shape, int(mask is not None), mch, int(want_edges),
+                                 _aligned16(pred, ref, mask, R)) if FUSED_LOSS else -2
+            if nf != -2:
+                part, stride, counts = _ordered_partials(nf, "consistency_fused_fwd_ord", pred.device)
+                rc = lib.advchain_consistency_fused_fwd_ord(_ptr(pred), _ptr(ref), _ptr(mask), _ptr(R), _ptr(part), stride,
+                                                            counts, *args)
                 fused = rc != -2
                 if fused:
-                    _lib.check(rc, "consistency_fused_fwd")
-                    P = D = None
-                else:
-                    P = torch.empty_like(pred)
-                    D = torch.empty_like(pred)
-                    _lib.check(lib.advchain_consistency_fwd(_ptr(pred), _ptr(ref), _ptr(mask), _ptr(P), _ptr(D), _ptr(R),
-                                                            _ptr(slots), N, K, nd, dims, mch, int(ref_is_prob),
-                                                            int(want_edges), int(want_kl), _stream()), "consistency_fwd")
+                    _lib.check(rc, "consistency_fused_fwd_ord")
+            if not fused:
+                P = torch.empty_like(pred)
+                D = torch.empty_like(pred)
+                part, stride, counts = _ordered_partials(_ordered_stride(
+                    "fwd", N, K, shape, mch, int(want_edges), _aligned16(pred, ref, mask, P, D, R)), "consistency_fwd_ord",
+                    pred.device)
+                _lib.check(lib.advchain_consistency_fwd_ord(_ptr(pred), _ptr(ref), _ptr(mask), _ptr(P), _ptr(D), _ptr(R),
+                                                            _ptr(part), stride, counts, *args), "consistency_fwd_ord")
+            _lib.check(lib.advchain_consistency_finish_ord(_ptr(part), stride, counts, _lib.float_array(coef), _ptr(sums),
+                                                           _ptr(value), _stream()), "consistency_finish_ord")
+            return _Consistency._save_fp32(ctx, value, sums, pred, ref, mask, R, P, D, fused, coef, mch, ref_is_prob,
+                                           want_edges)
+        slots = _persistent_zeros("loss", (4, 64), pred.device)   # per-workgroup partials, 64 slots per sum; zeroed by the finisher
+        try:
+            # f2 fused: one marching kernel straight from the logits, nothing saved but R (K = 2..4, rows of 4j <= 256 voxels)
+            rc = lib.advchain_consistency_fused_fwd(_ptr(pred), _ptr(ref), _ptr(mask), _ptr(R), _ptr(slots), N, K, nd, dims, mch,
+                                                    int(ref_is_prob), int(want_edges), int(want_kl), _stream()) if FUSED_LOSS else -2
+            fused = rc != -2
+            if fused:
+                _lib.check(rc, "consistency_fused_fwd")
+                P = D = None
+            else:
+                P = torch.empty_like(pred)
+                D = torch.empty_like(pred)
+                _lib.check(lib.advchain_consistency_fwd(_ptr(pred), _ptr(ref), _ptr(mask), _ptr(P), _ptr(D), _ptr(R),
+                                                        _ptr(slots), N, K, nd, dims, mch, int(ref_is_prob),
+                                                        int(want_edges), int(want_kl), _stream()), "consistency_fwd")
             _lib.check(lib.advchain_consistency_finish(_ptr(slots), _lib.float_array(coef), _ptr(sums), _ptr(value), 1,
                                                        _stream()), "consistency_finish")
         except BaseException:
             _forget_persistent(slots)
             raise
-        return _Consistency._save_fp32(ctx, value, sums, pred, ref, mask, R, P, D, stats, wide, fused, coef, mch, ref_is_prob,
-                                       want_edges)
+        return _Consistency._save_fp32(ctx, value, sums, pred, ref, mask, R, P, D, fused, coef, mch, ref_is_prob, want_edges)
 
     @staticmethod
-    def _save_fp32(ctx, value, sums, pred, ref, mask, R, P, D, stats, wide, fused, coef, mch, ref_is_prob, want_edges):
-        """What the backward of the fp32 families needs -- the same in both modes."""
+    def _save_fp32(ctx, value, sums, pred, ref, mask, R, P, D, fused, coef, mch, ref_is_prob, want_edges):
+        """What the backward of the K <= 16 fp32 families needs -- the same in both modes."""
         K = pred.shape[1]
         need_pred, need_ref = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         need_grad = need_pred or need_ref
         if need_grad:
-            if wide:
-                ctx.save_for_backward(pred, ref, R, mask, stats)
-            elif fused:
+            if fused:
                 ctx.save_for_backward(pred, ref, R, mask)
             elif need_ref:
                 # the reference side reads the operands themselves (references to the inputs, not copies)
@@ -1828,7 +1807,6 @@ class _Consistency(torch.autograd.Function):
                 ctx.save_for_backward(P, D, R, mask)
         # ref_is_prob: 'kl' sees the reference through a where() -- without 'mse' or 'contour' it has no gradient
         ctx.ref_grad = need_ref and not (ref_is_prob and coef[0] == 0.0 and not (want_edges and K > 1))
-        ctx.wide = wide
         ctx.fused = fused
         ctx.cfg = (coef, mch, int(ref_is_prob))
         ctx.mark_non_differentiable(sums)
@@ -1837,8 +1815,8 @@ class _Consistency(torch.autograd.Function):
 
     @staticmethod
     def _forward_lp(ctx, pred, ref, mask, coef, ref_is_prob, want_edges, class_w=None):
-        """At least one operand stored in bf16, or class weights (csrc/loss_lp.hip): the run-time-K scheme for every K, each
-        operand read in its own storage type."""
+        """At least one operand stored in bf16, class weights, or K >= WIDE_LOSS_MIN_K (csrc/loss_lp.hip): the run-time-K scheme
+        for every K, each operand read in its own storage type."""
         N, K = pred.shape[:2]
         nd = pred.dim() - 2
         dims = _lib.dims_array(pred.shape[2:])
@@ -1854,35 +1832,30 @@ class _Consistency(torch.autograd.Function):
         stats = torch.empty((N, 4) + tuple(pred.shape[2:]), device=pred.device, dtype=torch.float32)
         lib = _lib.load()
         cw = None if class_w is None else class_weights_device(class_w, pred.device)
-        det = is_deterministic()
-        if det:         # the value in a fixed order (see forward)
+        operands = (_ptr(pred), int(pred.dtype == torch.bfloat16), _ptr(ref), int(ref.dtype == torch.bfloat16), _ptr(mask),
+                    _ptr(stats), _ptr(R))
+        args = (N, K, nd, dims, mch, int(ref_is_prob), int(want_edges), int(want_kl))
+        if is_deterministic():
+            # the value in a fixed order (see forward); the ord entry takes class_w (NULL: the unweighted loss)
             part, stride, counts = _ordered_partials(_ordered_stride("lp_fwd", N, K, tuple(pred.shape[2:]), int(want_edges)),
                                                      "consistency_lp_fwd_ord", pred.device)
-            _lib.check(lib.advchain_consistency_lp_fwd_ord(
-                _ptr(pred), int(pred.dtype == torch.bfloat16), _ptr(ref), int(ref.dtype == torch.bfloat16), _ptr(mask),
-                _ptr(stats), _ptr(R), _ptr(part), stride, counts, N, K, nd, dims, mch, int(ref_is_prob), int(want_edges),
-                int(want_kl), _ptr(cw), _stream()), "consistency_lp_fwd_ord")
-            _lib.check(lib.advchain_consistency_finish_ord(_ptr(part), stride, counts, _lib.float_array(coef), _ptr(sums),
-                                                           _ptr(value), _stream()), "consistency_finish_ord")
-        slots = None if det else _persistent_zeros("loss", (4, 64), pred.device)
+            slots = None
+            name, sums_args, weights = "consistency_lp_fwd_ord", (_ptr(part), stride, counts), (_ptr(cw),)
+        else:
+            slots = _persistent_zeros("loss", (4, 64), pred.device)
+            name, sums_args = "consistency_%s_fwd" % ("lp" if cw is None else "cw"), (_ptr(slots),)
+            weights = () if cw is None else (_ptr(cw),)      # (the cw entry: class_w in front of the stream)
         try:
-            if det:
-                pass
-            elif cw is None:
-                _lib.check(lib.advchain_consistency_lp_fwd(
-                    _ptr(pred), int(pred.dtype == torch.bfloat16), _ptr(ref), int(ref.dtype == torch.bfloat16), _ptr(mask),
-                    _ptr(stats), _ptr(R), _ptr(slots), N, K, nd, dims, mch, int(ref_is_prob), int(want_edges), int(want_kl),
-                    _stream()), "consistency_lp_fwd")
+            _lib.check(getattr(lib, "advchain_" + name)(*(operands + sums_args + args + weights + (_stream(),))), name)
+            if slots is None:
+                _lib.check(lib.advchain_consistency_finish_ord(_ptr(part), stride, counts, _lib.float_array(coef), _ptr(sums),
+                                                               _ptr(value), _stream()), "consistency_finish_ord")
             else:
-                _lib.check(lib.advchain_consistency_cw_fwd(
-                    _ptr(pred), int(pred.dtype == torch.bfloat16), _ptr(ref), int(ref.dtype == torch.bfloat16), _ptr(mask),
-                    _ptr(stats), _ptr(R), _ptr(slots), N, K, nd, dims, mch, int(ref_is_prob), int(want_edges), int(want_kl),
-                    _ptr(cw), _stream()), "consistency_cw_fwd")
-            if not det:
                 _lib.check(lib.advchain_consistency_finish(_ptr(slots), _lib.float_array(coef), _ptr(sums), _ptr(value), 1,
                                                            _stream()), "consistency_finish")
         except BaseException:
-            _forget_persistent(slots)
+            if slots is not None:
+                _forget_persistent(slots)
             raise
         if need_grad:
             ctx.save_for_backward(pred, ref, R, mask, stats)
@@ -1906,16 +1879,24 @@ class _Consistency(torch.autograd.Function):
         cw = ctx.cw
         family = "lp" if cw is None else "cw"
         weights = () if cw is None else (_ptr(cw),)         # (the cw entries: class_w in front of the stream)
+        fp32 = cw is None and pred.dtype == torch.float32 and ref.dtype == torch.float32
         for need, side in ((need_pred, "bwd"), (need_ref, "ref_bwd")):
             if not need:
                 continue
-            name = "consistency_%s_%s" % (family, side)
             out = torch.empty_like(pred if side == "bwd" else ref)     # (the operand's dtype)
-            _lib.check(getattr(lib, "advchain_" + name)(
-                _ptr(pred), int(pred.dtype == torch.bfloat16), _ptr(ref), int(ref.dtype == torch.bfloat16),
-                _ptr(stats), _ptr(R), _ptr(mask), _ptr(gs), _ptr(out), float(coef[0]), float(coef[1]),
-                float(coef[2]), float(coef[3]), is_gt, N, K, pred.dim() - 2, _lib.dims_array(pred.shape[2:]), mch,
-                *(weights + (_stream(),))), name)
+            tail = (_ptr(stats), _ptr(R), _ptr(mask), _ptr(gs), _ptr(out), float(coef[0]), float(coef[1]), float(coef[2]),
+                    float(coef[3]), is_gt, N, K, pred.dim() - 2, _lib.dims_array(pred.shape[2:]), mch)
+            if fp32 and side == "ref_bwd":
+                # two fp32 operands, no weights: the kernel of csrc/loss_ref.hip parks its intermediate in the fp32 output, where
+                # k_lp_ref_grad recomputes it (438 against 299 us at 32 x 20 x 256 x 256, profiles/r18/loss_fold/summary.md)
+                name = "consistency_ref_bwd"
+                lib.advchain_set_ref_grad_reg_max_k(int(REF_GRAD_REG_MAX_K))
+                rc = lib.advchain_consistency_ref_bwd(_ptr(pred), _ptr(ref), *(tail + (_stream(),)))
+            else:
+                name = "consistency_%s_%s" % (family, side)
+                rc = getattr(lib, "advchain_" + name)(_ptr(pred), int(pred.dtype == torch.bfloat16), _ptr(ref),
+                                                      int(ref.dtype == torch.bfloat16), *(tail + weights + (_stream(),)))
+            _lib.check(rc, name)
             if side == "bwd":
                 gpred = out
             else:
@@ -1932,34 +1913,24 @@ class _Consistency(torch.autograd.Function):
         need_pred, need_ref = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and ctx.ref_grad
         gs = _dev(gloss.reshape(1), "grad")
         lib = _lib.load()
-        gpred = gref = stats = None
-        if ctx.wide:
-            pred, ref, R, mask, stats = ctx.saved_tensors
-            N, K = pred.shape[:2]
-            if need_pred:
-                gpred = torch.empty_like(pred)
-                _lib.check(lib.advchain_consistency_wide_bwd(
-                    _ptr(pred), _ptr(ref), _ptr(stats), _ptr(R), _ptr(mask), _ptr(gs), _ptr(gpred),
-                    float(coef[0]), float(coef[1]), float(coef[2]), float(coef[3]), is_gt, N, K, pred.dim() - 2,
-                    _lib.dims_array(pred.shape[2:]), mch, _stream()), "consistency_wide_bwd")
-        else:
-            saved = ctx.saved_tensors
-            P, D, R, mask = saved[:4]                      # (fused: pred, ref, R, mask)
-            pred, ref = (P, D) if ctx.fused else (saved[4:6] if len(saved) > 4 else (None, None))
-            if need_pred:
-                N, K = P.shape[:2]
-                gpred = torch.empty_like(P)
-                entry = lib.advchain_consistency_fused_bwd if ctx.fused else lib.advchain_consistency_bwd
-                _lib.check(entry(_ptr(P), _ptr(D), _ptr(R), _ptr(mask), _ptr(gs), _ptr(gpred),
-                                 float(coef[0]), float(coef[1]), float(coef[2]), float(coef[3]),
-                                 is_gt, N, K, P.dim() - 2, _lib.dims_array(P.shape[2:]), mch, _stream()),
-                           "consistency_fused_bwd" if ctx.fused else "consistency_bwd")
+        gpred = gref = None
+        saved = ctx.saved_tensors
+        P, D, R, mask = saved[:4]                      # (fused: pred, ref, R, mask)
+        pred, ref = (P, D) if ctx.fused else (saved[4:6] if len(saved) > 4 else (None, None))
+        if need_pred:
+            N, K = P.shape[:2]
+            gpred = torch.empty_like(P)
+            entry = lib.advchain_consistency_fused_bwd if ctx.fused else lib.advchain_consistency_bwd
+            _lib.check(entry(_ptr(P), _ptr(D), _ptr(R), _ptr(mask), _ptr(gs), _ptr(gpred),
+                             float(coef[0]), float(coef[1]), float(coef[2]), float(coef[3]),
+                             is_gt, N, K, P.dim() - 2, _lib.dims_array(P.shape[2:]), mch, _stream()),
+                       "consistency_fused_bwd" if ctx.fused else "consistency_bwd")
         if need_ref:
             N, K = ref.shape[:2]
             gref = torch.empty_like(ref)
             lib.advchain_set_ref_grad_reg_max_k(int(REF_GRAD_REG_MAX_K))      # (process-wide in the library: the knob of this module)
             _lib.check(lib.advchain_consistency_ref_bwd(
-                _ptr(pred), _ptr(ref), _ptr(stats), _ptr(R), _ptr(mask), _ptr(gs), _ptr(gref),
+                _ptr(pred), _ptr(ref), None, _ptr(R), _ptr(mask), _ptr(gs), _ptr(gref),
                 float(coef[0]), float(coef[1]), float(coef[2]), float(coef[3]), is_gt, N, K, ref.dim() - 2,
                 _lib.dims_array(ref.shape[2:]), mch, _stream()), "consistency_ref_bwd")
         return gpred, gref, None, None, None, None, None

@@ -559,8 +559,12 @@ int advchain_consistency_fused_bwd(const float* pred, const float* ref, const fl
  * never materialised.  wide_bwd: grad_pred (N,K,dims) from pred, ref, stats and R (NULL: no edge terms) by the formula of
  * advchain_consistency_bwd, gs = *grad_scale (device scalar, NULL = 1); no atomics on grad_pred, so it is bit-reproducible.
  * pred / ref / grad_pred fp32 contiguous, any alignment (16-byte aligned tensors with a voxel count divisible by 4 take
- * 16-byte loads); N < 65536 (N == 0: ADVCHAIN_OK, no launch), fewer than 2^31 voxels, mask_channels 1 or K.  Capture-safe:
- * kernel launches on `stream` only.  Returns ADVCHAIN_OK or a negative code (advchain_last_error names the entry). */
+ * 16-byte loads; a lane owns the same 4 voxels either way, so no sum, and with it no value, depends on the alignment of a
+ * tensor); N < 65536 (N == 0: ADVCHAIN_OK, no launch), fewer than 2^31 voxels, mask_channels 1 or K.  Capture-safe: kernel
+ * launches on `stream` only.  Returns ADVCHAIN_OK or a negative code (advchain_last_error names the entry).
+ * These entries (and advchain_consistency_wide_fwd_partials / wide_fwd_ord below) ARE the lp entries further down with both
+ * storage flags 0 and no class weights -- the same kernels (loss_lp.hip), stats and R interchangeable with theirs -- under the
+ * fp32 signatures. */
 int advchain_consistency_wide_fwd(const float* pred, const float* ref, const float* mask, float* stats, float* R, float* sums,
                                   int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels, int ref_is_prob,
                                   int want_edges, int want_kl, void* stream);
@@ -595,7 +599,7 @@ int advchain_get_ref_grad_reg_max_k(void);
 
 /* low-precision storage (round 10, loss_lp.hip): the same loss and both of its gradients for logits stored in bf16 (a model
  * under autocast), every K from 1 to 65535, 2D and 3D.  pred / ref are read as fp32 (flag 0) or as raw bf16 words (flag 1),
- * independently; bf16 -> fp32 is exact and all arithmetic is the fp32 arithmetic of the wide entries, so lp_fwd computes the
+ * independently; bf16 -> fp32 is exact and all arithmetic is fp32 (the wide entries are these with both flags 0), so lp_fwd computes the
  * fp32 loss of the upcast operands.  mask, stats (N, 4, dims), R (N, 2(K-1), dims; NULL when no backward is needed) and the
  * slot sums are fp32 and have the layouts of advchain_consistency_wide_fwd (finish with advchain_consistency_finish); a
  * reference given as probabilities (ref_is_prob) is read in its own storage type as it is.  lp_bwd writes grad_pred in pred's
@@ -648,8 +652,9 @@ int advchain_consistency_cw_ref_bwd(const void* pred, int pred_bf16, const void*
  *              launch STORES its partial into its own cell (zeros included): no clearing, no atomics;
  *   stride   : capacity of a row, at least the family's *_fwd_partials(...) for the same arguments (host-only queries: the
  *              most workgroups a launch of the family has; `aligned16`: every tensor is 16-byte aligned, which selects the
- *              vector kernels; -1 for bad sizes; the fused query returns -2 where the fused entry does).  A buffer that is
- *              too small is an argument error and nothing is enqueued;
+ *              vector kernels -- accepted and IGNORED by the wide query, whose grids do not depend on alignment; -1 for bad
+ *              sizes; the fused query returns -2 where the fused entry does).  A buffer that is too small is an argument
+ *              error and nothing is enqueued;
  *   counts   : int32[4] in HOST memory, written by the entry: the number of cells of row r that the launches write
  *              (0: the row is not part of this evaluation -- no 'kl', no edges).
  * The same kernels as the default mode's, instantiated with a store in place of the atomic; R / P / D / stats are bit for bit

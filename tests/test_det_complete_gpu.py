@@ -279,9 +279,9 @@ def test_loss_value_is_ordered_in_every_forward_family(name):
     want = oracle_value(pred, ref, mask, cw)
     want_kl = oracle_value(pred, ref, mask, cw, ["kl"], [1.0])
     pred, ref, mask = pred.to(DEV), ref.to(DEV), mask.to(DEV)
-    entry = {"fused": "advchain_consistency_fused_fwd", "three": "advchain_consistency_fwd", "wide": "advchain_consistency_wide_fwd",
+    entry = {"fused": "advchain_consistency_fused_fwd", "three": "advchain_consistency_fwd", "wide": "advchain_consistency_lp_fwd",
              "lp": "advchain_consistency_lp_fwd", "cw": "advchain_consistency_cw_fwd"}[family]
-    ord_entry = "advchain_consistency_lp_fwd_ord" if family in ("lp", "cw") else entry + "_ord"
+    ord_entry = "advchain_consistency_lp_fwd_ord" if family in ("wide", "lp", "cw") else entry + "_ord"
     try:
         ops.set_deterministic(False)
         del lib.records[:]

@@ -137,7 +137,7 @@ def test_value_and_prediction_grad_do_not_move(K, dims):
         assert torch.equal(both[0], only[0]), (K, dims, mode)
 
 
-_PRED_SIDE = ("k_consistency_bwd", "k_loss_fused_bwd", "k_wide_bwd")
+_PRED_SIDE = ("k_consistency_bwd", "k_loss_fused_bwd", "k_lp_bwd")
 
 
 @pytest.mark.parametrize("dims", [(37, 52), (5, 6, 64)])

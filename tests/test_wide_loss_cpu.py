@@ -1,6 +1,6 @@
 """The consistency loss and the solver with more than 16 classes, as far as a machine without a GPU can check them: the
 host side (normalisers, no class cap, solver control flow) against the oracle through the TEST-ONLY operator backend, and
-the host-side argument checks of the two C entries of csrc/loss_wide.hip (no launch)."""
+the host-side argument checks of the two C entries of csrc/loss_lp.hip (no launch)."""
 import contextlib
 import ctypes
 import io

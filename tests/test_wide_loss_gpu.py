@@ -1,5 +1,5 @@
-"""The consistency loss for a run-time class count (csrc/loss_wide.hip: advchain_consistency_wide_fwd/bwd, taken from
-ops.WIDE_LOSS_MIN_K = 17 classes on) and the solver with a 20-class model.
+"""The consistency loss for a run-time class count (the fp32 kernels of csrc/loss_lp.hip, taken from ops.WIDE_LOSS_MIN_K = 17
+classes on) and the solver with a 20-class model.
 
 Tolerances are those of tests/test_ops_gpu.py::test_kl_term_in_every_kernel_variant: value 1e-7 + 2e-5 |v|, gradient 2e-5 of its
 maximum + 1e-10, against the CPU oracle in fp32 (whose own fp32-against-float64 spread at these class counts is 2.5e-7 / 6.9e-7:
@@ -153,6 +153,15 @@ def test_one_class_through_the_wide_path(dims):
         assert torch.isfinite(wide[1]).all()
 
 
+def off_by_4(t):
+    """A contiguous device copy of `t` that starts 4 bytes off a 16-byte boundary."""
+    flat = torch.empty(t.numel() + 1, device=DEV, dtype=t.dtype)
+    out = flat[1:].view(t.shape)
+    out.copy_(t)
+    assert out.data_ptr() % 16 == 4 and out.is_contiguous()
+    return out
+
+
 @pytest.mark.parametrize("dims", [(11, 20), (5, 6, 18)])
 def test_views_and_misaligned_tensors(dims):
     """A non-contiguous view (`x[..., 1:]`), its contiguous copy and a contiguous tensor that starts 4 bytes off a 16-byte
@@ -171,12 +180,6 @@ def test_views_and_misaligned_tensors(dims):
         v.backward()
         return float(v.detach())
 
-    def off_by_4(t):
-        flat = torch.empty(t.numel() + 1, device=DEV, dtype=t.dtype)
-        out = flat[1:].view(t.shape)
-        out.copy_(t)
-        assert out.data_ptr() % 16 == 4 and out.is_contiguous()
-        return out
     b = pc.to(DEV).requires_grad_(True)
     copy = (loss(b, rc.to(DEV), mc.to(DEV)), b.grad.cpu())
     B = pred.to(DEV).requires_grad_(True)
@@ -189,6 +192,39 @@ def test_views_and_misaligned_tensors(dims):
     _check(off, want, (dims, "misaligned"))
     assert torch.equal(view[1], copy[1]) and abs(view[0] - copy[0]) <= 1e-6 * abs(copy[0])
     assert torch.equal(off[1], copy[1])      # (one gradient kernel for both; the statistics pass differs in its load width only)
+
+
+@pytest.mark.parametrize("dims", [(11, 20), (5, 6, 18)])
+def test_deterministic_value_does_not_depend_on_alignment(dims):
+    """Deterministic mode, fp32, K = 20: the value and both gradients from 16-byte aligned operands are equal, bit for bit, to
+    those from copies that start 4 bytes off a 16-byte boundary -- a lane of the statistics pass owns the same 4 voxels with
+    16-byte loads and with scalar ones, so every sum has one order."""
+    from advchain_amd import ops
+    from advchain_amd.common.loss import calc_segmentation_consistency
+    pred, ref, mk, _ = _operands(20, dims)
+    mk = mk[:, :1].contiguous()
+    types, weights = ["mse", "kl", "contour"], [0.7, 1.3, 0.5]
+
+    def run(place):
+        a, b, m = place(pred).requires_grad_(True), place(ref).requires_grad_(True), place(mk)
+        v = calc_segmentation_consistency(a, b, types, weights, scales=[0], mask=m)
+        v.backward()
+        return v.detach().clone(), a.grad.clone(), b.grad.clone()
+
+    def aligned(t):
+        out = t.to(DEV)
+        assert out.data_ptr() % 16 == 0 and out.is_contiguous()
+        return out
+    was = ops.is_deterministic()
+    ops.set_deterministic(True)
+    try:
+        want, got = run(aligned), run(off_by_4)
+    finally:
+        ops.set_deterministic(was)
+    print("%s: value %.9g (aligned) %.9g (4 bytes off)" % (dims, float(want[0]), float(got[0])))
+    assert float(want[1].abs().max()) > 0 and float(want[2].abs().max()) > 0
+    for w, g, what in zip(want, got, ("value", "prediction.grad", "reference.grad")):
+        assert torch.equal(w, g), (dims, what)
 
 
 def test_grad_scale():

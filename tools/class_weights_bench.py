@@ -3,7 +3,7 @@ class_weights=None on the same operands, with device events:
 
   (a) weighted:   calc_segmentation_consistency(..., class_weights=w), w cycling through (0.25, 2.0, 0.0, 1.5, 0.5);
   (b) unweighted: calc_segmentation_consistency(..., class_weights=None) -- fp32 / fp32: the register kernels of csrc/loss.hip
-      up to 16 classes and csrc/loss_wide.hip + loss_ref.hip above; bf16 / bf16: the unweighted kernels of csrc/loss_lp.hip.
+      up to 16 classes and the unweighted fp32 kernels of csrc/loss_lp.hip above; bf16 / bf16: the unweighted kernels of csrc/loss_lp.hip.
 
 Both operands require grad (a teacher / student pair); one-channel mask, mse+kl+contour.  Two storage pairs: fp32 / fp32 and
 bf16 / bf16.  The paths alternate over --rounds; the best round of each is reported (median of --iters).  One JSON line per

@@ -19,7 +19,7 @@ sys.path.insert(0, ROOT)
 
 GROUPS = (("general-C warps (C = K)", ("k_grid_sample_fwd", "k_grid_sample_bwd", "k_affine_warp_fwd", "k_affine_warp_bwd")),
           ("passes around the int64 image (deterministic mode)", ("k_det_absmax", "k_det_convert", "k_det_convert_bits")),
-          ("wide loss", ("k_wide_stats", "k_wide_edge", "k_wide_bwd", "k_consistency_finish")))
+          ("wide loss", ("k_lp_stats", "k_lp_edge", "k_lp_bwd", "k_consistency_finish")))
 
 
 def run(args):

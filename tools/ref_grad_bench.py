@@ -34,7 +34,7 @@ from wide_loss_bench import PEAK_BPS, aten_loss, coefficients      # noqa: E402
 
 MIX = "mse+kl+contour"
 SHAPES = [(32, 4, 256, 256), (32, 20, 256, 256), (4, 4, 128, 128, 64)]
-PRED_SIDE = ("k_consistency_bwd", "k_loss_fused_bwd", "k_wide_bwd")
+PRED_SIDE = ("k_consistency_bwd", "k_loss_fused_bwd", "k_lp_bwd")
 
 
 def selected(spec):

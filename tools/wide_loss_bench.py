@@ -1,4 +1,4 @@
-"""Times the consistency loss for a run-time class count (csrc/loss_wide.hip, through ops.consistency_sums), forward and
+"""Times the consistency loss for a run-time class count (csrc/loss_lp.hip, through ops.consistency_sums), forward and
 backward separately with device events, against (a) an ATen expression of the same loss written out below (the outside
 yardstick) and (b), for K <= 16, the register / three-kernel path of csrc/loss.hip on the same tensors in the same process
 (ops.WIDE_LOSS_MIN_K = 17 against = 2, alternating).  One JSON line per case; --out DIR keeps them.
@@ -154,7 +154,7 @@ def run(args):
             json.dump(rows, f, indent=1)
 
 
-KERNELS = {"k_wide_stats": "fwd", "k_wide_edge": "fwd", "k_wide_bwd": "bwd", "k_consistency_finish": None}
+KERNELS = {"k_lp_stats": "fwd", "k_lp_edge": "fwd", "k_lp_bwd": "bwd", "k_consistency_finish": None}
 
 
 def summarize(stats_csv, out, spec):
