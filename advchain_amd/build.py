@@ -31,8 +31,6 @@ PER_FILE_FLAGS = {
     "jacobian.hip": ["-ffp-contract=off"],              # the same stencils and determinant: map and statistics agree bitwise
     "seg_dice.hip": ["-ffp-contract=off"],              # fp32 / bf16 and vector / scalar instantiations round alike (bitwise)
 }
-if os.environ.get("ADVCHAIN_BUILD_SLP_EVERYWHERE"):     # A/B knob: the compiler default for every source
-    PER_FILE_FLAGS = {}
 
 
 def sources():

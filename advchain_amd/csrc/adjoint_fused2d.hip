@@ -22,7 +22,6 @@
 //     never read by a valid output) with every LDS index clamped;
 //   * exact bounds only: the caller guarantees the displacement of phi_0..phi_{k-1} (read back from the forward's
 //     measurement) -- no overflow list, no device-side check needed here.
-#include <stdlib.h>
 #include "sampler_common.h"
 
 namespace advchain {
@@ -251,8 +250,7 @@ using namespace advchain;
 // pointers); gk, g0 and the fields must not alias.
 int advchain_adjoint_fused2d_launch(const float* gk, const float* phi0, const float* fields, float* g0, int64_t N, Dims d, int k,
                                     int32_t* workspace, hipStream_t st) {
-  static const bool off = getenv("ADVCHAIN_NO_FUSE2D_BWD") != nullptr;   // A/B knob
-  if (off || d.s0 != 1 || k < 2 || k > kFuseBwdMax || !workspace) return ADVCHAIN_ERR_UNSUPPORTED;
+  if (d.s0 != 1 || k < 2 || k > kFuseBwdMax || !workspace) return ADVCHAIN_ERR_UNSUPPORTED;
   if ((d.s2 & 3) != 0 || d.s2 < 8) return ADVCHAIN_ERR_UNSUPPORTED;
   const uintptr_t al = reinterpret_cast<uintptr_t>(gk) | reinterpret_cast<uintptr_t>(phi0) | reinterpret_cast<uintptr_t>(fields) |
                        reinterpret_cast<uintptr_t>(g0);

@@ -18,7 +18,6 @@
 //            lane keeps 2H+1 partial sums (its sample's deposits on x-H..x+H), which 2H whole-wave DPP shifts fold
 //            into the owning lanes at the end.
 // The overflow list (normally empty) is drained by a second launch with global atomics, all corners of a sample.
-#include <stdlib.h>
 #include "sampler_common.h"
 
 namespace advchain {
@@ -627,10 +626,9 @@ int advchain_warp_adjoint_march_launch(const float* gout, const float* in, const
 // Workspace protocol identical to advchain_scatter_tiled_launch (header [0] overflow count, [3] max|result|).
 int advchain_self_adjoint_gather_launch(const float* gout, const float* phi, float* gphi, int64_t N, int ndim, Dims d,
                                         int32_t* workspace, int chain, int halo, hipStream_t st) {
-  static const bool off = getenv("ADVCHAIN_NO_ADJOINT_GATHER") != nullptr;   // A/B knob
   const bool strict = halo < 0;     // negative: exact bound |halo|, guaranteed by the caller
   if (strict) halo = -halo;
-  if (off || !workspace || halo < 1 || !gather_shape_ok(d)) return ADVCHAIN_ERR_UNSUPPORTED;
+  if (!workspace || halo < 1 || !gather_shape_ok(d)) return ADVCHAIN_ERR_UNSUPPORTED;
   if (strict && ndim == 3 && halo == 1) {
     const int rc = advchain_self_adjoint_march_launch(gout, phi, gphi, N, d, workspace, st);
     if (rc != ADVCHAIN_ERR_UNSUPPORTED) return rc;
@@ -655,10 +653,9 @@ int advchain_self_adjoint_gather_launch(const float* gout, const float* phi, flo
 int advchain_warp_adjoint_gather_launch(const float* gout, const float* in, const float* grid, float* gin, float* ggrid,
                                         int64_t N, int64_t C, int ndim, Dims d, int padding, int clamp_grid,
                                         int32_t* workspace, int halo, hipStream_t st) {
-  static const bool off = getenv("ADVCHAIN_NO_ADJOINT_GATHER") != nullptr;   // A/B knob
   const bool strict = halo < 0;     // negative: exact bound |halo|, guaranteed by the caller
   if (strict) halo = -halo;
-  if (off || !workspace || halo < 1 || !gin || padding == PAD_REFLECTION) return ADVCHAIN_ERR_UNSUPPORTED;
+  if (!workspace || halo < 1 || !gin || padding == PAD_REFLECTION) return ADVCHAIN_ERR_UNSUPPORTED;
   if (!gather_shape_ok(d)) return ADVCHAIN_ERR_UNSUPPORTED;
   if (C != 1 && C != 4) return ADVCHAIN_ERR_UNSUPPORTED;
   if (strict && ndim == 3 && halo == 1) {

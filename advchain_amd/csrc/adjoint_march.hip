@@ -30,7 +30,6 @@
 // Contract: the caller guarantees |unnormalize(grid) - s| < 1 voxel for every sample (ops.squaring_halo / ops.warp_halo
 // measure it in the forward).  Shapes outside the fast form (rows longer than 64 voxels, rows not a multiple of 4,
 // misaligned bases) return ADVCHAIN_ERR_UNSUPPORTED and the caller keeps the tile kernel of adjoint_gather.hip.
-#include <stdlib.h>
 #include <type_traits>
 #include "sampler_common.h"
 
@@ -39,10 +38,7 @@ namespace advchain {
 // MODE: 0 = zeros padding, positions as given; 1 = positions clipped to [0, S-1] (clamp_grid), zero coordinate gradient
 // beyond the border; 2 = border padding (clipped, zero coordinate gradient AT and beyond the border)
 enum { kMarchFree = 0, kMarchClamp = 1, kMarchBorder = 2 };
-// timing experiments only (ADVCHAIN_MARCH_DEBUG, results are wrong): switch a phase off
-constexpr int kDbgNoA = 16, kDbgNoB = 32, kDbgNoStore = 64, kDbgNoStage = 128;
 constexpr int kSegOwn = 56;       // owned lanes of an x segment (rows longer than 64 voxels)
-constexpr int kMarchXcd = 256;    // workgroup -> tile map that keeps halo-sharing tiles on one XCD (one L2)
 
 // WIDE (rows of 68 .. 80 voxels, cfg-5's 160 x 160 x 80): the x fold through whole-wave DPP shifts ties a lane to an x,
 // so a row cannot be cut into flat items as in the forward sampler.  Instead three A waves own RPW rows each, lanes <-> x
@@ -62,11 +58,7 @@ struct MarchCfg {
   // 4 zeros | 64 (80) voxels; the 4 zeros to the RIGHT of a row are the left zeros of the next row in memory (every staged
   // row of every slot is followed by another one; the last one by a 4-float pad): 68 instead of 72 floats per row is what lets
   // three workgroups of the self-composition share a CU's 160 KiB (53 KiB each)
-#ifdef ADVCHAIN_MARCH_PAD8      // A/B build: rows with their own right zeros (72 / 88 floats)
-  static constexpr int PITCH = WIDE ? kWidePW + 8 : 72;
-#else
   static constexpr int PITCH = WIDE ? kWidePW + 4 : 68;
-#endif
   static constexpr int QPR = WIDE ? kWidePW / 4 : 16;           // 16-byte staging items per row
   static_assert(!WIDE || NW == 4, "wide form: three A waves and one B wave");
   static constexpr bool HAS_IMG = GG && !SELF;
@@ -82,7 +74,7 @@ struct MarchCfg {
   static constexpr size_t LDS = (size_t)(ROWS_END + NW * TRW) * sizeof(float);
   // per SIMD: 128 / 168 / 256 VGPRs (512-thread blocks: 2 waves per SIMD each).  Without the SLP vectoriser (build.py) the
   // self-composition needs 152: three workgroups a CU
-  static constexpr int MIN_WAVES = (C == 1) ? 4 : (SELF ? (RPW == 1 && NW == 8 ? 4 : 3) : 2);
+  static constexpr int MIN_WAVES = (C == 1) ? 4 : (SELF ? 3 : 2);
   static_assert(R * QPR <= NT, "one staging item (4 voxels of one row, all channels) per thread");
   static_assert(!SELF || C == 3, "the self-composition carries 3 channels");
 };
@@ -92,7 +84,7 @@ __device__ __forceinline__ float march_unnormalize(float g, int S) { return ((g 
 template <int C, bool SELF, bool GG, int MODE, int NW, int RPW, bool WIDE = false>
 __global__ void __launch_bounds__(NW * 64, (MarchCfg<C, SELF, GG, NW, RPW, WIDE>::MIN_WAVES))
 k_adjoint_march(const float* __restrict__ gout, const float* __restrict__ in, const float* __restrict__ grid,
-                float* __restrict__ gin, float* __restrict__ ggrid, Dims d, int n1, int zc, int flags,
+                float* __restrict__ gin, float* __restrict__ ggrid, Dims d, int n1, int zc,
                 int32_t* __restrict__ untracked, int nseg) {
   using G = MarchCfg<C, SELF, GG, NW, RPW, WIDE>;
   constexpr int R = G::R, TY = G::TY, RC = G::RING_CH, LC = G::LATE_CH, P = G::PITCH, PS = G::PS, LS = G::LS;
@@ -108,7 +100,7 @@ k_adjoint_march(const float* __restrict__ gout, const float* __restrict__ in, co
   // that the halo rows / planes two neighbouring workgroups both stage are served by the same L2
   int tile = blockIdx.x + gridDim.x * blockIdx.y;
   const int tiles = gridDim.x * gridDim.y;
-  if ((flags & kMarchXcd) && (tiles & 7) == 0) tile = (tile & 7) * (tiles >> 3) + (tile >> 3);
+  if ((tiles & 7) == 0) tile = (tile & 7) * (tiles >> 3) + (tile >> 3);
   const int n = tile / (int)gridDim.x;
   int rem = tile - n * (int)gridDim.x;
   // rows longer than 64 voxels: x segments of 56 owned lanes with 4 halo lanes either side (16-byte aligned staging)
@@ -324,7 +316,7 @@ k_adjoint_march(const float* __restrict__ gout, const float* __restrict__ in, co
     const bool fin = zt >= za && zt < zb;
     {
       // ---- phase B: deposits of sample plane zp on the target planes zp-1, zp, zp+1
-      if (zp >= 0 && zp < d.s0 && !(flags & kDbgNoB)) {
+      if (zp >= 0 && zp < d.s0) {
 #pragma unroll
         for (int i = 0; i < RPW + 2; ++i) {
           const int r = i;                        // staged row of the sample past the lane's own_row0; sample y = y0 - 1 + own_row0 + r
@@ -382,7 +374,7 @@ k_adjoint_march(const float* __restrict__ gout, const float* __restrict__ in, co
     }
 
     // ---- phase A: coordinate-path gradient of the owned samples of plane zp (corner values from the ring)
-    const bool do_a = (SELF || GG) && zp >= za && zp < zb && !(flags & kDbgNoA);
+    const bool do_a = (SELF || GG) && zp >= za && zp < zb;
     if constexpr (!SELF && GG) {
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
@@ -486,9 +478,9 @@ k_adjoint_march(const float* __restrict__ gout, const float* __restrict__ in, co
         fetch_ring(zp + 3, pr);
         fetch_late(zp + 2, pl);
       }
-      if (!(flags & kDbgNoStore)) store_rows(vals, dst, row_base, ok);
+      store_rows(vals, dst, row_base, ok);
     } else {
-      if (!(flags & kDbgNoStore)) store_rows(vals, dst, row_base, ok);
+      store_rows(vals, dst, row_base, ok);
       if (has_item) {
         if (zp + 2 <= zb) commit_ring(zp + 2, pr);
         if (zp + 1 <= zb) commit_late(zp + 1, pl);
@@ -510,8 +502,6 @@ k_adjoint_march(const float* __restrict__ gout, const float* __restrict__ in, co
 using namespace advchain;
 
 static int march_zc(const Dims& d, int64_t N, int ty) {
-  static const int forced = getenv("ADVCHAIN_MARCH_ZC") ? atoi(getenv("ADVCHAIN_MARCH_ZC")) : 0;   // A/B knob (0: the rule below)
-  if (forced > 0) return forced;
   // enough workgroups to fill 256 CUs four deep, but chunks no shorter than 8 planes (2 of ZC + 2 steps are halo work)
   const int64_t cols = N * ((d.s1 + ty - 1) / ty);
   int zc = d.s0;
@@ -524,32 +514,25 @@ static void launch_march(const float* gout, const float* in, const float* grid, 
                          Dims d, int32_t* ws, hipStream_t st) {
   using G = MarchCfg<C, SELF, GG, NW, RPW, WIDE>;
   auto kern = k_adjoint_march<C, SELF, GG, MODE, NW, RPW, WIDE>;
-  // occupancy experiment (round 6, profiles/r06/f1_3d/): see launch_fwd_march (sample_march.hip)
-  static const size_t lds_pad = getenv("ADVCHAIN_MARCH_LDS_PAD") ? (size_t)atoi(getenv("ADVCHAIN_MARCH_LDS_PAD")) * 1024 : 0;
   static bool attr_set = false;
-  if (G::LDS + lds_pad > 65536 && !attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(G::LDS + lds_pad));
+  if (G::LDS > 65536 && !attr_set) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS);
     attr_set = true;
   }
-  static const int dbg = (getenv("ADVCHAIN_MARCH_DEBUG") ? atoi(getenv("ADVCHAIN_MARCH_DEBUG")) : 0) |
-                         (kMarchXcd);
   const int n1 = (d.s1 + G::TY - 1) / G::TY;
   const int nseg = (WIDE || d.s2 <= 64) ? 1 : (d.s2 + kSegOwn - 1) / kSegOwn;
   const int zc = march_zc(d, N * nseg, G::TY);
   const int n0 = (d.s0 + zc - 1) / zc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(nseg * n1 * n0), (unsigned)N), dim3(G::NT), G::LDS + lds_pad, st, gout, in, grid, gin, ggrid, d,
-                     n1, zc, dbg, SELF ? ws : (int32_t*)nullptr, nseg);
+  hipLaunchKernelGGL(kern, dim3((unsigned)(nseg * n1 * n0), (unsigned)N), dim3(G::NT), G::LDS, st, gout, in, grid, gin, ggrid, d,
+                     n1, zc, SELF ? ws : (int32_t*)nullptr, nseg);
 }
 
 // rows of 68 .. 80 voxels: the A / B wave form (MarchCfg, WIDE)
 static bool march_wide(const Dims& d) {
-  static const bool off = getenv("ADVCHAIN_NO_WIDE_ADJOINT") != nullptr;   // A/B knob
-  return !off && d.s2 > 64 && d.s2 <= kWidePW;
+  return d.s2 > 64 && d.s2 <= kWidePW;
 }
 
 static bool march_shape_ok(const Dims& d, const void* a, const void* b, const void* c, const void* e, const void* f) {
-  static const bool off = getenv("ADVCHAIN_NO_MARCH_ADJOINT") != nullptr;   // A/B knob
-  if (off) return false;
   const uintptr_t al = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
                        reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(f);
   return d.s2 >= 8 && (d.s2 & 3) == 0 && (al & 15) == 0 && d.s0 >= 2 && d.voxels() * 4 < (1ll << 31);
@@ -559,11 +542,9 @@ static bool march_shape_ok(const Dims& d, const void* a, const void* b, const vo
 int advchain_self_adjoint_march_launch(const float* gout, const float* phi, float* gphi, int64_t N, Dims d,
                                        int32_t* workspace, hipStream_t st) {
   if (!march_shape_ok(d, gout, phi, gphi, nullptr, nullptr)) return ADVCHAIN_ERR_UNSUPPORTED;
-  static const int rpw = 2;   // measured optimum (was a tuning knob until round 4)
+  // two rows per wave: the measured optimum of {4 x 1, 4 x 2, 8 x 1} waves x rows (round 4)
   if (march_wide(d)) launch_march<3, true, false, kMarchBorder, 4, 2, true>(gout, phi, phi, gphi, nullptr, N, d, workspace, st);
-  else if (rpw == 2) launch_march<3, true, false, kMarchBorder, 4, 2>(gout, phi, phi, gphi, nullptr, N, d, workspace, st);
-  else if (rpw == 8) launch_march<3, true, false, kMarchBorder, 8, 1>(gout, phi, phi, gphi, nullptr, N, d, workspace, st);
-  else launch_march<3, true, false, kMarchBorder, 4, 1>(gout, phi, phi, gphi, nullptr, N, d, workspace, st);
+  else launch_march<3, true, false, kMarchBorder, 4, 2>(gout, phi, phi, gphi, nullptr, N, d, workspace, st);
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
 }

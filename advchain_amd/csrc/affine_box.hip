@@ -701,10 +701,7 @@ k_affine_box_gin(const float* __restrict__ gout, const float* __restrict__ theta
 
 using namespace advchain;
 
-static const bool g_no_affine_box = getenv("ADVCHAIN_NO_AFFINE_BOX") != nullptr;   // A/B knob: direct-gather kernels
-
 static inline bool box_shape_ok(const Dims& d, const void* a, const void* b, const void* c) {
-  if (g_no_affine_box) return false;
   if (d.s2 % 4 != 0 || d.s2 < 4) return false;
   return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
 }
@@ -742,8 +739,9 @@ int advchain_affine_box_gtheta_launch(const float* gout, const float* in, const 
 // its box of grad_out once more for the maximum: 15 of 112 us at 4 x 4 x 128 x 128 x 64).
 bool advchain_affine_box_gin_launch(const float* gout, const float* theta, const float* geo, const int* mode, float* gin,
                                     int64_t N, int64_t C, int ndim, Dims d, hipStream_t st, const float* tilemax) {
-  static const bool no_gin = getenv("ADVCHAIN_NO_AFFINE_BOX_GIN") != nullptr;   // A/B knob: the lattice gather of sampler.hip
-  if (no_gin || g_no_affine_box || C > 4) return false;
+  // the documented precision escape: the float lattice gather of sampler.hip instead of the fixed-point box
+  static const bool no_gin = getenv("ADVCHAIN_NO_AFFINE_BOX_GIN") != nullptr;
+  if (no_gin || C > 4) return false;
   dim3 b(kBlock);
   if (ndim == 3) {
     dim3 g(box_tiles<3, 8>(d), (unsigned)N);

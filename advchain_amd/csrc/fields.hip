@@ -1588,8 +1588,7 @@ static int tp_interp_fwd_launch(const float* coef, float* out, const int32_t* it
   ADVCHAIN_CHECK_ARG(full.voxels() < (1ll << 31), "tp_interp_fwd: volume too large");
   ADVCHAIN_CHECK_ARG(T.a[2].g <= kTpMaxLds, "tp_interp_fwd: coefficient row too long");
   dim3 grid((unsigned)((full.s1 + kTpChunk - 1) / kTpChunk), (unsigned)full.s0, (unsigned)planes);
-  static const bool no_planes = getenv("ADVCHAIN_NO_TP_PLANES") != nullptr;   // A/B knob
-  if (!no_planes && full.s0 >= 2 * kTpZB && T.a[0].B == 2 && T.a[1].B == 2 && T.a[2].B == 2 && kTpChunk * T.a[2].g <= kTpMaxLds) {
+  if (full.s0 >= 2 * kTpZB && T.a[0].B == 2 && T.a[1].B == 2 && T.a[2].B == 2 && kTpChunk * T.a[2].g <= kTpMaxLds) {
     // 3D linear upsampling: kTpZB planes per workgroup, pipelined
     dim3 gp(grid.x, (unsigned)((full.s0 + kTpZB - 1) / kTpZB), (unsigned)planes);
     *nwg = (int64_t)gp.x * gp.y * gp.z;
@@ -1661,8 +1660,7 @@ int advchain_tp_interp_fwd_smoothed_pair(const float* vel, float* s1, float* out
   ADVCHAIN_CHECK_ARG(P >= 0 && 2 * P < 65536 && C >= 1, "tp_interp_fwd_smoothed_pair: bad planes/C");
   BandTables T;
   ADVCHAIN_CHECK_ARG(unpack_tables(itab, ftab, S, g, B, T), "tp_interp_fwd_smoothed_pair: bad band tables");
-  static const bool off = getenv("ADVCHAIN_NO_TP_GS_FUSE") != nullptr;   // A/B knob
-  if (off || S[0] != 1 || g[0] != 1 || g[1] * g[2] > kGsFuseMax || T.a[2].g > kTpMaxLds) return ADVCHAIN_ERR_UNSUPPORTED;
+  if (S[0] != 1 || g[0] != 1 || g[1] * g[2] > kGsFuseMax || T.a[2].g > kTpMaxLds) return ADVCHAIN_ERR_UNSUPPORTED;
   if (P == 0) return ADVCHAIN_OK;
   Dims full{(int)S[0], (int)S[1], (int)S[2]};
   ADVCHAIN_CHECK_ARG(full.voxels() < (1ll << 31), "tp_interp_fwd_smoothed_pair: volume too large");
@@ -1714,10 +1712,9 @@ int advchain_band_reduce_axis(const float* in, const float* in2, float* out, con
     ADVCHAIN_LAUNCH_CHECK();
     return ADVCHAIN_OK;
   }
-  static const bool no_slab = getenv("ADVCHAIN_NO_BAND_SLAB") != nullptr;   // A/B knob: one thread per output, taps from global memory
-  // (small problems only -- one thread per output leaves cfg-2's y pass with 128 workgroups walking 40 dependent taps:
+  // the slab form (small problems only -- one thread per output leaves cfg-2's y pass with 128 workgroups walking 40 dependent taps:
   // 14.4 -> 8.3 us; with 3 k+ workgroups, the 3D passes, the per-thread kernel is 2-4 % faster)
-  if (!no_slab && total <= 131072 && inner > 1 && inner % 4 == 0 && aligned && outer < (1ll << 31) && (int64_t)A.S * 5 <= kBrSlabFloats) {
+  if (total <= 131072 && inner > 1 && inner % 4 == 0 && aligned && outer < (1ll << 31) && (int64_t)A.S * 5 <= kBrSlabFloats) {
     int IC = (int)inner;                       // inner columns per workgroup: the slab S x (IC + 1) within 48 KiB
     while ((int64_t)A.S * (IC + 1) > kBrSlabFloats) IC = (IC / 2 + 3) / 4 * 4;
     const int chunks = (int)((inner + IC - 1) / IC);
@@ -1965,13 +1962,12 @@ int advchain_gauss_axis(const float* in, float* out, const float* aux, int64_t p
                                        reinterpret_cast<uintptr_t>(aux)) & 15) == 0;
   dim3 grid(advchain_blocks(v4 ? total / 4 : total, kBlock));
   int riw = (v4 && d.s2 >= 4 && 64 % (d.s2 / 4) == 0 && (total / 4) % 64 == 0) ? 1 : 0;   // x rows aligned to waves
-  static const bool no_riw2 = false, no_zmarch = getenv("ADVCHAIN_NO_GAUSS_ZMARCH") != nullptr;   // A/B knob
-  if (!riw && v4 && axis == 2 && d.s2 >= 8 && d.s2 / 4 <= 64 && !no_riw2) {   // rows that do not divide a wave: whole rows per wave
+  if (!riw && v4 && axis == 2 && d.s2 >= 8 && d.s2 / 4 <= 64) {   // rows that do not divide a wave: whole rows per wave
     riw = 2;
     const int64_t rows = total / d.s2, rpw = 64 / (d.s2 / 4);
     grid = dim3(advchain_blocks(((rows + rpw - 1) / rpw) * 64, kBlock));
   }
-  if (v4 && axis == 0 && d.s0 >= 32 && !no_zmarch) {   // z pass of a volume: marching form
+  if (v4 && axis == 0 && d.s0 >= 32) {   // z pass of a volume: marching form
     const int zc = 27;                                   // 3 rounds of 9 outputs: 1.3 loads per output
     const int nchunk = (d.s0 + zc - 1) / zc;
     const int64_t threads = planes * nchunk * d.s1 * (d.s2 / 4);
@@ -2020,8 +2016,7 @@ int advchain_gauss_axis(const float* in, float* out, const float* aux, int64_t p
 // The shapes advchain_gauss_xy takes (pointer alignment aside): for callers that must know before they enqueue anything
 // (the composite entries of demons_compose.cpp).
 bool advchain_gauss_xy_takes(int ndim, const int64_t* dims, int64_t planes) {
-  static const bool off = getenv("ADVCHAIN_NO_GAUSS_XY") != nullptr;   // A/B knob (the one advchain_gauss_xy reads)
-  if (off || !fdims_ok(ndim, dims)) return false;
+  if (!fdims_ok(ndim, dims)) return false;
   const Dims d = fmake_dims(ndim, dims);
   if ((d.s2 & 3) != 0 || d.s2 < 8 || d.s2 > 512 || d.s1 < 8 || planes > 65535 || d.s0 > 65535) return false;
   int TY = 32;
@@ -2042,8 +2037,7 @@ int advchain_gauss_xy(const float* in, float* out, const float* aux, int64_t pla
   ADVCHAIN_CHECK_ARG(C >= 1 && C <= 3 && pre >= 0 && pre <= 2 && post >= 0 && post <= 2 && (post != 2 || aux), "gauss_xy: bad C/pre/post");
   ADVCHAIN_CHECK_ARG(post == 0 || ndim == 2, "gauss_xy: post belongs to the last axis");
   const Dims d = fmake_dims(ndim, dims);
-  static const bool off = getenv("ADVCHAIN_NO_GAUSS_XY") != nullptr;   // A/B knob
-  if (off || (d.s2 & 3) != 0 || d.s2 < 8 || d.s2 > 512 || d.s1 < 8 || planes > 65535 || d.s0 > 65535 ||
+  if ((d.s2 & 3) != 0 || d.s2 < 8 || d.s2 > 512 || d.s1 < 8 || planes > 65535 || d.s0 > 65535 ||
       ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(aux) |
         reinterpret_cast<uintptr_t>(in_hi)) & 15) != 0)
     return ADVCHAIN_ERR_UNSUPPORTED;

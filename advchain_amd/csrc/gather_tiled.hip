@@ -8,7 +8,6 @@
 // workgroup), then every thread takes its taps from LDS (ds_read, ~100 clk latency instead of ~2 us) and writes
 // 4 consecutive voxels with one 16-byte store.  Corners outside the staged region (displacement beyond the halo)
 // fall back to global gathers, so results do not depend on the halo size.
-#include <stdlib.h>
 #include "sampler_common.h"
 
 namespace advchain {
@@ -207,19 +206,13 @@ k_sample_tiled(const float* __restrict__ in, const float* __restrict__ grid, flo
 
 using namespace advchain;
 
-static bool choose_gtile(int ndim, const Dims& d, int C, int halo_hint, GTile& tc) {
-  static const int h3 = 1;   // measured optimum (was a tuning knob until round 4)
-  static const int h2 = 8;
+// 3D only: in 2D (4 corners) the direct 4-chain gather kernels measured faster, and no 2D tile kernel is built
+static bool choose_gtile(const Dims& d, int C, int halo_hint, GTile& tc) {
+  constexpr int h3 = 1;      // measured optimum (round 4): the halo where the caller gives none
   if (d.s2 < 8 || d.s2 >= (1 << 23) || (int64_t)d.s0 * d.s1 >= (1 << 23)) return false;   // 24-bit index products
-  static const bool tiles_2d = false;
-  if (ndim == 2 && !tiles_2d) return false;   // measured: in 2D (4 corners) the direct 4-chain gather kernels are faster
-  int h = ndim == 3 ? h3 : h2;
-  if (halo_hint > 0) h = halo_hint;
-  static const int t0_3 = 2;   // measured: small tiles (more resident workgroups) beat low halo amplification
-  static const int t1_3 = 8;
-  static const int t1_2 = 16;
-  if (ndim == 3) { tc.t0 = t0_3; tc.t1 = t1_3; tc.h0 = tc.h1 = h; }
-  else { tc.t0 = 1; tc.t1 = t1_2; tc.h0 = 0; tc.h1 = h; }
+  const int h = halo_hint > 0 ? halo_hint : h3;
+  tc.t0 = 2; tc.t1 = 8;      // measured: small tiles (more resident workgroups) beat low halo amplification
+  tc.h0 = tc.h1 = h;
   if (d.s2 <= 96) { tc.t2 = d.s2; tc.h2 = 0; }     // whole rows: no x halo
   else { tc.t2 = 64; tc.h2 = (h + 3) / 4 * 4; }
   if (tc.t1 > d.s1) tc.t1 = d.s1;
@@ -239,14 +232,14 @@ static bool choose_gtile(int ndim, const Dims& d, int C, int halo_hint, GTile& t
   return true;
 }
 
-template <int DIM, int PAD, bool SELF>
+template <int PAD, bool SELF>
 static bool launch_sample_c(int C, dim3 g, size_t lds, hipStream_t st, const float* in, const float* grid, float* out,
                             const float* phi0, Dims d, GTile tc, int clamp_grid, int final_mode, float* disp_out, int unaligned) {
-#define LAUNCH(C_) hipLaunchKernelGGL((k_sample_tiled<DIM, PAD, C_, SELF>), g, dim3(kBlock), lds, st, in, grid, out, phi0, d, tc, clamp_grid, final_mode, disp_out, unaligned)
+#define LAUNCH(C_) hipLaunchKernelGGL((k_sample_tiled<3, PAD, C_, SELF>), g, dim3(kBlock), lds, st, in, grid, out, phi0, d, tc, clamp_grid, final_mode, disp_out, unaligned)
   switch (C) {
     case 1: if constexpr (!SELF) { LAUNCH(1); return true; } return false;
-    case 2: if constexpr (!SELF || DIM == 2) { LAUNCH(2); return true; } return false;
-    case 3: if constexpr (!SELF || DIM == 3) { LAUNCH(3); return true; } return false;
+    case 2: if constexpr (!SELF) { LAUNCH(2); return true; } return false;
+    case 3: LAUNCH(3); return true;
     case 4: if constexpr (!SELF) { LAUNCH(4); return true; } return false;
     default: return false;
   }
@@ -270,11 +263,8 @@ int advchain_sample_ring_launch(const float* in, const float* grid, float* out, 
 // below a voxel, 116 against 465 at 4 voxels).  `hint` = the caller's displacement estimate in voxels, rounded up
 // (0 = unknown): a performance hint, results do not depend on it.
 static bool march_forward_pays(bool self, int64_t C, const Dims& d, int hint) {
-  static const bool always = false;   // measured optimum (was a tuning knob until round 4): the round-2 policy before the hint
-  if (always) return true;
-  static const bool no_flat = getenv("ADVCHAIN_NO_FLAT_FWD") != nullptr;   // A/B knob
-  static const int flat_hint_max = 1;   // measured optimum (was a tuning knob until round 4)
-  if (d.s2 > 64 && d.s2 <= 128 && !no_flat) return hint <= flat_hint_max;   // lane <-> flat voxel (k_sample_march_flat): no idle lanes
+  constexpr int flat_hint_max = 1;      // measured optimum (round 4)
+  if (d.s2 > 64 && d.s2 <= 128) return hint <= flat_hint_max;   // lane <-> flat voxel (k_sample_march_flat): no idle lanes
   if (d.s2 > 64) return !self && C == 4 && hint <= 1;
   return hint <= 1;
 }
@@ -282,36 +272,28 @@ static bool march_forward_pays(bool self, int64_t C, const Dims& d, int hint) {
 int advchain_sample_tiled_launch(bool self, const float* in, const float* grid, float* out, const float* phi0,
                                  int64_t N, int64_t C, int ndim, Dims d, int padding, int clamp_grid, int final_mode,
                                  int halo, float* disp_out, hipStream_t st, int disp_hint) {
-  static const bool off = getenv("ADVCHAIN_NO_GATHER_TILES") != nullptr;   // A/B knob
-  if (off || C < 1 || C > 4) return ADVCHAIN_ERR_UNSUPPORTED;
-  if (ndim == 3 && march_forward_pays(self, C, d, disp_hint)) {
+  if (ndim != 3 || C < 1 || C > 4) return ADVCHAIN_ERR_UNSUPPORTED;
+  if (march_forward_pays(self, C, d, disp_hint)) {
     const int rc = advchain_sample_march_launch(self, in, grid, out, phi0, N, C, d, padding, clamp_grid, final_mode, disp_out, st);
     if (rc != ADVCHAIN_ERR_UNSUPPORTED) return rc;
   }
-  if (ndim == 3 && !self && C == 1 && disp_hint >= 2) {   // 2 .. 4 voxels: the ring of 2H+2 planes (sample_ring.hip)
+  if (!self && C == 1 && disp_hint >= 2) {   // 2 .. 4 voxels: the ring of 2H+2 planes (sample_ring.hip)
     const int rc = advchain_sample_ring_launch(in, grid, out, N, d, padding, clamp_grid, disp_hint, st);
     if (rc != ADVCHAIN_ERR_UNSUPPORTED) return rc;
   }
   const int unaligned = (reinterpret_cast<uintptr_t>(in) & 15) != 0 || (d.s2 & 3) != 0;   // only `in` is read 16 bytes at a time
   GTile tc;
-  if (!choose_gtile(ndim, d, (int)C, halo, tc)) return ADVCHAIN_ERR_UNSUPPORTED;
+  if (!choose_gtile(d, (int)C, halo, tc)) return ADVCHAIN_ERR_UNSUPPORTED;
   const size_t lds = (size_t)C * (tc.t0 + 2 * tc.h0) * (tc.t1 + 2 * tc.h1) * tc.rw * sizeof(float);
   dim3 g((unsigned)(tc.n0 * tc.n1 * tc.n2), (unsigned)N);
   bool ok = false;
   if (self) {
-    ok = ndim == 3 ? launch_sample_c<3, PAD_BORDER, true>((int)C, g, lds, st, in, grid, out, phi0, d, tc, 0, final_mode, disp_out, unaligned)
-                   : launch_sample_c<2, PAD_BORDER, true>((int)C, g, lds, st, in, grid, out, phi0, d, tc, 0, final_mode, disp_out, unaligned);
-  } else if (ndim == 3) {
-    switch (padding) {
-      case PAD_ZEROS: ok = launch_sample_c<3, PAD_ZEROS, false>((int)C, g, lds, st, in, grid, out, phi0, d, tc, clamp_grid, 0, nullptr, unaligned); break;
-      case PAD_BORDER: ok = launch_sample_c<3, PAD_BORDER, false>((int)C, g, lds, st, in, grid, out, phi0, d, tc, clamp_grid, 0, nullptr, unaligned); break;
-      default: ok = launch_sample_c<3, PAD_REFLECTION, false>((int)C, g, lds, st, in, grid, out, phi0, d, tc, clamp_grid, 0, nullptr, unaligned); break;
-    }
+    ok = launch_sample_c<PAD_BORDER, true>((int)C, g, lds, st, in, grid, out, phi0, d, tc, 0, final_mode, disp_out, unaligned);
   } else {
     switch (padding) {
-      case PAD_ZEROS: ok = launch_sample_c<2, PAD_ZEROS, false>((int)C, g, lds, st, in, grid, out, phi0, d, tc, clamp_grid, 0, nullptr, unaligned); break;
-      case PAD_BORDER: ok = launch_sample_c<2, PAD_BORDER, false>((int)C, g, lds, st, in, grid, out, phi0, d, tc, clamp_grid, 0, nullptr, unaligned); break;
-      default: ok = launch_sample_c<2, PAD_REFLECTION, false>((int)C, g, lds, st, in, grid, out, phi0, d, tc, clamp_grid, 0, nullptr, unaligned); break;
+      case PAD_ZEROS: ok = launch_sample_c<PAD_ZEROS, false>((int)C, g, lds, st, in, grid, out, phi0, d, tc, clamp_grid, 0, nullptr, unaligned); break;
+      case PAD_BORDER: ok = launch_sample_c<PAD_BORDER, false>((int)C, g, lds, st, in, grid, out, phi0, d, tc, clamp_grid, 0, nullptr, unaligned); break;
+      default: ok = launch_sample_c<PAD_REFLECTION, false>((int)C, g, lds, st, in, grid, out, phi0, d, tc, clamp_grid, 0, nullptr, unaligned); break;
     }
   }
   if (!ok) return ADVCHAIN_ERR_UNSUPPORTED;

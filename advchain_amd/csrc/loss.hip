@@ -16,7 +16,6 @@
 //           T' recovered from the saved P and D (T = P - D).
 // The caller owns the normalisers (global N under batch sharding).
 // Streaming + 3^d stencil: HBM-bound, no MFMA.
-#include <stdlib.h>
 #include <algorithm>
 #include "loss_common.h"
 
@@ -1350,8 +1349,7 @@ k_loss_fused_bwd3d_z(const float* __restrict__ pred, const float* __restrict__ r
 
 // ---- the z-marching fused 3D loss: shapes, chunk length, grid, LDS
 static inline bool z3_takes(const Dims& d, bool edges) {
-  static const bool off = getenv("ADVCHAIN_NO_FUSED_LOSS_3DZ") != nullptr;   // A/B knob
-  if (off || !edges || d.s0 < 2 || d.s2 % 4 != 0) return false;
+  if (!edges || d.s0 < 2 || d.s2 % 4 != 0) return false;
   const int lpr = d.s2 / 4;
   return lpr >= 1 && lpr <= 32;        // at least two rows a wave: RW = 4 x (64 / lpr) >= 8 rows, 6 of them own
 }
@@ -1376,11 +1374,9 @@ static inline dim3 march_grid(const Dims& d, int64_t N) {
   const int strips = (d.s2 >> 6) * ((d.s1 + kMarch - 1) / kMarch) * d.s0;
   return dim3((unsigned)((strips + kBlock / 64 - 1) / (kBlock / 64)), (unsigned)N);
 }
-static const bool g_no_march = getenv("ADVCHAIN_NO_MARCH") != nullptr;   // A/B knob
-static const bool g_no_march4 = getenv("ADVCHAIN_NO_MARCH4") != nullptr;   // A/B knob
 
 static inline bool march4_ok(const Dims& d, const void* a, const void* b, const void* c, const void* e) {
-  if (g_no_march4 || d.s2 % 4 != 0) return false;
+  if (d.s2 % 4 != 0) return false;
   const int lpr = d.s2 / 4;
   if (lpr > 64 || lpr < 1) return false;       // a row must fit one wave; rows need not divide it (idle tail lanes)
   const uintptr_t al = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
@@ -1390,8 +1386,6 @@ static inline bool march4_ok(const Dims& d, const void* a, const void* b, const 
 // rows marched per strip: as long as possible (each strip re-reads 2 halo rows) while the launch still has ~1024 waves
 // (measured: 8 rows beat 4 at 2048 waves, 3D 84 vs 92 us; 2D 1024 waves: 8 and 4 rows equal)
 static inline int march4_len(const Dims& d, int64_t N) {
-  static const int forced = 0;   // measured optimum (was a tuning knob until round 4)
-  if (forced > 0) return forced;
   const int groups_per_wave = 64 / (d.s2 / 4);
   for (int m = kMarch; m > 2; m /= 2)
     if (N * d.s0 * ((d.s1 + m - 1) / m) / groups_per_wave >= 1024) return m;
@@ -1406,7 +1400,6 @@ static inline dim3 march4_grid(const Dims& d, int64_t N, int mlen) {
 // The marching edge kernel of a three-kernel forward, if one takes the call: its grid, and which of the two it is.
 struct EdgeMarch { bool four; int mlen; dim3 grid; };
 static bool edge_march_plan(int64_t K, int64_t N, const Dims& d, const float* D, const float* mask, float* R, bool rows, EdgeMarch& m) {
-  if (g_no_march) return false;
   if (march4_ok(d, D, mask, R, nullptr) && K >= 2 && K <= 5) {
     m.four = true;
     m.mlen = march4_len(d, N);
@@ -1446,7 +1439,6 @@ static bool launch_bwd_march(int64_t K, int64_t N, const Dims& d, hipStream_t st
                              const float* R, const float* mask, const float* gscale, float* gpred, float c_mse,
                              float c_a, float c_b, int mask_ch, bool rows, float c_kl, int kl_gt) {
   const bool kl = c_kl != 0.f;
-  if (g_no_march) return false;
   if (march4_ok(d, P, D, R, mask) && (reinterpret_cast<uintptr_t>(gpred) & 15) == 0) {
     const int mlen = march4_len(d, N);
     const dim3 g4 = march4_grid(d, N, mlen), b4(kBlock);
@@ -1558,15 +1550,14 @@ static int consistency_fused_fwd(const OrdCounts* oc, const float* pred, const f
   ADVCHAIN_CHECK_ARG(pred && ref && sums, "consistency_fused_fwd: null pointer");
   ADVCHAIN_CHECK_ARG(ldims_ok(ndim, dims), "consistency_fused_fwd: bad dims");
   ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && K >= 1 && K <= kMaxK, "consistency_fused_fwd: bad N/K (K <= 16)");
-  static const bool off = getenv("ADVCHAIN_NO_FUSED_LOSS") != nullptr;   // A/B knob
   // 3D: the y-marching kernel below was measured SLOWER than the three-kernel form (K = 4: 4 x 4 x 128 x 128 x 64 230 against
   // 199 us -- its z fold reads three planes per row) and is instantiated for 2D only since round 5; 3D takes
-  // k_loss_fused_fwd3d_z (z-marching with the y neighbours through LDS; edges wanted, rows of at most 128 voxels;
-  // ADVCHAIN_NO_FUSED_LOSS_3DZ switches it off for A/B) or the unfused entries.
+  // k_loss_fused_fwd3d_z (z-marching with the y neighbours through LDS; edges wanted, rows of at most 128 voxels)
+  // or the unfused entries.
   const Dims d = lmake_dims(ndim, dims);
   const bool edges = want_edges && K > 1;
   const bool zmarch = ndim == 3 && z3_takes(d, edges);
-  if (off || (ndim == 3 && !zmarch) || K < 2 || K > 4 || (mask && mask_channels != 1)) return ADVCHAIN_ERR_UNSUPPORTED;
+  if ((ndim == 3 && !zmarch) || K < 2 || K > 4 || (mask && mask_channels != 1)) return ADVCHAIN_ERR_UNSUPPORTED;
   if (d.voxels() >= (1ll << 31) || !march4_ok(d, pred, ref, mask, R)) return ADVCHAIN_ERR_UNSUPPORTED;
   if (oc)
     for (int r = 0; r < 4; ++r) oc->counts[r] = 0;
@@ -1714,11 +1705,10 @@ int advchain_consistency_fused_fwd(const float* pred, const float* ref, const fl
 int64_t advchain_consistency_fused_fwd_partials(int64_t N, int64_t K, int ndim, const int64_t* dims, int has_mask, int mask_channels,
                                                 int want_edges, int aligned16) {
   if (!dims || !ldims_ok(ndim, dims) || N < 0 || N >= 65536 || K < 1 || K > kMaxK) return -1;
-  static const bool off = getenv("ADVCHAIN_NO_FUSED_LOSS") != nullptr;
   const Dims d = lmake_dims(ndim, dims);
   const bool edges = want_edges && K > 1;
   const bool zmarch = ndim == 3 && z3_takes(d, edges);
-  if (off || (ndim == 3 && !zmarch) || K < 2 || K > 4 || (has_mask && mask_channels != 1)) return ADVCHAIN_ERR_UNSUPPORTED;
+  if ((ndim == 3 && !zmarch) || K < 2 || K > 4 || (has_mask && mask_channels != 1)) return ADVCHAIN_ERR_UNSUPPORTED;
   const void* a = reinterpret_cast<const void*>(aligned16 ? (uintptr_t)0 : (uintptr_t)4);
   if (d.voxels() >= (1ll << 31) || !march4_ok(d, a, a, a, a)) return ADVCHAIN_ERR_UNSUPPORTED;
   if (N == 0) return 0;

@@ -14,7 +14,6 @@
 //
 // The arithmetic of a tap (weights as products, accumulation order) is the one of gather_tiled.hip / sample_linear:
 // the squaring chain amplifies rounding differences 2^8-fold and its parity tolerance was set with that order.
-#include <stdlib.h>
 #include "sampler_common.h"
 
 namespace advchain {
@@ -293,7 +292,6 @@ k_sample_march_flat(const float* __restrict__ in, const float* __restrict__ grid
   int tile = blockIdx.x + gridDim.x * blockIdx.y;
   const int tiles = gridDim.x * gridDim.y;
   if ((xcd & 1) && (tiles & 7) == 0) tile = (tile & 7) * (tiles >> 3) + (tile >> 3);   // XCD-contiguous tiles (see above)
-  const int dbg = xcd >> 4;   // timing experiments only (ADVCHAIN_FWD_MARCH_DEBUG, results are wrong): 1 no taps, 2 no stores
   const int n = tile / (int)gridDim.x;
   const int rem = tile - n * (int)gridDim.x;
   const int ty = rem % n1, tz = rem / n1;
@@ -411,10 +409,7 @@ k_sample_march_flat(const float* __restrict__ in, const float* __restrict__ grid
       const float wy1 = ys - fy, wy0 = (fy + 1.f) - ys;
       const float wz1 = zs - fz, wz0 = (fz + 1.f) - zs;
       const bool staged = (unsigned)(iz - z + 1) <= 1u && (unsigned)(iy - uy + 1) <= 1u && (unsigned)(ix + 1) <= (unsigned)W;
-      if (dbg & 1) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) res[c][i] = wx1 + wy1 + wz1;
-      } else if (staged) {
+      if (staged) {
         float w[8];
         w[0] = (wx0 * wy0) * wz0; w[1] = (wx1 * wy0) * wz0; w[2] = (wx0 * wy1) * wz0; w[3] = (wx1 * wy1) * wz0;
         w[4] = (wx0 * wy0) * wz1; w[5] = (wx1 * wy0) * wz1; w[6] = (wx0 * wy1) * wz1; w[7] = (wx1 * wy1) * wz1;
@@ -479,7 +474,7 @@ k_sample_march_flat(const float* __restrict__ in, const float* __restrict__ grid
         const int a = j / (IPW * 16), i = (j / 16) % IPW, q = j & 15;
         const float4 v4 = *reinterpret_cast<const float4*>(tr + (a * IPW + i) * 64 + 4 * q);
         const int f4 = (wave * IPW + i) * 64 + 4 * q;
-        if (j < ITEMS && c0 + a < C && f4 < flat_n && !(dbg & 2))
+        if (j < ITEMS && c0 + a < C && f4 < flat_n)
           *reinterpret_cast<float4*>(outn + (size_t)(c0 + a) * V + tile_off + (uint32_t)f4) = v4;
       }
       lds_order();
@@ -502,8 +497,6 @@ k_sample_march_flat(const float* __restrict__ in, const float* __restrict__ grid
 using namespace advchain;
 
 static int fwd_march_zc(const Dims& d, int64_t N, int ty, int C) {
-  static const int forced = getenv("ADVCHAIN_FWD_MARCH_ZC") ? atoi(getenv("ADVCHAIN_FWD_MARCH_ZC")) : 0;   // A/B knob (0: the rule below)
-  if (forced > 0) return forced;
   // measured at 4 x C x 128 x 128 x 64: the one-channel warp is latency-bound and wants 8 workgroups per CU even at
   // chunks of 4 planes (15.4 us against 17.7 at 8 and 25 at 16 planes); 3-4 channels want 4 per CU and chunks >= 8
   // (a measured dead end: handing the grid values to their lanes through LDS with 16-byte loads -- 18.9 us)
@@ -519,21 +512,17 @@ static void launch_fwd_march(const float* in, const float* grid, float* out, con
                              int final_mode, float* disp_out, hipStream_t st) {
   using G = FwdMarchCfg<C, SELF, NW, RPW>;
   auto kern = k_sample_march<C, SELF, MODE, NW, RPW>;
-  // occupancy experiment (round 6, profiles/r06/f1_3d/): ADVCHAIN_MARCH_LDS_PAD = extra dynamic LDS in KiB that nobody touches --
-  // the kernel then runs with the workgroups-per-CU a fused two-level kernel's LDS footprint would leave it (results unchanged)
-  static const size_t lds_pad = getenv("ADVCHAIN_MARCH_LDS_PAD") ? (size_t)atoi(getenv("ADVCHAIN_MARCH_LDS_PAD")) * 1024 : 0;
   static bool attr_set = false;
-  if (G::LDS + lds_pad > 65536 && !attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(G::LDS + lds_pad));
+  if (G::LDS > 65536 && !attr_set) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS);
     attr_set = true;
   }
   const int n1 = (d.s1 + G::TY - 1) / G::TY;
   const int nseg = d.s2 <= 64 ? 1 : (d.s2 + kFwdSegOwn - 1) / kFwdSegOwn;
   const int zc = fwd_march_zc(d, N * nseg, G::TY, C);
   const int n0 = (d.s0 + zc - 1) / zc;
-  static const bool no_xcd = false;   // measured optimum (was a tuning knob until round 4)
-  hipLaunchKernelGGL(kern, dim3((unsigned)(nseg * n1 * n0), (unsigned)N), dim3(G::NT), G::LDS + lds_pad, st, in, grid, out, phi0, d, n1, zc,
-                     final_mode, disp_out, no_xcd ? -nseg : nseg);
+  hipLaunchKernelGGL(kern, dim3((unsigned)(nseg * n1 * n0), (unsigned)N), dim3(G::NT), G::LDS, st, in, grid, out, phi0, d, n1, zc,
+                     final_mode, disp_out, nseg);
 }
 
 // rows of 68 .. 80 (PW = 80) and 84 .. 128 (PW = 128) voxels: lane <-> flat voxel (k_sample_march_flat)
@@ -557,10 +546,8 @@ static void launch_fwd_flat(const float* in, const float* grid, float* out, cons
   const int n1 = (d.s1 + G::TY - 1) / G::TY;
   const int zc = fwd_march_zc(d, N, G::TY, C);
   const int n0 = (d.s0 + zc - 1) / zc;
-  static const bool no_xcd = false;   // measured optimum (was a tuning knob until round 4)
-  static const int dbg = getenv("ADVCHAIN_FWD_MARCH_DEBUG") ? atoi(getenv("ADVCHAIN_FWD_MARCH_DEBUG")) : 0;   // timing experiments
   hipLaunchKernelGGL(kern, dim3((unsigned)(n1 * n0), (unsigned)N), dim3(nw * 64), G::lds_bytes(nw), st, in, grid, out, phi0, d, n1,
-                     zc, final_mode, disp_out, (no_xcd ? 0 : 1) | (dbg << 4));
+                     zc, final_mode, disp_out, 1);
 }
 
 template <int C>
@@ -581,13 +568,11 @@ static void launch_fwd_march_mode(int mode, const float* in, const float* grid, 
 int advchain_sample_march_launch(bool self, const float* in, const float* grid, float* out, const float* phi0, int64_t N,
                                  int64_t C, Dims d, int padding, int clamp_grid, int final_mode, float* disp_out,
                                  hipStream_t st) {
-  static const bool off = getenv("ADVCHAIN_NO_MARCH_FWD") != nullptr;   // A/B knob
-  if (off || padding == PAD_REFLECTION) return ADVCHAIN_ERR_UNSUPPORTED;
+  if (padding == PAD_REFLECTION) return ADVCHAIN_ERR_UNSUPPORTED;
   const uintptr_t al = reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out);
   if (d.s2 < 8 || (d.s2 & 3) != 0 || (al & 15) != 0 || d.s0 < 2 || d.voxels() * 4 >= (1ll << 31))
     return ADVCHAIN_ERR_UNSUPPORTED;
-  static const bool no_flat = getenv("ADVCHAIN_NO_FLAT_FWD") != nullptr;   // A/B knob
-  const bool flat = !no_flat && d.s2 > 64 && d.s2 <= kFlatPW2;
+  const bool flat = d.s2 > 64 && d.s2 <= kFlatPW2;
   if (self) {
     if (C != 3) return ADVCHAIN_ERR_UNSUPPORTED;
     if (flat) launch_fwd_flat<3, true, kFwdBorder>(in, nullptr, out, phi0, N, d, final_mode, disp_out, st);

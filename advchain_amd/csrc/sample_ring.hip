@@ -12,7 +12,6 @@
 // H comes from the caller's displacement hint and is a performance parameter only: a lane whose corners leave the ring
 // takes sample_linear's gathers, and the ring path uses the same arithmetic (weights as products, tap_acc order), so the
 // result does not depend on H or on which kernel ran.
-#include <stdlib.h>
 #include "sampler_common.h"
 
 namespace advchain {
@@ -162,19 +161,15 @@ using namespace advchain;
 // ADVCHAIN_ERR_UNSUPPORTED: the caller uses the tile kernel / the direct gathers.
 int advchain_sample_ring_launch(const float* in, const float* grid, float* out, int64_t N, Dims d, int padding, int clamp_grid,
                                 int hint, hipStream_t st) {
-  static const bool off = getenv("ADVCHAIN_NO_RING_FWD") != nullptr;   // A/B knob
-  static const int h_forced = 0;   // measured optimum (was a tuning knob until round 4)
-  if (off || padding == PAD_REFLECTION) return ADVCHAIN_ERR_UNSUPPORTED;
+  if (padding == PAD_REFLECTION) return ADVCHAIN_ERR_UNSUPPORTED;
   const uintptr_t al = reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(grid);
   if (d.s2 < 8 || d.s2 > 64 || (d.s2 & 3) != 0 || (al & 15) != 0 || d.s0 < 2 || d.voxels() * 4 >= (1ll << 31))
     return ADVCHAIN_ERR_UNSUPPORTED;
-  int H = h_forced > 0 ? h_forced : hint;
+  const int H = hint;
   if (H < 2 || H > 4) return ADVCHAIN_ERR_UNSUPPORTED;
   const int n1 = (int)((d.s1 + 7) / 8);
-  static const int zc_forced = 0;
   int zc = (int)d.s0;
   while (zc > 16 && N * n1 * ((d.s0 + zc - 1) / zc) < 1024) zc = (zc + 1) / 2;
-  if (zc_forced > 0) zc = zc_forced;
   const int n0 = (int)((d.s0 + zc - 1) / zc);
   dim3 g((unsigned)(n1 * n0 * N));
 #define GO(PAD_, H_) do { \

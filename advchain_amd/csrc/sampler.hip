@@ -14,7 +14,6 @@
 // supply the memory-level parallelism a dependent grid -> gather -> store sequence lacks.  Backward scatters
 // go through the LDS-tiled owner-computes kernel (scatter_tiled.hip); the global-atomic kernels here are the
 // fallback for resampling / nearest.  No MFMA: there is no contraction here.
-#include <stdlib.h>
 #include "sampler_common.h"
 #include "affine_geo.h"
 #include "det_fix.h"
@@ -1205,13 +1204,12 @@ int advchain_affine_warp_fwd(const float* in, const float* theta, float* out, in
   ADVCHAIN_CHECK_ARG(d.voxels() < (1ll << 31), "affine_warp_fwd: per-sample volume too large");
   dim3 g(affine_grid_blocks(d), (unsigned)N), b(kBlock);
   hipStream_t st = (hipStream_t)stream;
-  static const float thr = 7.f;   // measured optimum (was a tuning knob until round 4) (break-even measured at ~6 degrees)
-  static const bool no_v = getenv("ADVCHAIN_NO_AFFINE_V") != nullptr;   // A/B knob
+  constexpr float thr = 7.f;   // measured optimum (round 4; break-even measured at ~6 degrees)
   if (interp == INTERP_LINEAR && padding == PAD_ZEROS && advchain_affine_box_fwd_launch(in, theta, out, N, C, ndim, d, st)) {
     ADVCHAIN_LAUNCH_CHECK();
     return ADVCHAIN_OK;
   }
-  if (interp == INTERP_LINEAR && C <= 4 && !no_v) {
+  if (interp == INTERP_LINEAR && C <= 4) {
     const unsigned nw = (unsigned)affine_waves(d);
 #define GO_V(DIM_, CT_, VEC_) do { \
     dim3 gv((nw + (kBlock / 64) * VEC_ - 1) / ((kBlock / 64) * VEC_), (unsigned)N); \
@@ -1271,8 +1269,9 @@ int advchain_affine_warp_fwd_ride(const float* in, const float* theta, float* ou
 // squarings whose hinted input displacement (bits 8.. of a hint: 1/1024 pixel) leaves a quarter of room below one pixel for
 // the field to grow between two ascent steps, and the squarings behind them while the window (the sum of the levels' row
 // halos either side) stays small: a level whose input moves less than h pixels takes its corners from h rows either side.
-static int fuse_rule(int n, const int32_t* hints, int fuse_max, int* halos_out) {
-  static const int hs_max = getenv("ADVCHAIN_FUSE2D_HS") ? atoi(getenv("ADVCHAIN_FUSE2D_HS")) : 5;   // A/B knob: rows of halo in all
+static int fuse_rule(int n, const int32_t* hints, int* halos_out) {
+  constexpr int fuse_max = 5;   // levels in one launch at most
+  constexpr int hs_max = 5;     // rows of halo in all
   int k = 0, halos = 0, hs = 0;
   while (k < n - 1 && k < fuse_max && ((unsigned)hints[k] >> 8) != 0) {
     const float e = (float)((unsigned)hints[k] >> 8) * (1.25f / 1024.f);
@@ -1286,15 +1285,10 @@ static int fuse_rule(int n, const int32_t* hints, int fuse_max, int* halos_out) 
   return k;
 }
 
-static int fuse_max_levels() {
-  static const int fuse_max = getenv("ADVCHAIN_FUSE2D_MAX") ? atoi(getenv("ADVCHAIN_FUSE2D_MAX")) : 5;   // A/B knob (0 = off)
-  return fuse_max;
-}
-
 int advchain_expo_chain_fused_levels(int64_t N, int ndim, const int64_t* dims, int n, const int32_t* hints) {
-  if (ndim != 2 || !hints || !dims_ok(ndim, dims) || n < 1 || n > 64 || fuse_max_levels() < 2) return 0;
+  if (ndim != 2 || !hints || !dims_ok(ndim, dims) || n < 1 || n > 64) return 0;
   int halos = 0;
-  const int k = fuse_rule(n, hints, fuse_max_levels(), &halos);
+  const int k = fuse_rule(n, hints, &halos);
   if (k < 2) return 0;
   return advchain_expo_fused_fwd2d_launch(nullptr, nullptr, N, make_dims(ndim, dims), k, halos, nullptr, nullptr, nullptr, true) == ADVCHAIN_OK ? k : 0;
 }
@@ -1309,16 +1303,15 @@ int advchain_expo_chain_fwd(const float* phi0, float* fields, float* pos, int64_
   // windows, bit-identical fields).  The kernel verifies the premise itself and raises *fuse_flag when a window moves too
   // far for some of its levels; ONE repeat launch behind it (k_expo_repeat2d) then runs exactly those levels the ordinary
   // way, and returns at once while the flag is down.
-  const int fuse_max = fuse_max_levels();
   int fused = 0;
-  if (ndim == 2 && fuse_flag && hints && fuse_max >= 2) {
+  if (ndim == 2 && fuse_flag && hints) {
     // how many: the leading squarings whose hinted input displacement (bits 8.. of a hint: 1/1024 pixel) leaves a quarter
     // of room below one pixel for the field to grow between two ascent steps; a level some window cannot do after all is
     // repeated by the launch behind the fused kernel
     // ... and the squarings behind them while the window (the sum of the levels' row halos either side) stays small: a
     // level whose input moves less than h pixels takes its corners from h rows either side
     int halos = 0;
-    const int k = fuse_rule(n, hints, fuse_max, &halos);
+    const int k = fuse_rule(n, hints, &halos);
     if (k >= 2) {
       const int rf = advchain_expo_fused_fwd2d_launch(phi0, fields, N, make_dims(ndim, dims), k, halos, disp_rows, fuse_flag,
                                                       (hipStream_t)stream);
@@ -1380,9 +1373,8 @@ int advchain_expo_chain_bwd(const float* grad_pos, const float* phi0, const floa
   // 2D: consecutive whole-row scatters hand the row maxima of their output to the next one (its fixed-point scale): no
   // k_march_rowmax pre-pass between them
   const Dims dd = make_dims(ndim, dims);
-  static const bool no_handover = getenv("ADVCHAIN_NO_ROWMAX_HANDOVER") != nullptr;   // A/B knob: a k_march_rowmax pre-pass per launch
   auto rows = [&](int i) {
-    return !no_handover && ndim == 2 && workspace && i >= 0 && i < n - kf && halos[i] <= -2 && advchain_scatter_rows2d_takes(true, 2, dd, PAD_BORDER, -halos[i], N);
+    return ndim == 2 && workspace && i >= 0 && i < n - kf && halos[i] <= -2 && advchain_scatter_rows2d_takes(true, 2, dd, PAD_BORDER, -halos[i], N);
   };
   for (int i = 0; i < n - kf; ++i) {                 // squaring m = n-1 .. kf; the last step of the call writes grad_phi0
     const int m = n - 1 - i;
@@ -1448,8 +1440,7 @@ int advchain_affine_warp_bwd(const float* grad_out, const float* in, const float
   }
   const int* mode = nullptr;
   int nbx_theta = -1;     // >= 0: the box kernel was asked for the theta gradient already (0 = it declined the shape)
-  static const bool no_gather = getenv("ADVCHAIN_AFFINE_ATOMIC") != nullptr;  // A/B knob
-  if (grad_in && workspace && interp == INTERP_LINEAR && padding == PAD_ZEROS && C <= 8 && !no_gather) {
+  if (grad_in && workspace && interp == INTERP_LINEAR && padding == PAD_ZEROS && C <= 8) {
     // gather formulation of grad_in (no atomics); samples it cannot handle are flagged and scattered below
     float* geo = workspace + N * (int64_t)nb * ndim * (ndim + 1);
     int* md = reinterpret_cast<int*>(geo + N * kGeoFloats);

@@ -18,7 +18,6 @@
 // The price is halo work: samples are visited (TY+2H)/TY x (ZC+2H)/ZC times (loads, taps, range tests -- not atomics).
 //
 // Contract: |unnormalize(grid) - s| < H voxels for every sample, guaranteed by the caller (negative `halo`).
-#include <stdlib.h>
 #include "sampler_common.h"
 
 namespace advchain {
@@ -737,10 +736,6 @@ k_scatter_march3d_flat(const float* __restrict__ gout, const float* __restrict__
 //   * two stages and one spare plane in each ring: ONE barrier per step.
 // 16 waves own 16 rows (2.25 visits per sample at H = 4 instead of 3); 156 KiB of LDS, one workgroup a CU.
 // ---------------------------------------------------------------------------------------------------------------------
-// A/B build switch (tools/ab/build_variant.sh -DADVCHAIN_WIDE_TRIM=0): the trimmed deposit arithmetic of the wide march scatter
-#ifndef ADVCHAIN_WIDE_TRIM
-#define ADVCHAIN_WIDE_TRIM 1
-#endif
 template <int H>
 struct WideCfg {
   static constexpr int TY = 16, NWV = 16, NT = NWV * 64, XS = 68;
@@ -757,8 +752,7 @@ struct WideCfg {
 template <int PAD, bool GG, int H>
 __global__ void __launch_bounds__(WideCfg<H>::NT)
 k_scatter_march3d_wide(const float* __restrict__ gout, const float* __restrict__ in, const float* __restrict__ grid,
-                       float* __restrict__ gin, float* __restrict__ ggrid, Dims d, int n1, int zc, int clamp_grid,
-                       int32_t* __restrict__ ws) {
+                       float* __restrict__ gin, float* __restrict__ ggrid, Dims d, int n1, int zc, int clamp_grid) {
   using G = WideCfg<H>;
   constexpr int TY = G::TY, NWV = G::NWV, NT = G::NT, XS = G::XS, NS = G::NS, NP = G::NP, R = G::R;
   extern __shared__ int acc[];                                // [NS][TY][64]
@@ -835,40 +829,35 @@ k_scatter_march3d_wide(const float* __restrict__ gout, const float* __restrict__
     fetch_rows(za - H + 1, rowA);
     fetch_in(za + 1, inA);
     // ... and while they travel: the fixed-point scale from the maximum |grad_out| over the rows this workgroup visits, zeroed
-    // rings.  ws == nullptr (round 6): no row-maxima pre-pass was launched -- the workgroup reads its own (TY + 2H) x (zc + 2H)
-    // rows of grad_out itself, 16 bytes per lane, four requests in flight per thread (a plane's visited rows are one
+    // rings.  No row-maxima pre-pass (round 6): the workgroup reads its own (TY + 2H) x (zc + 2H) rows of grad_out itself,
+    // 16 bytes per lane, four requests in flight per thread (a plane's visited rows are one
     // contiguous run; 2.25x the tensor over all workgroups, out of L2): the separate k_march_rowmax64 launch was 5.1 us of
     // the north-star backward's 67.6
     {
       const int ya = max(y0 - H, 0), yn = min(y0 + TY + H, d.s1) - ya;
       const int zlo = max(za - H, 0), zn = min(zb + H, d.s0) - zlo;
       float m = 0.f;
-      if (ws) {
-        const float* rowmax = reinterpret_cast<const float*>(ws + 4) + (int64_t)n * d.s0 * d.s1;
-        for (int i = tid; i < yn * zn; i += NT) m = fmaxf(m, rowmax[(zlo + i / yn) * d.s1 + ya + i % yn]);
-      } else {
-        const int per_plane = (yn * d.s2) >> 2, total = per_plane * zn;     // float4 items (S2 % 4 == 0)
-        const int pstride = d.s1 * d.s2;
-        const float* base = gon + (unsigned)(zlo * pstride + ya * d.s2);
-        bool bad = false;
-        for (int i0 = tid; i0 < total; i0 += 4 * NT) {
-          float4 v[4];
+      const int per_plane = (yn * d.s2) >> 2, total = per_plane * zn;     // float4 items (S2 % 4 == 0)
+      const int pstride = d.s1 * d.s2;
+      const float* base = gon + (unsigned)(zlo * pstride + ya * d.s2);
+      bool bad = false;
+      for (int i0 = tid; i0 < total; i0 += 4 * NT) {
+        float4 v[4];
 #pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int i = min(i0 + u * NT, total - 1);
-            const int pl = i / per_plane, r4 = i - pl * per_plane;
-            v[u] = *reinterpret_cast<const float4*>(base + (unsigned)(pl * pstride + 4 * r4));
-          }
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const float q = fmaxf(fmaxf(fabsf(v[u].x), fabsf(v[u].y)), fmaxf(fabsf(v[u].z), fabsf(v[u].w)));
-            m = fmaxf(m, q);
-            bad = bad || !(fabsf(v[u].x) <= 3.0e38f) || !(fabsf(v[u].y) <= 3.0e38f) || !(fabsf(v[u].z) <= 3.0e38f) ||
-                  !(fabsf(v[u].w) <= 3.0e38f);
-          }
+        for (int u = 0; u < 4; ++u) {
+          const int i = min(i0 + u * NT, total - 1);
+          const int pl = i / per_plane, r4 = i - pl * per_plane;
+          v[u] = *reinterpret_cast<const float4*>(base + (unsigned)(pl * pstride + 4 * r4));
         }
-        if (bad) m = __int_as_float(0x7f800000);      // a non-finite gradient must surface (lesson 36): scale 0, factor inf
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const float q = fmaxf(fmaxf(fabsf(v[u].x), fabsf(v[u].y)), fmaxf(fabsf(v[u].z), fabsf(v[u].w)));
+          m = fmaxf(m, q);
+          bad = bad || !(fabsf(v[u].x) <= 3.0e38f) || !(fabsf(v[u].y) <= 3.0e38f) || !(fabsf(v[u].z) <= 3.0e38f) ||
+                !(fabsf(v[u].w) <= 3.0e38f);
+        }
       }
+      if (bad) m = __int_as_float(0x7f800000);      // a non-finite gradient must surface (lesson 36): scale 0, factor inf
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
       if (lane == 0) wmax[wave] = m;
@@ -967,7 +956,6 @@ k_scatter_march3d_wide(const float* __restrict__ gout, const float* __restrict__
             anyz[cz] = pz >= zlo && pz < zhi;
             wzm[cz] = anyz[cz] ? t.wz(cz) : 0.f;
           }
-#if ADVCHAIN_WIDE_TRIM
           {
             // the upper corner's slot is the lower one's successor in the ring (where the clamp engages the corner carries
             // weight 0 and any slot inside the ring will do): one wrap each instead of two clamps and four selects
@@ -979,15 +967,6 @@ k_scatter_march3d_wide(const float* __restrict__ gout, const float* __restrict__
             slot -= slot >= NS ? NS : 0;
             slotz[1] = slot * (TY * 64);
           }
-#else
-#pragma unroll
-          for (int cz = 0; cz < 2; ++cz) {
-            int slot = sz + min(max(t.z.i0 + cz - zp, -H), H + 1);
-            slot += slot < 0 ? NS : 0;
-            slot -= slot >= NS ? NS : 0;
-            slotz[cz] = slot * (TY * 64);
-          }
-#endif
           const float gsc = fix_in(go * fs.mul, fs);
           const float a0 = wxm[0] * gsc, a1 = wxm[1] * gsc;
 #pragma unroll
@@ -1079,10 +1058,6 @@ k_scatter_march3d_wide(const float* __restrict__ gout, const float* __restrict__
 // or stored (grad_grid).  Whole rows: the halo work is in y only, (TY+2H)/TY (the 2D tiles of scatter_tiled.hip pay it
 // on both axes and need an overflow list; the window scatter pays 1.7 global float atomics per sample and channel).
 // ---------------------------------------------------------------------------------------------------------------------
-// A/B build switch (tools/ab/build_all_variant.sh -DADVCHAIN_ROWS2D_FLAT=0): the branch-light deposits of the whole-row scatter
-#ifndef ADVCHAIN_ROWS2D_FLAT
-#define ADVCHAIN_ROWS2D_FLAT 1
-#endif
 __device__ __forceinline__ int rows2d_fix_bits(int H) {   // (2H+2)^2 deposits of weight <= 1 stay below 2^31 (fix_scale)
   return H <= 2 ? 25 : (H <= 4 ? 24 : (H <= 8 ? 22 : (H <= 16 ? 20 : 18)));
 }
@@ -1166,7 +1141,7 @@ k_scatter_rows2d(const float* __restrict__ gout, const float* __restrict__ in, c
       float gs[C];                                  // grad_out times the power-of-two part of the scale (fs.mul is in the weights)
 #pragma unroll
       for (int c = 0; c < C; ++c) gs[c] = PLAIN ? go[c] : fix_in(go[c], fs);
-      if constexpr (ADVCHAIN_ROWS2D_FLAT && SELF) {
+      if constexpr (SELF) {
       // branch-light deposits for the squarings (round 6; the 3D march scatters do the same since lesson 37 b): per-axis masked weights, and
       // a masked corner adds its zero at the lane's OWN column of an owned row -- never two lanes on one cell -- instead of
       // four exec-mask regions per item; 24-bit multiplies for the cell rows (a 32-bit v_mul_lo costs four VALU slots)
@@ -1326,17 +1301,16 @@ using namespace advchain;
 
 // The shapes / bounds the whole-row scatter takes; TY = owned rows per workgroup (0: not taken).
 static int rows2d_tile(bool self, int64_t C, const Dims& d, int padding, int H, int64_t N) {
-  static const bool off = getenv("ADVCHAIN_NO_SCATTER_ROWS2D") != nullptr;   // A/B knob
   // from which bound on: 3 pixels (below, the gather form of adjoint_gather.hip is faster) -- for a squaring whose launch fills
   // the machine, 2 (round 5, once the own rows' coordinate path moved into their deposit visit: 35 against 46 us in a chain
   // at 64 x 2 x 256 x 256; with 96 workgroups, 8 x 2 x 192 x 192, the gather form wins, 8.6 against 14.3 us)
   const int hmin = (self && N * ((d.s1 + 15) / 16) >= 512) ? 2 : 3;
-  if (off || padding == PAD_REFLECTION || H < hmin || H > (self ? 32 : 16) || d.s0 != 1) return 0;
+  if (padding == PAD_REFLECTION || H < hmin || H > (self ? 32 : 16) || d.s0 != 1) return 0;
   if (d.s2 < 16 || d.s2 > 512 || d.voxels() * 4 >= (1ll << 31)) return 0;
   if (self ? C != 2 : (C != 1 && C != 4)) return 0;
   const int nseg = (d.s2 + 63) / 64;
   int TY = H >= 8 ? 32 : 16;
-  static const size_t lds_cap = 49152;   // measured optimum (was a tuning knob until round 4)
+  constexpr size_t lds_cap = 49152;      // measured optimum (round 4)
   while (TY > 4 && ((size_t)C * TY * d.s2 * 4 > lds_cap || TY * nseg > 64)) TY >>= 1;   // 48 KiB of cells, 8 own items a wave
   if ((size_t)C * TY * d.s2 * sizeof(int) > 65536 - 64 || TY * nseg > 64) return 0;
   return TY;
@@ -1381,9 +1355,8 @@ int advchain_scatter_rows2d_launch(bool self, const float* gout, const float* in
 int advchain_scatter_march_launch(bool self, const float* gout, const float* in, const float* grid, float* gin, float* ggrid,
                                   int64_t N, int64_t C, Dims d, int padding, int clamp_grid, int H, int32_t* workspace,
                                   hipStream_t st) {
-  static const bool off = getenv("ADVCHAIN_NO_SCATTER_MARCH") != nullptr;   // A/B knob
-  static const int hmax = 8;   // measured optimum (was a tuning knob until round 4)
-  if (off || !workspace || !gin || padding == PAD_REFLECTION || H < 2 || H > hmax || H > 8) return ADVCHAIN_ERR_UNSUPPORTED;
+  constexpr int hmax = 8;      // measured optimum (round 4); also the largest bound the per-channel form is instantiated for
+  if (!workspace || !gin || padding == PAD_REFLECTION || H < 2 || H > hmax) return ADVCHAIN_ERR_UNSUPPORTED;
   if (d.s2 > 1024 || d.s2 < 8 || d.s0 < 2 || d.voxels() * 4 >= (1ll << 31)) return ADVCHAIN_ERR_UNSUPPORTED;
   const int nseg = d.s2 <= 64 ? 1 : (int)((d.s2 + (64 - 2 * H) - 1) / (64 - 2 * H));
   if (self ? C != 3 : (C != 1 && C != 4)) return ADVCHAIN_ERR_UNSUPPORTED;
@@ -1419,8 +1392,7 @@ int advchain_scatter_march_launch(bool self, const float* gout, const float* in,
     return ADVCHAIN_OK;
   }
   // self-composition on rows of 68 .. 80 voxels: lane <-> flat sample (k_scatter_march3d_flat)
-  static const bool no_flat = getenv("ADVCHAIN_NO_SCATTER_MARCH_FLAT") != nullptr;   // A/B knob
-  if (!no_flat && self && H <= 4 && d.s2 > 64 && d.s2 <= 80) {
+  if (self && H <= 4 && d.s2 > 64 && d.s2 <= 80) {
     const int TYf = 8, W = (int)d.s2;
     int NSf = 2 * H + 3;
     if ((size_t)NSf * 3 * TYf * W * 4 > 80 * 1024) NSf = 2 * H + 2;       // two workgroups a CU
@@ -1428,8 +1400,6 @@ int advchain_scatter_march_launch(bool self, const float* gout, const float* in,
     const int n1f = (int)((d.s1 + TYf - 1) / TYf);
     int zcf = (int)d.s0;
     while (zcf > 8 && N * n1f * ((d.s0 + zcf - 1) / zcf) < 512) zcf = (zcf + 1) / 2;
-    static const int zcf_forced = 0;   // (0: the rule below; was a tuning knob until round 4)
-    if (zcf_forced > 0) zcf = zcf_forced;
     const int n0f = (int)((d.s0 + zcf - 1) / zcf);
     const int rows = (int)(d.s0 * d.s1);
     launch_rowmax<3>(gout, reinterpret_cast<float*>(workspace + 4), d, rows, N, 3, st);
@@ -1446,29 +1416,21 @@ int advchain_scatter_march_launch(bool self, const float* gout, const float* in,
     return ADVCHAIN_OK;
   }
   // image warps with rows of at most 64 voxels: the 16-byte form
-  static const bool no_wide = getenv("ADVCHAIN_NO_SCATTER_MARCH_WIDE") != nullptr;   // A/B knob
   auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  if (!no_wide && !self && C == 1 && H <= 4 && d.s2 <= 64 && d.s2 % 4 == 0 && aligned16(gout) && aligned16(in) && aligned16(grid) &&
+  if (!self && C == 1 && H <= 4 && d.s2 <= 64 && d.s2 % 4 == 0 && aligned16(gout) && aligned16(in) && aligned16(grid) &&
       aligned16(gin) && aligned16(ggrid)) {
     const bool ggw = ggrid != nullptr;
     const int n1w = (int)((d.s1 + 15) / 16);
     int zcw = (int)d.s0;
     while (zcw > 16 && N * n1w * ((d.s0 + zcw - 1) / zcw) < 256) zcw = (zcw + 1) / 2;
-    static const int zcw_forced = 0;   // (0: the rule below; was a tuning knob until round 4)
-    if (zcw_forced > 0) zcw = zcw_forced;
     const int n0w = (int)((d.s0 + zcw - 1) / zcw);
-    const int rows = (int)(d.s0 * d.s1);
-    dim3 rg((unsigned)((rows + kBlock / 16 - 1) / (kBlock / 16)), (unsigned)N);
-    // round 6: the workgroups take the maximum over their own rows themselves (ADVCHAIN_WIDE_ROWMAX_PASS: the pre-pass, A/B)
-    static const bool rowmax_pass = getenv("ADVCHAIN_WIDE_ROWMAX_PASS") != nullptr;
-    if (rowmax_pass) launch_rowmax<1>(gout, reinterpret_cast<float*>(workspace + 4), d, rows, N, 1, st);
-    int32_t* const ws_arg = rowmax_pass ? workspace : nullptr;
+    // (round 6: the workgroups take the maximum over their own rows themselves -- no row-maxima pre-pass)
     dim3 gw((unsigned)(n1w * n0w * N));
 #define GOW(PAD_, GG_, H_) do { \
       auto kern = k_scatter_march3d_wide<PAD_, GG_, H_>; \
       static bool attr_set = false; \
       if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WideCfg<H_>::lds(GG_)); attr_set = true; } \
-      hipLaunchKernelGGL(kern, gw, dim3(WideCfg<H_>::NT), WideCfg<H_>::lds(GG_), st, gout, in, grid, gin, ggrid, d, n1w, zcw, clamp_grid, ws_arg); } while (0)
+      hipLaunchKernelGGL(kern, gw, dim3(WideCfg<H_>::NT), WideCfg<H_>::lds(GG_), st, gout, in, grid, gin, ggrid, d, n1w, zcw, clamp_grid); } while (0)
 #define GOW_H(PAD_, GG_) do { if (H == 2) GOW(PAD_, GG_, 2); else if (H == 3) GOW(PAD_, GG_, 3); else GOW(PAD_, GG_, 4); } while (0)
     if (padding == PAD_BORDER) { if (ggw) GOW_H(PAD_BORDER, true); else GOW_H(PAD_BORDER, false); }
     else { if (ggw) GOW_H(PAD_ZEROS, true); else GOW_H(PAD_ZEROS, false); }
@@ -1478,19 +1440,15 @@ int advchain_scatter_march_launch(bool self, const float* gout, const float* in,
     return ADVCHAIN_OK;
   }
   // rows per workgroup: as many as 60 KiB of accumulator planes allow, at most 8
-  static const int ty_forced = 0;
   int NS = 2 * H + 3;
   int TY = 8;    // (16 halves the y halo work but leaves 512 workgroups at 4 x 128 x 128 x 64)
   if ((size_t)NS * C * TY * 64 * 4 > 65536) NS = 2 * H + 2;
   while (TY > 4 && (size_t)NS * C * TY * 64 * 4 > 65536) TY >>= 1;
-  if (ty_forced == 4 || ty_forced == 8) TY = ty_forced;
   const size_t lds = (size_t)NS * C * TY * 64 * sizeof(int);
   if (lds > 65536) return ADVCHAIN_ERR_UNSUPPORTED;
   const int n1 = (d.s1 + TY - 1) / TY;
-  static const int zc_forced = 0;   // (0: the rule below; was a tuning knob until round 4)
   int zc = d.s0;
   while (zc > 8 && N * n1 * nseg * ((d.s0 + zc - 1) / zc) < 512) zc = (zc + 1) / 2;   // (16 planes: 1003 GB/s, 8: 942, 32: 834)
-  if (zc_forced > 0) zc = zc_forced;
   const int n0 = (d.s0 + zc - 1) / zc;
   {
     const int rows = (int)(d.s0 * d.s1);

@@ -14,7 +14,6 @@
 //      of 4 scattered ones.
 // Every sample is read and processed exactly once, there is no halo, no overflow list and no max|grad_out| pre-pass;
 // the price is a zero-filled destination and float-atomic (order-dependent, ~1e-7 relative) accumulation across tiles.
-#include <stdlib.h>
 #include "sampler_common.h"
 #include "det_fix.h"   // kDetBits, det_scale, k_det_absmax, k_det_convert
 
@@ -33,10 +32,6 @@ __device__ __forceinline__ void win_global_add(float* __restrict__ gin, unsigned
   if (DET) atomicAdd(acc + idx, (unsigned long long)__float2ll_rn(fix_in(v * sdet.mul, sdet)));
   else atomic_add_f32(gin + idx, v);
 }
-// A/B build switch (tools/ab/build_all_variant.sh -DADVCHAIN_WINDOW_FLAT=0): the branch-light deposits of the 3D window scatter
-#ifndef ADVCHAIN_WINDOW_FLAT
-#define ADVCHAIN_WINDOW_FLAT 1
-#endif
 constexpr int kWinT = 32;               // sample tile edge
 constexpr int kWinCells = 8192;         // LDS window budget in cells (all channels together): 32 KiB
 constexpr int kWinCellsC4 = 12288;      // four channels: 48 KiB (2048 cells per channel = 45 x 45 capped stretched 32 x 32 tiles)
@@ -540,7 +535,6 @@ k_scatter_window3d(const float* __restrict__ gout, const float* __restrict__ in,
     const bool inx[2] = {wx0 >= 0 && wx0 < ww, wx0 + 1 >= 0 && wx0 + 1 < ww};
     const bool iny[2] = {wy0 >= 0 && wy0 < wh, wy0 + 1 >= 0 && wy0 + 1 < wh};
     const bool inz[2] = {wz0 >= 0 && wz0 < wd, wz0 + 1 >= 0 && wz0 + 1 < wd};
-#if ADVCHAIN_WINDOW_FLAT
     {
       // branch-light deposits (round 6, as in the owner-computes scatters): every corner adds into the window with a masked
       // weight -- a corner that is invalid or lies outside a capped window adds zero at a cell of the lane's own -- and only a
@@ -576,27 +570,6 @@ k_scatter_window3d(const float* __restrict__ gout, const float* __restrict__ in,
             }
       }
     }
-#else
-#pragma unroll
-    for (int cz = 0; cz < 2; ++cz)
-#pragma unroll
-      for (int cy = 0; cy < 2; ++cy)
-#pragma unroll
-        for (int cx = 0; cx < 2; ++cx) {
-          if (!t.ok(cz, cy, cx)) continue;
-          const float w = t.w(cz, cy, cx);
-          if (inx[cx] && iny[cy] && inz[cz]) {
-            const float ws = w * fs.mul;
-            int* cell = win + cell0 + (cz ? plane : 0) + (cy ? ww : 0) + cx;
-#pragma unroll
-            for (int c = 0; c < CP; ++c) atomicAdd(cell + c * cells, fix_round(ws * fix_in(go[c0 + c], fs)));
-          } else {
-            const int64_t dst = vox0 + (cz ? planev : 0) + (cy ? rowv : 0) + cx + (int64_t)c0 * V;
-#pragma unroll
-            for (int c = 0; c < CP; ++c) win_global_add<DET>(ginn, accn, dst + (int64_t)c * V, w * go[c0 + c], sdet);
-          }
-        }
-#endif
     if ((SELF || GG) && c0 == 0) {
       float ax = 0.f, ay = 0.f, az = 0.f;
 #pragma unroll
@@ -653,9 +626,8 @@ extern "C" int advchain_get_deterministic(void);
 int advchain_scatter_window_launch(bool self, const float* gout, const float* in, const float* grid, float* gin,
                                    float* ggrid, int64_t N, int64_t C, int ndim, Dims d, int padding, int clamp_grid,
                                    int halo, int32_t* workspace, hipStream_t st, int32_t* det_ws, int32_t* stage_ws) {
-  static const bool off = getenv("ADVCHAIN_NO_WINDOW_SCATTER") != nullptr;   // A/B knob
-  static const int min3 = 2;   // measured optimum (was a tuning knob until round 4)
-  if (off || padding == PAD_REFLECTION) return ADVCHAIN_ERR_UNSUPPORTED;
+  constexpr int min3 = 2;      // measured optimum (round 4): the smallest 3D displacement hint taken here
+  if (padding == PAD_REFLECTION) return ADVCHAIN_ERR_UNSUPPORTED;
   if (d.s2 >= (1 << 23) || (int64_t)d.s0 * d.s1 >= (1 << 23)) return ADVCHAIN_ERR_UNSUPPORTED;   // 24-bit index products
   if (self ? C != ndim : (C != 1 && C != 2 && C != 4)) return ADVCHAIN_ERR_UNSUPPORTED;
   if (ndim == 3 && (halo < 0 ? -halo : halo) < min3) return ADVCHAIN_ERR_UNSUPPORTED;
@@ -724,8 +696,7 @@ int advchain_scatter_window_launch(bool self, const float* gout, const float* in
     // would be half empty; 88.2 -> 86.9 ms per cfg-5 call from the flat flush, -> 86.1 with this shape; 16 x 16 x 8 the same
     // on the solver's fields and worse on rough ones, whose windows outgrow the LDS budget).  Rows of 64: 32 x 8 x 4 stays
     // (cfg-3 14.41 against 14.58 ms)
-    static const int shape = getenv("ADVCHAIN_WIN3_SHAPE") ? atoi(getenv("ADVCHAIN_WIN3_SHAPE")) : -1;   // A/B knob: 0 | 1
-    const int sh = shape >= 0 ? (shape != 0) : ((d.s2 % 32 != 0 && d.s2 % 16 == 0) ? 1 : 0);
+    const int sh = (d.s2 % 32 != 0 && d.s2 % 16 == 0) ? 1 : 0;
     const int TXs = sh == 0 ? 32 : 16, TYs = kBlock / TXs, TZs = 4;
     const int n2 = (d.s2 + TXs - 1) / TXs, n1 = (d.s1 + TYs - 1) / TYs, n0 = (d.s0 + TZs - 1) / TZs;
     dim3 g((unsigned)(n0 * n1 * n2), (unsigned)N);

@@ -7,7 +7,6 @@ memory (``torch.empty``), the current stream and the autograd tape only.
 import collections
 import ctypes
 import functools
-import os
 
 import numpy as np
 import torch
@@ -181,8 +180,8 @@ def raw_grid_sample_fwd_ride(inp, grid, ride, interp, padding, clamp_grid, nonze
 
 
 DISP_SLOTS = 4096     # ADVCHAIN_DISP_SLOTS of include/advchain_hip.h
-ADAPTIVE_HALO = os.environ.get("ADVCHAIN_NO_ADAPTIVE_HALO") is None   # measure the displacement in forward and size the backward halos from it
-PAIR_FIELDS = os.environ.get("ADVCHAIN_NO_PAIR_FIELDS") is None       # a solver step integrates field(+v) and field(-v) as one batch
+ADAPTIVE_HALO = True  # measure the displacement in forward and size the backward halos from it
+PAIR_FIELDS = True    # a solver step integrates field(+v) and field(-v) as one batch
 TILED_SCATTER = True  # LDS-tiled owner-computes scatter (False: global-atomic kernels; for A/B tests)
 FUSED_LOSS = True     # the consistency loss straight from the logits (no P / D intermediates); False: A/B tests
 WIDE_LOSS_MIN_K = 17  # class counts from here on take the run-time-K loss kernels (loss_lp.hip: any K < 65536, no P / D); below:
@@ -675,7 +674,7 @@ def normalized_axpy(base, x, step=1.0, gate=None, old=None):
 # ------------------------------------------------------------------------------------------------
 # autograd Functions
 # ------------------------------------------------------------------------------------------------
-FUSED_UPDATE = os.environ.get("ADVCHAIN_FUSED_UPDATE_OFF") is None   # the parameter updates of an ascent step as ONE launch (advchain_update_multi); False: one per transform (A/B)
+FUSED_UPDATE = True   # the parameter updates of an ascent step as ONE launch (advchain_update_multi); False: one per transform
 
 
 @_on_tensor_device
@@ -1432,7 +1431,7 @@ class _DemonsField(torch.autograd.Function):
         site = None
         if frozen:           # every selection of this chain from the plan (its own recorded displacements, with the margin)
             if disp is None:
-                raise PlanMismatch("launch plan: a frozen chain needs the measured displacements (ADVCHAIN_NO_ADAPTIVE_HALO is set)")
+                raise PlanMismatch("launch plan: a frozen chain needs the measured displacements (ops.ADAPTIVE_HALO is off)")
             site = plan.take("chain", n=n, d=d)
             hints = site["bounds"].values()
         else:

@@ -61,3 +61,31 @@ def test_product_never_imports_the_oracle():
             if f.endswith(".py"):
                 src = open(os.path.join(base, f)).read()
                 assert "oracle" not in src.replace("the CPU oracle", ""), os.path.join(base, f)
+
+
+def test_product_reads_no_environment_knobs():
+    """The library reads one environment variable (the documented precision escape of the affine grad_in), the Python layer
+    one (the compiler of build.py); every other knob was an A/B switch and is gone."""
+    csrc = os.path.join(ROOT, "advchain_amd", "csrc")
+    names = set()
+    for f in sorted(os.listdir(csrc)):
+        path = os.path.join(csrc, f)
+        if os.path.isfile(path) and f.endswith((".hip", ".cpp", ".h")):
+            src = open(path).read()
+            found = re.findall(r"\bgetenv\s*\(\s*([^)]*)\)", src)
+            assert len(found) == len(re.findall(r"\bgetenv\b", src)), path
+            for arg in found:
+                m = re.fullmatch(r'"(\w+)"\s*', arg)
+                assert m, "getenv of something other than a literal in %s: %s" % (path, arg)
+                names.add(m.group(1))
+    assert names == {"ADVCHAIN_NO_AFFINE_BOX_GIN"}
+    names = set()
+    for base, _, files in os.walk(os.path.join(ROOT, "advchain_amd")):
+        for f in files:
+            if f.endswith(".py"):
+                src = open(os.path.join(base, f)).read()
+                found = re.findall(r"""\benviron\s*(?:\.get\s*\(|\[)\s*["'](\w+)["']""", src)
+                assert len(found) == len(re.findall(r"\benviron\b", src)), os.path.join(base, f)
+                assert not re.search(r"\bgetenv\b|\bputenv\b", src), os.path.join(base, f)
+                names.update(found)
+    assert names == {"HIPCC"}
