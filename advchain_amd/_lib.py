@@ -100,6 +100,12 @@ PROTOTYPES = {
     "advchain_dice_workspace": (_L, [_L, _L, _I, _P]),
     "advchain_dice_fwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _F, _F, _F, _P]),
     "advchain_dice_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _F, _F, _P]),
+    "advchain_edt": (_I, [_P, _I, _P, _I, _P, _L, _I, _P, _P]),
+    "advchain_signed_maps_workspace": (_L, [_L, _L, _I, _P]),
+    "advchain_signed_maps": (_I, [_P, _P, _P, _P, _L, _L, _I, _P, _P]),
+    "advchain_boundary_workspace": (_L, [_L, _L, _I, _P]),
+    "advchain_boundary_fwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _P]),
+    "advchain_boundary_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _P]),
     "advchain_image_diff2d_fwd": (_I, [_P, _P, _P, _L, _L, _P, _P]),
     "advchain_image_diff2d_bwd": (_I, [_P, _P, _P, _L, _L, _P, _P]),
     "advchain_jacobian_det2d_fwd": (_I, [_P, _P, _L, _P, _P]),

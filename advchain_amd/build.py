@@ -30,6 +30,8 @@ PER_FILE_FLAGS = {
     "deform_diff.hip": ["-ffp-contract=off"],           # one rounding per ATen op of the reference (bitwise forwards)
     "jacobian.hip": ["-ffp-contract=off"],              # the same stencils and determinant: map and statistics agree bitwise
     "seg_dice.hip": ["-ffp-contract=off"],              # fp32 / bf16 and vector / scalar instantiations round alike (bitwise)
+    "seg_boundary.hip": ["-ffp-contract=off"],          # the same
+    "edt.hip": ["-ffp-contract=off"],                   # f + (s delta)^2 rounds the same in every pass and tiling
 }
 
 

@@ -1,6 +1,8 @@
 """Segmentation losses (reference: advchain/common/loss.py): the consistency loss (loss.py:8-249) and the supervised
 ``contour_loss`` / ``One_Hot`` / ``cross_entropy_2D`` (loss.py:102-220, 252-326, on csrc/seg_loss.hip); ``dice_loss`` /
-``dice_ce_loss`` / ``cross_entropy_3D`` (not in the reference; csrc/seg_dice.hip) complete the supervised loss of a 2D or 3D step.
+``dice_ce_loss`` / ``cross_entropy_3D`` (not in the reference; csrc/seg_dice.hip) complete the supervised loss of a 2D or 3D step;
+``distance_transform_edt`` / ``signed_distance_maps`` / ``boundary_loss`` (not in the reference; csrc/edt.hip, csrc/seg_boundary.hip)
+are the exact Euclidean distance maps of masks and label maps on the device and the boundary loss on them.
 
 'mse', 'contour' and 'kl' all run in the fused HIP kernels (:func:`advchain_amd.ops.consistency_sums`:
 softmax + mask + squared error + KL sum + 3^d edge stencils in two launches forward, one backward per operand that
@@ -300,3 +302,106 @@ def dice_ce_loss(input, target, weight=None, ignore_background=False, batch_dice
     _dice_arguments("dice_ce_loss", input, target, weight, ignore_background, smooth, (dice_weight, ce_weight))
     return ops.dice_loss(input, target, weight=weight, ignore_background=ignore_background, batch_dice=batch_dice,
                          smooth=smooth, dice_weight=dice_weight, ce_weight=ce_weight)
+
+
+# ---- Euclidean distance maps and the boundary loss (not in the reference; csrc/edt.hip, csrc/seg_boundary.hip) -------------------
+
+def _check_sampling(name, sampling, ndim):
+    if sampling is None:
+        return None
+    try:
+        vals = [float(s) for s in sampling]
+    except TypeError:
+        raise ValueError("%s: sampling must be None or one number per spatial axis" % name)
+    if len(vals) != ndim:
+        raise ValueError("%s: sampling has the wrong length: %d numbers for %d spatial axes" % (name, len(vals), ndim))
+    for s in vals:
+        if not math.isfinite(s) or s <= 0:
+            raise ValueError("%s: sampling must be positive and finite, got %r" % (name, s))
+    return tuple(vals)
+
+
+def distance_transform_edt(mask, sampling=None, squared=False):
+    """Exact Euclidean distance transform on the device (csrc/edt.hip), scipy.ndimage.distance_transform_edt's definition.
+    mask: (B,H,W) or (B,D,H,W), bool, uint8, int64 or fp32, nonzero is foreground; every leading entry is transformed on its
+    own.  Returns fp32 of the same shape: at a foreground voxel the distance to the nearest zero voxel of the same entry, 0 at a
+    zero voxel, and +inf at the foreground voxels of an entry that has no zero voxel.  sampling: None (unit spacing) or one
+    positive finite number per spatial axis, in axis order (D,) H, W.  squared=True returns the squared distance (with unit
+    spacing an exact integer).  With unit spacing the arithmetic is int32 and the result the same bits on every run."""
+    if not isinstance(mask, torch.Tensor) or mask.dim() not in (3, 4):
+        raise ValueError("distance_transform_edt expects a 3-D (B,H,W) or 4-D (B,D,H,W) mask")
+    sampling = _check_sampling("distance_transform_edt", sampling, mask.dim() - 1)
+    _require_gpu(mask, "mask")
+    return ops.distance_transform_edt(mask, sampling=sampling, squared=bool(squared))
+
+
+def _check_num_classes(name, K):
+    if isinstance(K, bool) or not isinstance(K, int) or K < 1:
+        raise ValueError("%s: num_classes must be a positive integer, got %r" % (name, K))
+    if K > MAX_CLASSES:
+        raise NotImplementedError("%s takes at most %d classes, got %d" % (name, MAX_CLASSES, K))
+
+
+def signed_distance_maps(target, num_classes, sampling=None):
+    """Signed Euclidean distance maps of a label map, straight from the labels (no one-hot tensor; csrc/edt.hip).  target:
+    (N,H,W) or (N,D,H,W) int64 labels.  Returns (N,num_classes,dims) fp32 with
+
+        phi_nk(v) = d(v, F_nk) - d(v, B_nk),   F_nk = {u : target[n,u] == k},  B_nk its complement in entry n
+
+    positive outside the class, negative inside, at least one spacing in magnitude (the symmetric convention: Kervadec's
+    one_hot2dist shifts the inside by one voxel).  A label outside [0, num_classes), -100 included, belongs to no class.  A class
+    that is absent from entry n, or fills it, has no boundary: its plane is 0.  The maps are a constant (no gradient)."""
+    if not isinstance(target, torch.Tensor) or target.dim() not in (3, 4):
+        raise ValueError("signed_distance_maps expects 3-D (N,H,W) or 4-D (N,D,H,W) labels")
+    _check_num_classes("signed_distance_maps", num_classes)
+    sampling = _check_sampling("signed_distance_maps", sampling, target.dim() - 1)
+    _require_gpu(target, "target")
+    return ops.signed_distance_maps(target, num_classes, sampling=sampling)
+
+
+def boundary_loss(input, target=None, weight=None, ignore_background=True, sampling=None, dist_maps=None):
+    """Boundary (surface) loss of Kervadec et al. (csrc/seg_boundary.hip).  input: (N,K,H,W) or (N,K,D,H,W) fp32 or bf16 logits,
+    read as they are, the softmax over K runs inside the kernel (float16 is refused).  Exactly one of target ((N,dims) int64
+    labels: their :func:`signed_distance_maps` with `sampling` are computed on the device) and dist_maps ((N,K,dims) fp32, e.g.
+    from :func:`signed_distance_maps`, computed once and reused; a constant) supplies the maps phi:
+
+        loss = 1/(N V) sum_n sum_{v counted} sum_{k counted} omega_k p_k(v) phi_nk(v),   omega_k = w_k / sum of the counted w_j
+
+    Class 0 is not counted with ignore_background (the default, as in the paper).  With target, a voxel labelled -100 is not
+    counted (zero gradient) but stays in N V; any other label outside [0, K) makes the value and the gradient NaN.  With dist_maps
+    every voxel is counted.  weight: K numbers (tensor, list or array; constants), normalised on the device over the counted
+    classes.  Returns an fp32 scalar, bitwise reproducible; the gradient has the logits' dtype (computed in fp32, rounded once)."""
+    if not isinstance(input, torch.Tensor) or input.dim() not in (4, 5):
+        raise ValueError("boundary_loss expects 4-D (N,C,H,W) or 5-D (N,C,D,H,W) logits")
+    K = input.size(1)
+    if K > MAX_CLASSES:
+        raise NotImplementedError("boundary_loss takes at most %d classes, got %d" % (MAX_CLASSES, K))
+    sampling = _check_sampling("boundary_loss", sampling, input.dim() - 2)
+    if weight is not None:
+        if isinstance(weight, torch.Tensor):
+            n = weight.numel()
+        elif hasattr(weight, "__len__"):
+            n = len(weight)
+        else:
+            raise ValueError("boundary_loss: weight must be a tensor, list or array with one number per class")
+        if n != K:
+            raise ValueError("boundary_loss: weight has the wrong length: %d entries for %d classes" % (n, K))
+    if ignore_background and K == 1:
+        raise ValueError("boundary_loss: no class left (1 class, ignore_background=True)")
+    if (target is None) == (dist_maps is None):
+        raise ValueError("boundary_loss: exactly one of target and dist_maps supplies the distance maps")
+    if target is not None:
+        if not isinstance(target, torch.Tensor) or tuple(target.shape) != (input.shape[0],) + tuple(input.shape[2:]):
+            raise ValueError("boundary_loss: target must be labels of shape %s" % ((input.shape[0],) + tuple(input.shape[2:]),))
+    else:
+        if not isinstance(dist_maps, torch.Tensor) or dist_maps.shape != input.shape:
+            raise ValueError("boundary_loss: dist_maps must have the input's shape %s" % (tuple(input.shape),))
+        if sampling is not None:
+            raise ValueError("boundary_loss: sampling belongs to the maps; it has no meaning with dist_maps")
+        if torch.is_grad_enabled() and dist_maps.requires_grad:
+            warnings.warn('advchain_amd: boundary_loss treats dist_maps as a constant (detach it to silence this warning)',
+                          stacklevel=2)
+    _require_gpu(input, "input")
+    _require_gpu(target if target is not None else dist_maps, "target" if target is not None else "dist_maps")
+    return ops.boundary_loss(input, target=target, weight=weight, ignore_background=bool(ignore_background), sampling=sampling,
+                             dist_maps=dist_maps)

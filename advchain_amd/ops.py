@@ -2149,6 +2149,132 @@ def dice_loss(x, target, weight=None, ignore_background=False, batch_dice=False,
     return _Dice.apply(x, labels, soft, weight, (flags, float(smooth), float(dice_weight), float(ce_weight)))
 
 
+# ---- Euclidean distance transform, signed distance maps (csrc/edt.hip) and the boundary loss (csrc/seg_boundary.hip) -----------
+
+_MASK_KINDS = {torch.bool: 1, torch.uint8: 1, torch.int64: 2, torch.float32: 3}
+
+
+def _sampling_array(sampling, ndim):
+    return None if sampling is None else _lib.float_array([float(s) for s in sampling])
+
+
+def _edt_check(rc, what, sp):
+    if rc == -2:
+        raise NotImplementedError("%s: spatial shape %s is too large for the distance fields (%s)"
+                                  % (what, tuple(sp), _lib.load().advchain_last_error().decode()))
+    _lib.check(rc, what)
+
+
+@_on_tensor_device
+def distance_transform_edt(mask, sampling=None, squared=False):
+    """Exact Euclidean distance transform of every leading entry of mask (B,H,W) / (B,D,H,W) (bool, uint8, int64 or fp32;
+    nonzero is foreground): fp32 distance to the nearest zero voxel (include/advchain_hip.h: advchain_edt)."""
+    if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
+        raise _lib.AdvchainHipError("mask must be a CUDA/ROCm tensor: the advchain_amd kernels have no CPU path")
+    if mask.dtype not in _MASK_KINDS:
+        raise _lib.AdvchainHipError("mask must be bool, uint8, int64 or float32, got %s" % mask.dtype)
+    mask = mask.detach()
+    mask = mask if mask.is_contiguous() else mask.contiguous()
+    sp = tuple(mask.shape[1:])
+    out = torch.empty(mask.shape, device=mask.device, dtype=torch.float32)
+    if mask.numel() == 0:
+        raise ValueError("distance_transform_edt: empty mask %s" % (tuple(mask.shape),))
+    _edt_check(_lib.load().advchain_edt(_ptr(mask), _MASK_KINDS[mask.dtype], _sampling_array(sampling, len(sp)), int(bool(squared)),
+                                        _ptr(out), mask.shape[0], len(sp), _lib.dims_array(sp), _stream()), "edt", sp)
+    return out
+
+
+@_on_tensor_device
+def signed_distance_maps(labels, num_classes, sampling=None):
+    """(N,dims) int64 labels -> (N,K,dims) fp32 signed Euclidean distance maps, positive outside a class and negative inside
+    (include/advchain_hip.h: advchain_signed_maps)."""
+    labels = _dev_labels(labels.detach() if isinstance(labels, torch.Tensor) else labels, "target")
+    N, K = labels.shape[0], int(num_classes)
+    sp = tuple(labels.shape[1:])
+    lib = _lib.load()
+    dims = _lib.dims_array(sp)
+    n = lib.advchain_signed_maps_workspace(N, K, len(sp), dims)
+    if n < 0:
+        raise NotImplementedError("signed_distance_maps: N=%d, K=%d, spatial shape %s is too large for the distance fields (an axis "
+                                  "above 32767 -- 8192 for the leading axes -- or a squared diagonal of 2^30 or more)" % (N, K, sp))
+    ws = torch.empty(int(n), device=labels.device, dtype=torch.float32)
+    out = torch.empty((N, K) + sp, device=labels.device, dtype=torch.float32)
+    _edt_check(lib.advchain_signed_maps(_ptr(labels), _sampling_array(sampling, len(sp)), _ptr(out), _ptr(ws), N, K, len(sp), dims,
+                                        _stream()), "signed_maps", sp)
+    return out
+
+
+class _Boundary(torch.autograd.Function):
+    """1/(N V) sum omega_k softmax(x)_k maps_k over the counted voxels and classes (include/advchain_hip.h:
+    advchain_boundary_fwd).  Differentiable w.r.t. the logits; the maps are a constant.  Two launches forward, one backward."""
+
+    @staticmethod
+    def forward(ctx, x, labels, maps, weight, flags):
+        N, K = x.shape[:2]
+        sp = tuple(x.shape[2:])
+        dims = _lib.dims_array(sp)
+        lib = _lib.load()
+        need = ctx.needs_input_grad[0]
+        saved = torch.empty((N, 2) + sp, device=x.device, dtype=torch.float32) if need else None
+        n = lib.advchain_boundary_workspace(N, K, len(sp), dims)
+        if n < 0:
+            raise ValueError("bad loss shape: N=%d, K=%d, dims=%s" % (N, K, sp))
+        ws = torch.empty(int(n), device=x.device, dtype=torch.float32)
+        value = torch.empty((), device=x.device, dtype=torch.float32)
+        _lib.check(lib.advchain_boundary_fwd(_ptr(x), int(x.dtype == torch.bfloat16), _ptr(labels), _ptr(maps), _ptr(weight),
+                                             _ptr(saved), _ptr(ws), _ptr(value), N, K, len(sp), dims, flags, _stream()),
+                   "boundary_fwd")
+        if need:
+            ctx.save_for_backward(x, labels, maps, weight, saved)
+        ctx.flags = flags
+        return value
+
+    @staticmethod
+    def backward(ctx, gloss):
+        x, labels, maps, weight, saved = ctx.saved_tensors
+        N, K = x.shape[:2]
+        sp = tuple(x.shape[2:])
+        gs = _dev(gloss.reshape(1), "grad")
+        gx = torch.empty_like(x)
+        _lib.check(_lib.load().advchain_boundary_bwd(_ptr(x), int(x.dtype == torch.bfloat16), _ptr(labels), _ptr(maps), _ptr(weight),
+                                                     _ptr(saved), _ptr(gs), _ptr(gx), N, K, len(sp), _lib.dims_array(sp),
+                                                     ctx.flags, _stream()), "boundary_bwd")
+        return gx, None, None, None, None
+
+
+@_on_tensor_device
+def boundary_loss(x, target=None, weight=None, ignore_background=True, sampling=None, dist_maps=None):
+    """The boundary loss on the HIP kernels.  x (N,K,dims) fp32 / bf16 logits; exactly one of target ((N,dims) int64 labels:
+    the maps are computed from them) and dist_maps ((N,K,dims) fp32); weight: K class weights (tensor, list or array) or None.
+    Returns an fp32 scalar."""
+    x = _dev_logits(x, "input")
+    if x.dim() not in (4, 5):
+        raise ValueError("boundary_loss takes 4-D (N,C,H,W) or 5-D (N,C,D,H,W) input, got %d-D" % x.dim())
+    N, K = x.shape[:2]
+    sp = tuple(x.shape[2:])
+    labels = None
+    if target is not None:
+        labels = _dev_labels(target, "target")
+        if tuple(labels.shape) != (N,) + sp:
+            raise ValueError("label target must be %s, got %s" % ((N,) + sp, tuple(labels.shape)))
+        _same_device(x, labels)
+        maps = signed_distance_maps(labels, K, sampling)
+    else:
+        maps = _dev(dist_maps.detach() if isinstance(dist_maps, torch.Tensor) else dist_maps, "dist_maps")
+        if maps.shape != x.shape:
+            raise ValueError("dist_maps must have the input's shape %s, got %s" % (tuple(x.shape), tuple(maps.shape)))
+    if weight is not None:
+        if isinstance(weight, torch.Tensor):
+            weight = weight.detach().to(device=x.device, dtype=torch.float32)
+        else:
+            weight = torch.as_tensor(weight, dtype=torch.float32).to(x.device)
+        weight = weight.reshape(-1).contiguous()
+        if weight.numel() != K:
+            raise ValueError("weight must have %d entries, got %d" % (K, weight.numel()))
+    _same_device(x, labels, maps, weight)
+    return _Boundary.apply(x, labels, maps, weight, 1 if ignore_background else 0)
+
+
 class _Contour(torch.autograd.Function):
     """Edge energy of u = sum_{c in S}(input_c - T_c) (advchain/common/loss.py:102-220, Q14).  Differentiable w.r.t. the
     prediction and a soft target; the mask is a constant."""

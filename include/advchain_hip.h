@@ -763,6 +763,54 @@ int advchain_dice_bwd(const void* logits, int logits_bf16, const int64_t* labels
                       const float* lse, const float* coef, const float* grad_scale, void* grad_logits, float* grad_soft,
                       int64_t N, int64_t K, int ndim, const int64_t* dims, float dice_w, float ce_w, void* stream);
 
+/* ---- Euclidean distance transform and signed distance maps, 2D and 3D (edt.hip) --------------------------------------------
+ * Not in the reference.  Exact and separable: one pass along the contiguous axis (both sides of every row), then per further
+ * axis the lower envelope min_j f(j) + (s (i - j))^2 from LDS-staged lines.  `dims` is (H, W) or (D, H, W); `sampling` is NULL
+ * (unit spacing: int32 squared distances, exact, the same bits on every run) or ndim positive finite HOST floats in the order
+ * of dims (fp32 fields, no contraction).  ADVCHAIN_ERR_UNSUPPORTED for a shape the fields cannot hold: an axis above 32767, a
+ * squared diagonal of 2^30 or more (the "no seed yet" sentinel: sentinel + offset^2 stays below 2^31), or one of the
+ * non-contiguous axes above 16384 (8192 for the signed maps: one x of a whole line, of both fields, is staged in 64 KiB of LDS).
+ * No atomics, no memset, no host read-back; capturable on one stream.
+ * advchain_edt: mask (B, dims), mask_kind 1 = 8-bit (bool / uint8), 2 = int64, 3 = fp32; nonzero is foreground (NaN too).
+ *           out (B, dims) fp32: at a foreground voxel the Euclidean distance (squared = 1: its square, with unit spacing an
+ *           exact integer up to 2^24) to the nearest zero voxel of the same entry b, 0 at a zero voxel -- scipy's
+ *           distance_transform_edt -- and +inf at the foreground voxels of an entry without a zero voxel.  `out` doubles as
+ *           the field between the passes: no workspace.                                                                     */
+int advchain_edt(const void* mask, int mask_kind, const float* sampling, int squared, float* out, int64_t B, int ndim,
+                 const int64_t* dims, void* stream);
+/* advchain_signed_maps: labels (N, dims) int64 -> out (N, K, dims) fp32, straight from the labels (no one-hot tensor):
+ *           phi_nk(v) = d(v, F_nk) - d(v, B_nk), F_nk = {u: labels[n,u] == k}, B_nk its complement in entry n: positive outside
+ *           the class, negative inside, at least one spacing in magnitude (the symmetric convention; Kervadec's one_hot2dist
+ *           has (d(v, B) - 1) inside).  A label outside [0, K), -100 included, belongs to no class; labels are only compared
+ *           with class indices.  A class absent from entry n, or filling it, has no boundary: its plane is 0.  Both fields
+ *           of every (n, k) -- squared distance to the nearest member and to the nearest non-member -- go through the passes in
+ *           `workspace` (advchain_signed_maps_workspace 4-byte words, 16-byte aligned; host-only query, -1 for bad sizes; no
+ *           clearing needed); the last pass evaluates only the field that the voxel's own membership selects.              */
+int64_t advchain_signed_maps_workspace(int64_t N, int64_t K, int ndim, const int64_t* dims); /* floats */
+int advchain_signed_maps(const int64_t* labels, const float* sampling, float* out, float* workspace, int64_t N, int64_t K,
+                         int ndim, const int64_t* dims, void* stream);
+
+/* ---- boundary (surface) loss, 2D and 3D (seg_boundary.hip) -----------------------------------------------------------------
+ * Not in the reference (Kervadec et al.).  logits (N,K,dims) fp32 (logits_bf16 = 0) or bf16 (1), maps (N,K,dims) fp32 signed
+ * distance maps (a constant), p = softmax over K inside the kernel:
+ *   value = 1/(N voxels) sum_n sum_{v counted} sum_{k counted} omega_k p_k(v) maps_nk(v),  omega_k = w_k / sum of the counted w_j
+ * with w = weight (K floats, device) or 1 and class 0 not counted under ADVCHAIN_BOUNDARY_IGNORE_BACKGROUND.  labels (N,dims)
+ * int64 or NULL: with labels a voxel labelled -100 is not counted (it stays in N voxels) and any other label outside [0,K)
+ * makes value and gradient NaN; with NULL every voxel is counted.  One sweep over logits and maps (online max / sum), one
+ * partial per workgroup in `workspace` (advchain_boundary_workspace floats; host-only query, -1 for bad sizes; no clearing
+ * needed), added in a fixed order by a second launch: no float atomics, no host read-back, bitwise reproducible, capturable.
+ * saved (N,2,voxels floats, or NULL): log-sum-exp and t(v) = sum_k omega_k maps_k p_k per voxel, for the backward.            */
+#define ADVCHAIN_BOUNDARY_IGNORE_BACKGROUND 1
+int64_t advchain_boundary_workspace(int64_t N, int64_t K, int ndim, const int64_t* dims); /* floats */
+int advchain_boundary_fwd(const void* logits, int logits_bf16, const int64_t* labels, const float* maps, const float* weight,
+                          float* saved, float* workspace, float* value, int64_t N, int64_t K, int ndim, const int64_t* dims,
+                          int flags, void* stream);
+/* its gradient, one launch: grad_logits_j = gs / (N voxels) p_j (omega_j maps_j - t) at counted voxels, 0 elsewhere (the logits'
+ *           dtype, computed in fp32 and rounded once); gs = *grad_scale (device scalar, NULL = 1).                          */
+int advchain_boundary_bwd(const void* logits, int logits_bf16, const int64_t* labels, const float* maps, const float* weight,
+                          const float* saved, const float* grad_scale, void* grad_logits, int64_t N, int64_t K, int ndim,
+                          const int64_t* dims, int flags, void* stream);
+
 /* ---- deformation helpers (deform_diff.hip) -----------------------------------------------------------------------------
  * The module-level helpers of adv_morph.py that users call to inspect or regularise a deformation.  H and W at least 2 (the
  * reference raises IndexError at 1), N < 65536.  Forwards round once per ATen op of the reference, in its order (no

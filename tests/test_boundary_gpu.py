@@ -1,0 +1,337 @@
+"""distance_transform_edt / signed_distance_maps / boundary_loss on the HIP kernels (csrc/edt.hip, csrc/seg_boundary.hip) against
+the brute-force float64 forms of tests/edt_forms.py: every pass and tile shape of the transform (rows shorter and longer than a
+wave, a column longer than a 64-wide LDS tile, 3D, the longest axis outermost), masks with near and far seeds, lines and
+entries without a seed, every mask dtype; the signed maps for 1 to 70 classes with absent and filling classes, -100 and
+out-of-range labels; the loss on every load path with labels and with given maps, bf16 logits and misaligned tensors bit for
+bit, bitwise reproducibility, a captured graph and the device guard.
+
+Bounds.  Unit spacing: squared distances are exact integers (torch.equal) and a distance is within 1.2e-7 relative of the
+float64 root (one fp32 ulp: the root of an exact integer is rounded once).  With a sampling: SAMPLING_TOL relative (2e-6;
+tests/test_boundary_cpu.py says why it is not 1e-6).  Loss: value within 2e-5 max(|want|, S), S = 1/(N V) sum omega_k p_k
+|phi_k| the size of the summands, gradient within 1e-5 of the largest |expected|; the closed form evaluated in fp32 stays a
+factor of ten inside both (tests/test_boundary_cpu.py)."""
+import functools
+
+import pytest
+import torch
+
+from tests.edt_forms import (EDT_PATTERNS, EDT_SHAPES, LOSS_SHAPES, MAP_CASES, SAMPLING, SAMPLING_TOL, boundary_closed,
+                             boundary_scale, edt_brute, label_case, loss_case, loss_weights, mask_pattern, signed_maps_brute)
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda")
+ULP = 1.2e-7
+TOL_V, TOL_G = 2e-5, 1e-5
+
+
+def _L():
+    import advchain.common.loss as L
+    return L
+
+
+def _ids(shapes):
+    return ["x".join(map(str, s)) for s in shapes]
+
+
+def _relative_close(got, want, tol, what):
+    """Zeros and infinities exactly, everything else within tol relative."""
+    got = got.detach().cpu().double()
+    special = (want == 0) | torch.isinf(want)
+    assert torch.equal(got[special], want[special]), what
+    rel = ((got - want).abs()[~special] / want[~special].abs())
+    worst = float(rel.max()) if rel.numel() else 0.0
+    print("%s: relative error %.3g (bound %.3g)" % (what, worst, tol))
+    assert worst <= tol, (what, worst)
+
+
+@functools.lru_cache(maxsize=None)
+def _edt_reference(shape, name):
+    m = mask_pattern(shape, name, seed=len(shape))
+    return m, edt_brute(m, squared=True), edt_brute(m, SAMPLING[len(shape) - 1])
+
+
+@pytest.mark.parametrize("name", EDT_PATTERNS)
+@pytest.mark.parametrize("shape", EDT_SHAPES, ids=_ids(EDT_SHAPES))
+def test_transform_against_brute_force(shape, name):
+    L = _L()
+    m, want_sq, want_s = _edt_reference(shape, name)
+    md = m.to(DEV)
+    sq = L.distance_transform_edt(md, squared=True)
+    assert sq.dtype == torch.float32 and sq.shape == md.shape
+    assert torch.equal(sq.cpu().double(), want_sq), (shape, name)
+    d = L.distance_transform_edt(md)
+    _relative_close(d, want_sq.sqrt(), ULP, "edt %s %s" % (shape, name))
+    s = SAMPLING[len(shape) - 1]
+    _relative_close(L.distance_transform_edt(md, sampling=s), want_s, SAMPLING_TOL, "edt sampling %s %s" % (shape, name))
+    _relative_close(L.distance_transform_edt(md, sampling=s, squared=True), want_s * want_s, 2 * SAMPLING_TOL,
+                    "edt sampling squared %s %s" % (shape, name))
+    for other in (md.to(torch.uint8), md.long() * 7, md.float() * -0.5):
+        assert torch.equal(L.distance_transform_edt(other), d)
+    assert torch.equal(L.distance_transform_edt(md), d)
+    if name == "full_entry":
+        assert bool(torch.isinf(d[0]).all()) and bool(torch.isfinite(d[1:]).all())
+
+
+@functools.lru_cache(maxsize=None)
+def _map_reference(K, shape):
+    y = label_case(K, shape, seed=K)
+    return y, signed_maps_brute(y, K), signed_maps_brute(y, K, SAMPLING[len(shape) - 1])
+
+
+@pytest.mark.parametrize("K,shape", MAP_CASES, ids=["K%d" % k for k, _ in MAP_CASES])
+def test_signed_maps_against_brute_force(K, shape):
+    L = _L()
+    y, want, want_s = _map_reference(K, shape)
+    yd = y.to(DEV)
+    got = L.signed_distance_maps(yd, K)
+    assert got.dtype == torch.float32 and tuple(got.shape) == (shape[0], K) + tuple(shape[1:])
+    _relative_close(got, want, ULP, "maps K=%d" % K)
+    assert float(got[-1].abs().max()) == 0.0                       # class 0 fills the last entry, every other class is absent
+    if K > 1:
+        assert float(got[:, K - 1].abs().max()) == 0.0             # absent everywhere
+    assert float(got[got != 0].abs().min()) >= 1.0                  # at least one spacing in magnitude
+    inside = torch.stack([yd == k for k in range(K)], 1)
+    assert bool((got[inside] <= 0).all()) and bool((got[~inside] >= 0).all())
+    _relative_close(L.signed_distance_maps(yd, K, sampling=SAMPLING[len(shape) - 1]), want_s, SAMPLING_TOL, "maps sampling K=%d" % K)
+    assert torch.equal(L.signed_distance_maps(yd, K), got)
+    # the map of class k is the difference of two transforms of its membership mask
+    for k in range(min(K, 3)):
+        member = yd == k
+        pair = L.distance_transform_edt(~member) - L.distance_transform_edt(member)
+        keep = torch.isfinite(pair)
+        assert torch.equal(got[:, k][keep], pair[keep])
+
+
+def _grads_of(fn, x):
+    v = fn()
+    return v.detach(), torch.autograd.grad(v, x)[0]
+
+
+@functools.lru_cache(maxsize=None)
+def _loss_reference(shape):
+    K = shape[1]
+    x, y = loss_case(shape, seed=K)
+    return x, y, signed_maps_brute(y, K)
+
+
+def _against_closed(x, fn, closed_kw, what):
+    v, g = _grads_of(fn, x)
+    assert v.dtype == torch.float32 and v.dim() == 0 and g.dtype == x.dtype and g.shape == x.shape
+    x64 = x.detach().cpu().double().requires_grad_(True)
+    w = boundary_closed(x64, **closed_kw)
+    (gw,) = torch.autograd.grad(w, x64)
+    scale = max(abs(float(w.detach())), boundary_scale(x64.detach(), **{k: closed_kw[k] for k in closed_kw if k != "sampling"}))
+    err = abs(float(v) - float(w.detach()))
+    gerr, gmax = float((g.cpu().double() - gw).abs().max()), max(float(gw.abs().max()), 1e-30)
+    print("%s: value %.9g, float64 %.9g, |diff| %.3g of %.3g; gradient |diff| %.3g of %.3g"
+          % (what, float(v), float(w.detach()), err, scale, gerr, gmax))
+    assert err <= TOL_V * scale, (what, float(v), float(w.detach()))
+    assert gerr <= TOL_G * gmax, (what, gerr, gmax)
+
+
+@pytest.mark.parametrize("shape", LOSS_SHAPES, ids=_ids(LOSS_SHAPES))
+def test_loss_against_float64_form(shape):
+    L = _L()
+    K = shape[1]
+    x0, y, maps64 = _loss_reference(shape)
+    x = x0.to(DEV).requires_grad_(True)
+    yd = y.to(DEV)
+    given = L.signed_distance_maps(yd, K)
+    given64 = given.cpu().double()
+    for ign in (False, True):
+        for w in (None, loss_weights(K), torch.tensor(loss_weights(K), device=DEV)):
+            wl = w.tolist() if isinstance(w, torch.Tensor) else w
+            what = "%s ign=%s w=%s" % (shape, ign, w is not None)
+            _against_closed(x, lambda: L.boundary_loss(x, yd, weight=w, ignore_background=ign),
+                            dict(target=y, weight=wl, ignore_background=ign, dist_maps=maps64), "labels " + what)
+            _against_closed(x, lambda: L.boundary_loss(x, dist_maps=given, weight=w, ignore_background=ign),
+                            dict(weight=wl, ignore_background=ign, dist_maps=given64), "maps " + what)
+    with pytest.raises(ValueError, match="ignore_background"):
+        L.boundary_loss(x[:, :1], yd)
+    v = L.boundary_loss(x[:, :1].contiguous(), yd, ignore_background=False)
+    torch.cuda.synchronize()
+    assert v.dim() == 0
+
+
+def test_default_arguments_and_sampling():
+    L = _L()
+    shape = (3, 4, 36, 57)
+    x0, y, maps64 = _loss_reference(shape)
+    x = x0.to(DEV).requires_grad_(True)
+    yd = y.to(DEV)
+    _against_closed(x, lambda: L.boundary_loss(x, yd), dict(target=y, dist_maps=maps64), "defaults")
+    s = SAMPLING[2]
+    maps_s = signed_maps_brute(y, 4, s)
+    _against_closed(x, lambda: L.boundary_loss(x, yd, sampling=s, ignore_background=False),
+                    dict(target=y, ignore_background=False, dist_maps=maps_s), "sampling")
+
+
+@pytest.mark.parametrize("shape", LOSS_SHAPES, ids=_ids(LOSS_SHAPES))
+def test_given_maps_are_the_label_path_bit_for_bit(shape):
+    L = _L()
+    K = shape[1]
+    x0, y = loss_case(shape, seed=K + 1, ignored=False)
+    x = x0.to(DEV).requires_grad_(True)
+    yd = y.to(DEV)
+    maps = L.signed_distance_maps(yd, K)
+    for ign in (False, True):
+        va, ga = _grads_of(lambda: L.boundary_loss(x, yd, ignore_background=ign, weight=loss_weights(K)), x)
+        vb, gb = _grads_of(lambda: L.boundary_loss(x, dist_maps=maps, ignore_background=ign, weight=loss_weights(K)), x)
+        assert torch.equal(va, vb) and torch.equal(ga, gb)
+
+
+def test_ignored_and_out_of_range_labels():
+    L = _L()
+    shape = (3, 4, 36, 57)
+    x0, y, _ = _loss_reference(shape)
+    x = x0.to(DEV).requires_grad_(True)
+    yd = y.to(DEV)
+    v, g = _grads_of(lambda: L.boundary_loss(x, yd), x)
+    assert bool(torch.isfinite(v)) and bool(torch.isfinite(g).all())
+    assert float(g.movedim(1, -1)[yd == -100].abs().max()) == 0.0
+    assert float(g.movedim(1, -1)[yd != -100].abs().max()) > 0.0
+    for bad in (4, -1, 2 ** 40):                                   # NaN, never an address
+        yb = yd.clone()
+        yb[0, 2, 3] = bad
+        vb, gb = _grads_of(lambda: L.boundary_loss(x, yb), x)
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(vb)), (bad, float(vb))
+        assert bool(torch.isnan(gb[0, :, 2, 3]).all())
+        maps = L.signed_distance_maps(yb, 4)
+        assert bool(torch.isfinite(maps).all())
+    # with given maps every voxel is counted
+    maps = L.signed_distance_maps(yd, 4)
+    vm, gm = _grads_of(lambda: L.boundary_loss(x, dist_maps=maps), x)
+    assert float(gm.movedim(1, -1)[yd == -100].abs().max()) > 0.0
+
+
+def test_refused_inputs():
+    from advchain_amd import _lib
+    L = _L()
+    x = torch.randn(2, 4, 8, 8, device=DEV)
+    y = torch.randint(0, 4, (2, 8, 8), device=DEV)
+    maps = L.signed_distance_maps(y, 4)
+    with pytest.raises(_lib.AdvchainHipError, match="float16"):
+        L.boundary_loss(x.half(), y)
+    with pytest.raises(_lib.AdvchainHipError):
+        L.boundary_loss(x, y.cpu())
+    with pytest.raises(_lib.AdvchainHipError):
+        L.boundary_loss(x, dist_maps=maps.cpu())
+    with pytest.raises(_lib.AdvchainHipError):
+        L.boundary_loss(x, dist_maps=maps.double())
+    with pytest.raises(RuntimeError):
+        L.boundary_loss(x, y.int())
+    with pytest.raises(RuntimeError):
+        L.signed_distance_maps(y.int(), 4)
+    with pytest.raises(_lib.AdvchainHipError):
+        L.distance_transform_edt(y.int())
+    with pytest.raises(NotImplementedError):
+        L.distance_transform_edt(torch.ones(1, 2, 40000, device=DEV, dtype=torch.bool))
+    with pytest.warns(UserWarning, match="constant"):
+        L.boundary_loss(x, dist_maps=maps.clone().requires_grad_(True))
+
+
+@pytest.mark.parametrize("shape", [(3, 4, 36, 57), (2, 20, 33, 31)], ids=["vector", "scalar"])
+def test_bf16_logits_are_the_fp32_call_on_the_upcast(shape):
+    L = _L()
+    K = shape[1]
+    x0, y, _ = _loss_reference(shape)
+    yd = y.to(DEV)
+    xb = x0.to(DEV).to(torch.bfloat16).requires_grad_(True)
+    x32 = xb.detach().float().requires_grad_(True)
+    maps = L.signed_distance_maps(yd, K)
+    for kw in (dict(target=yd), dict(dist_maps=maps, ignore_background=False)):
+        vb, gb = _grads_of(lambda: L.boundary_loss(xb, weight=loss_weights(K), **kw), xb)
+        v32, g32 = _grads_of(lambda: L.boundary_loss(x32, weight=loss_weights(K), **kw), x32)
+        assert vb.dtype == torch.float32 and gb.dtype == torch.bfloat16
+        assert torch.equal(vb, v32), (float(vb), float(v32))
+        assert torch.equal(gb, g32.bfloat16())
+
+
+def _offset_copy(t):
+    """The same values one element further into a fresh storage."""
+    buf = torch.empty(t.numel() + 1, device=t.device, dtype=t.dtype)
+    buf[1:] = t.reshape(-1)
+    return buf[1:].view(t.shape)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_value_does_not_depend_on_alignment(dtype):
+    L = _L()
+    shape = (3, 4, 36, 57)                       # V % 4 == 0
+    x0, y, _ = _loss_reference(shape)
+    yd = y.to(DEV)
+    xa = x0.to(DEV).to(dtype).requires_grad_(True)
+    xo = _offset_copy(xa.detach()).requires_grad_(True)
+    assert xa.data_ptr() % 16 == 0 and xo.data_ptr() % 16 != 0 and xo.is_contiguous()
+    maps = L.signed_distance_maps(yd, 4)
+    va, ga = _grads_of(lambda: L.boundary_loss(xa, yd), xa)
+    for xx, kw in ((xo, dict(target=yd)), (xa, dict(target=_offset_copy(yd)))):
+        vo, go = _grads_of(lambda: L.boundary_loss(xx, **kw), xx)
+        assert torch.equal(va, vo) and torch.equal(ga, go)
+    assert torch.equal(L.signed_distance_maps(_offset_copy(yd), 4), maps)
+    va, ga = _grads_of(lambda: L.boundary_loss(xa, dist_maps=maps), xa)
+    vo, go = _grads_of(lambda: L.boundary_loss(xa, dist_maps=_offset_copy(maps)), xa)
+    assert torch.equal(va, vo) and torch.equal(ga, go)
+    m = yd > 0
+    assert torch.equal(L.distance_transform_edt(_offset_copy(m)), L.distance_transform_edt(m))
+
+
+def test_runs_are_bitwise_identical_and_a_captured_graph_replays_them():
+    L = _L()
+    shape = (3, 4, 36, 57)
+    x0, y, _ = _loss_reference(shape)
+    x = x0.to(DEV).requires_grad_(True)
+    yd = y.to(DEV)
+    w = torch.rand(4, device=DEV) + 0.5
+
+    def step():
+        maps = L.signed_distance_maps(yd, 4, sampling=(1.5, 0.7))
+        edt = L.distance_transform_edt(yd > 0)
+        v, g = _grads_of(lambda: L.boundary_loss(x, dist_maps=maps, weight=w) + L.boundary_loss(x, yd), x)
+        return maps, edt, v, g
+
+    eager = step()
+    again = step()
+    assert all(torch.equal(a, b) for a, b in zip(eager, again))
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(2):
+            step()
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        static = step()
+    g.replay()
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(static, eager))
+    with torch.no_grad():
+        x.mul_(0.5)
+        yd.copy_(yd.flip(1))
+    g.replay()
+    fresh = step()
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(static, fresh))
+    assert not torch.equal(fresh[0], eager[0])
+
+
+def test_tensors_on_another_device_than_the_current_one():
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two devices")
+    L = _L()
+    x0, y, _ = _loss_reference((3, 4, 36, 57))
+    x = x0.to(DEV).requires_grad_(True)
+    yd = y.to(DEV)
+    v0, g0 = _grads_of(lambda: L.boundary_loss(x, yd), x)
+    m0, e0 = L.signed_distance_maps(yd, 4), L.distance_transform_edt(yd > 0)
+    x1 = x.detach().to("cuda:1").requires_grad_(True)
+    y1 = yd.to("cuda:1")
+    assert torch.cuda.current_device() == 0
+    v1, g1 = _grads_of(lambda: L.boundary_loss(x1, y1), x1)
+    m1, e1 = L.signed_distance_maps(y1, 4), L.distance_transform_edt(y1 > 0)
+    torch.cuda.synchronize("cuda:1")
+    assert v1.device == x1.device and g1.device == x1.device and m1.device == x1.device and e1.device == x1.device
+    assert torch.equal(v1.cpu(), v0.cpu()) and torch.equal(g1.cpu(), g0.cpu())
+    assert torch.equal(m1.cpu(), m0.cpu()) and torch.equal(e1.cpu(), e0.cpu())
