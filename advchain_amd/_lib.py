@@ -63,6 +63,9 @@ PROTOTYPES = {
     "advchain_expo_chain_fwd": (_I, [_P, _P, _P, _L, _I, _P, _I, _P, _P, _P, _P]),
     "advchain_expo_chain_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _P, _I, _P]),
     "advchain_gauss_xy": (_I, [_P, _P, _P, _L, _L, _I, _P, _P, _I, _I, _F, _P, _P, _L]),
+    "advchain_gauss_xy_staged": (_I, [_P, _P, _P, _L, _L, _I, _P, _P, _I, _I, _F, _P, _P, _L]),
+    "advchain_gauss_xy_lanes": (_I, [_P, _P, _P, _L, _L, _I, _P, _P, _I, _I, _F, _P, _P, _L, _I, _I]),
+    "advchain_gauss_xy_plan": (_I, [_I, _P, _L, _P, _P, _P]),
     "advchain_gauss_small": (_I, [_P, _P, _L, _I, _P, _P, _I, _F, _P]),
     "advchain_gauss_small_pair": (_I, [_P, _P, _L, _I, _P, _P, _F, _I, _P]),
     "advchain_axpy": (_I, [_P, _P, _P, _F, _L, _P]),

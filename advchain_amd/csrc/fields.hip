@@ -1173,6 +1173,104 @@ k_gauss_xy(const float* __restrict__ in, float* __restrict__ out, const float* _
   }
 }
 
+// The lane form of k_gauss_xy, for rows that never straddle a wave (Q = W/4 in {2, 4, .. 64}): the x neighbours of a staged
+// quad are the quads of lanes -1 and +1 of the same wave, so the x pass runs on registers (whole-wave DPP shifts) straight
+// after the loads and writes B; buffer A, its zero fill, its LDS round trip and the first barrier are gone, and the LDS is
+// (TY+8) * W * 4 bytes instead of (TY+8) * (2W+8) * 4.  Same loads, same prologue expressions, same multiply-add chain per
+// output in the same order, same y pass as k_gauss_xy: bit-identical results.  The zeros a row end shifts in stand for the
+// zero borders of A.  Every lane stays active through the shifts: an item past R * Q is clamped to the last one and only
+// its LDS store is masked (NT is a multiple of 64 and the round guard is uniform over the workgroup).  U: rounds of NT
+// items that cover (TY+8) * Q at most; all of a thread's loads are requested before its first x pass.
+template <int PRE, int POST, int NT, int U>
+__global__ void __launch_bounds__(NT)
+k_gauss_xy_lanes(const float* __restrict__ in, float* __restrict__ out, const float* __restrict__ aux, Dims d, int C, GaussW gw,
+                 float scale, int TY, const float* __restrict__ in_hi, int planes_lo) {
+  extern __shared__ float gx_lds[];
+  const int W = d.s2, Q = W >> 2;
+  const int R = TY + 8, NI = R * Q;
+  float* B = gx_lds;                       // [R][W]
+  const int plane = blockIdx.z, iz = blockIdx.y;
+  const int y0 = blockIdx.x * TY;
+  const int caxis = 2 - plane % C;
+  const int Sc = caxis == 2 ? d.s2 : (caxis == 1 ? d.s1 : d.s0);
+  const int64_t base = ((int64_t)plane * d.s0 + iz) * d.s1 * (int64_t)W;
+  const float* src = (in_hi && plane >= planes_lo) ? in_hi + (((int64_t)(plane - planes_lo) * d.s0 + iz) * d.s1 * (int64_t)W) : in + base;
+  // ---- loads (unconditional, from the clamped row of the clamped item)
+  float4 v[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    if (u * NT >= NI) break;                                       // uniform over the workgroup
+    const int e = min((int)threadIdx.x + u * NT, NI - 1);
+    const int r = e / Q, q = e - r * Q;
+    const int gy = y0 - 4 + r;
+    v[u] = *reinterpret_cast<const float4*>(src + (int64_t)min(max(gy, 0), d.s1 - 1) * W + 4 * q);
+  }
+  // ---- prologue and x pass in registers, rows outside the volume zeroed by a select
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    if (u * NT >= NI) break;
+    const int e0 = (int)threadIdx.x + u * NT;
+    const int e = min(e0, NI - 1);
+    const int r = e / Q, q = e - r * Q;
+    const int gy = y0 - 4 + r;
+    const bool inr = gy >= 0 && gy < d.s1;
+    float t[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+      if (PRE == 1) t[o] *= scale;
+      if (PRE == 2) {
+        float sl;
+        t[o] = border_identity(t[o], Sc, sl) - lin_coord(caxis == 2 ? 4 * q + o : (caxis == 1 ? gy : iz), Sc);
+      }
+      if (!inr) t[o] = 0.f;
+    }
+    float win[12];
+    const bool first = q == 0, last = q == Q - 1;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+      const float pv = lane_prev_f(t[o]), nx = lane_next_f(t[o]);
+      win[o] = first ? 0.f : pv;
+      win[4 + o] = t[o];
+      win[8 + o] = last ? 0.f : nx;
+    }
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int o = 0; o < 4; ++o)
+#pragma unroll
+      for (int k = 0; k < 9; ++k) acc[o] += gw.w[k] * win[o + k];
+    if (e0 < NI) *reinterpret_cast<float4*>(B + r * W + 4 * q) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+  }
+  __syncthreads();
+  // ---- y pass on the owned rows
+  for (int e = threadIdx.x; e < TY * Q; e += NT) {
+    const int ry = e / Q, q = e - ry * Q;
+    const int gy = y0 + ry;
+    if (gy >= d.s1) continue;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      const float4 b = *reinterpret_cast<const float4*>(B + (ry + k) * W + 4 * q);
+      acc[0] += gw.w[k] * b.x; acc[1] += gw.w[k] * b.y; acc[2] += gw.w[k] * b.z; acc[3] += gw.w[k] * b.w;
+    }
+    const int64_t off = base + (int64_t)gy * W + 4 * q;
+    if (POST == 1) {
+#pragma unroll
+      for (int o = 0; o < 4; ++o) acc[o] += lin_coord(caxis == 2 ? 4 * q + o : (caxis == 1 ? gy : iz), Sc);
+    }
+    if (POST == 2) {
+      const float4 a4 = *reinterpret_cast<const float4*>(aux + off);
+      const float av[4] = {a4.x, a4.y, a4.z, a4.w};
+#pragma unroll
+      for (int o = 0; o < 4; ++o) {
+        float slope;
+        border_identity(av[o], Sc, slope);
+        acc[o] *= slope;
+      }
+    }
+    *reinterpret_cast<float4*>(out + off) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+  }
+}
+
 // z pass, marching: a thread owns 4 consecutive x of one (plane, y) column and walks a chunk of ZC planes with the taps in
 // registers -- 1 + 8/ZC 16-byte loads per output instead of 9.  The per-output kernel above asks for every plane nine
 // times from workgroups that run on different XCDs at the same moment (no L2 reuse): at 8 x 3 x 160 x 160 x 80 the z pass
@@ -1652,6 +1750,8 @@ int advchain_tp_interp_sumsq_ordered(const float* coef, const int32_t* itab, con
 // advchain_gauss_small_pair (forward) + advchain_tp_interp_fwd in ONE launch: vel (P planes of g1 x g2) -> s1 (2P planes, the
 // smoothed batch [v; -v]) and out (2P planes of S1 x S2) = (add_identity ? identity : 0) + scale * up(s1).  2D, planes of at most
 // 1024 values, the 9-tap window.  ADVCHAIN_ERR_UNSUPPORTED (-2), nothing enqueued, for anything else: issue the two calls.
+// (kTpChunk = 32 rows a workgroup stays: with the rows as a run-time argument 128 planes of 256 x 256 took 22.9 us at 32 rows,
+// 29.4 at 16 and 28.2 at 64 as two chunks of the row loop -- profiles/r20/gauss_lanes.)
 int advchain_tp_interp_fwd_smoothed_pair(const float* vel, float* s1, float* out, const int32_t* itab, const float* ftab,
                                          const int64_t* S, const int64_t* g, const int64_t* B, int64_t P, int64_t C,
                                          int add_identity, float scale, float* disp_out, const float* weights9, float gscale,
@@ -2025,13 +2125,41 @@ bool advchain_gauss_xy_takes(int ndim, const int64_t* dims, int64_t planes) {
   return (size_t)(TY + 8) * (2 * d.s2 + 8) * sizeof(float) <= 65536;
 }
 
-extern "C" {
+// The lane form (k_gauss_xy_lanes) can take rows that never straddle a wave: Q = W/4 a power of two in 2 .. 64, W in 8 .. 256 --
+// a subset of the staged form's shapes (advchain_gauss_xy_takes is unchanged).  Where it is the default: gauss_xy_lane_rule.
+static bool gauss_xy_lane_shape(const Dims& d) {
+  const int Q = d.s2 >> 2;
+  return (d.s2 & 3) == 0 && Q >= 2 && Q <= 64 && (Q & (Q - 1)) == 0 && d.s1 >= 8;
+}
+// The five (rows per workgroup, threads per workgroup) the lane form is built for, with U = ceil((TY+8) * 64 / NT).
+static bool gauss_xy_lane_tile_ok(int ty, int nt) {
+  return (ty == 16 && (nt == 256 || nt == 512)) || (ty == 32 && (nt == 256 || nt == 512)) || (ty == 64 && nt == 1024);
+}
+// Where advchain_gauss_xy runs the lane form, and with which tile: rows of 256 voxels (one row a wave), 32 rows and 512 threads
+// a workgroup; every other shape keeps the staged kernel.  Measured (profiles/r20/gauss_lanes, medians of 50, us): 128 planes
+// of 256 x 256, forward <2,1> staged 36.6, lanes 31.8 / 29.5 / 31.8 / 28.2 / 27.5 at (16,256) / (16,512) / (32,256) / (32,512) /
+// (64,1024); adjoint <0,2> with the split input 30.0 against 25.4 / 23.7 / 25.4 / 23.6 / 24.0.  Eight waves a workgroup beat
+// four at either tile height; (32,512) wins by the project's rule at both shapes in both jobs, (64,1024) in three of the four
+// and within 0.8 us of it, and (32,512) gives a small launch twice the workgroups (64 rows: 4 a plane).  Rows of 64
+// voxels lose: 24 planes of 128 x 128 x 64 staged 61.0, lanes 65.9 at best (32,256), 80.6 at (32,512) -- four rows share a
+// wave there and a tile is 2.5 rounds of 256 items.  Rows of 8 .. 128 voxels in 2D are not measured and stay staged too.
+static bool gauss_xy_lane_rule(const Dims& d, int64_t planes, int& ty, int& nt) {
+  (void)planes;
+  if (!gauss_xy_lane_shape(d) || d.s2 != 256) return false;
+  ty = 32; nt = 512;
+  return true;
+}
+static inline int gauss_xy_clamp_ty(int TY, const Dims& d) { return TY > d.s1 ? (d.s1 + 7) / 8 * 8 : TY; }
+
+enum { kGxyAuto = 0, kGxyStaged = 1, kGxyLanes = 2 };
 
 // x and y passes of the separable Gaussian in one launch (rows of 4k <= 512 voxels, 16-byte aligned tensors).  `post` is
 // only legal when y is the last axis (ndim == 2).  Returns ADVCHAIN_ERR_UNSUPPORTED when the shape does not qualify: the
-// caller then runs the per-axis passes.
-int advchain_gauss_xy(const float* in, float* out, const float* aux, int64_t planes, int64_t C, int ndim, const int64_t* dims,
-                      const float* weights9, int pre, int post, float scale, void* stream, const float* in_hi, int64_t planes_lo) {
+// caller then runs the per-axis passes.  want: kGxyAuto -- the lane form where gauss_xy_lane_rule says so, else the staged one;
+// kGxyStaged -- always the staged kernel; kGxyLanes -- the lane form with the tile (ty, nt), unsupported for other shapes.
+static int gauss_xy_launch(const float* in, float* out, const float* aux, int64_t planes, int64_t C, int ndim, const int64_t* dims,
+                           const float* weights9, int pre, int post, float scale, void* stream, const float* in_hi, int64_t planes_lo,
+                           int want, int ty, int nt) {
   ADVCHAIN_CHECK_ARG(in && out && in != out && weights9, "gauss_xy: null/aliased pointer");
   ADVCHAIN_CHECK_ARG(fdims_ok(ndim, dims), "gauss_xy: bad dims");
   ADVCHAIN_CHECK_ARG(C >= 1 && C <= 3 && pre >= 0 && pre <= 2 && post >= 0 && post <= 2 && (post != 2 || aux), "gauss_xy: bad C/pre/post");
@@ -2042,16 +2170,50 @@ int advchain_gauss_xy(const float* in, float* out, const float* aux, int64_t pla
         reinterpret_cast<uintptr_t>(in_hi)) & 15) != 0)
     return ADVCHAIN_ERR_UNSUPPORTED;
   ADVCHAIN_CHECK_ARG(!in_hi || (planes_lo > 0 && planes_lo < planes), "gauss_xy: bad split of the input planes");
+  if (want == kGxyLanes) {
+    ADVCHAIN_CHECK_ARG(gauss_xy_lane_tile_ok(ty, nt), "gauss_xy_lanes: (ty, nt) must be (16,256), (16,512), (32,256), (32,512) or (64,1024)");
+    if (!gauss_xy_lane_shape(d)) return ADVCHAIN_ERR_UNSUPPORTED;
+  }
   if (planes == 0 || d.voxels() == 0) return ADVCHAIN_OK;
+  GaussW gw;
+  for (int k = 0; k < 9; ++k) gw.w[k] = weights9[k];
+  hipStream_t st = (hipStream_t)stream;
+  if (want == kGxyLanes || (want == kGxyAuto && gauss_xy_lane_rule(d, planes, ty, nt))) {
+    const int TY = gauss_xy_clamp_ty(ty, d);
+    const size_t lds = (size_t)(TY + 8) * d.s2 * sizeof(float);
+    dim3 grid((unsigned)((d.s1 + TY - 1) / TY), (unsigned)d.s0, (unsigned)planes);
+#define GXL(PRE, POST, NT_, U_) do { \
+    auto kern = k_gauss_xy_lanes<PRE, POST, NT_, U_>; \
+    if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+    hipLaunchKernelGGL(kern, grid, dim3(NT_), lds, st, in, out, aux, d, (int)C, gw, scale, TY, in_hi, (int)planes_lo); } while (0)
+#define GXL_TILE(PRE, POST) do { \
+    if (ty == 16 && nt == 256) GXL(PRE, POST, 256, 6); \
+    else if (ty == 16) GXL(PRE, POST, 512, 3); \
+    else if (ty == 32 && nt == 256) GXL(PRE, POST, 256, 10); \
+    else if (ty == 32) GXL(PRE, POST, 512, 5); \
+    else GXL(PRE, POST, 1024, 5); } while (0)
+    switch (pre * 3 + post) {
+      case 0: GXL_TILE(0, 0); break;
+      case 1: GXL_TILE(0, 1); break;
+      case 2: GXL_TILE(0, 2); break;
+      case 3: GXL_TILE(1, 0); break;
+      case 4: GXL_TILE(1, 1); break;
+      case 5: GXL_TILE(1, 2); break;
+      case 6: GXL_TILE(2, 0); break;
+      case 7: GXL_TILE(2, 1); break;
+      default: GXL_TILE(2, 2); break;
+    }
+#undef GXL_TILE
+#undef GXL
+    ADVCHAIN_LAUNCH_CHECK();
+    return ADVCHAIN_OK;
+  }
   int TY = 32;
   while (TY > 8 && (size_t)(TY + 8) * (2 * d.s2 + 8) * 4 > 53248) TY >>= 1;     // 52 KiB: three workgroups a CU
   if (TY > d.s1) TY = (d.s1 + 7) / 8 * 8;
   const size_t lds = (size_t)(TY + 8) * (2 * d.s2 + 8) * sizeof(float);
   if (lds > 65536) return ADVCHAIN_ERR_UNSUPPORTED;
-  GaussW gw;
-  for (int k = 0; k < 9; ++k) gw.w[k] = weights9[k];
   dim3 grid((unsigned)((d.s1 + TY - 1) / TY), (unsigned)d.s0, (unsigned)planes);
-  hipStream_t st = (hipStream_t)stream;
 #define GXY(PRE, POST) hipLaunchKernelGGL((k_gauss_xy<PRE, POST>), grid, dim3(kBlock), lds, st, in, out, aux, d, (int)C, gw, scale, TY, in_hi, (int)planes_lo)
   switch (pre * 3 + post) {
     case 0: GXY(0, 0); break;
@@ -2067,6 +2229,46 @@ int advchain_gauss_xy(const float* in, float* out, const float* aux, int64_t pla
 #undef GXY
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
+}
+
+extern "C" {
+
+int advchain_gauss_xy(const float* in, float* out, const float* aux, int64_t planes, int64_t C, int ndim, const int64_t* dims,
+                      const float* weights9, int pre, int post, float scale, void* stream, const float* in_hi, int64_t planes_lo) {
+  return gauss_xy_launch(in, out, aux, planes, C, ndim, dims, weights9, pre, post, scale, stream, in_hi, planes_lo, kGxyAuto, 0, 0);
+}
+
+// Always the staged kernel (k_gauss_xy): the reference form of the tests and of tools/gauss_xy_bench.py.
+int advchain_gauss_xy_staged(const float* in, float* out, const float* aux, int64_t planes, int64_t C, int ndim,
+                             const int64_t* dims, const float* weights9, int pre, int post, float scale, void* stream,
+                             const float* in_hi, int64_t planes_lo) {
+  return gauss_xy_launch(in, out, aux, planes, C, ndim, dims, weights9, pre, post, scale, stream, in_hi, planes_lo, kGxyStaged, 0, 0);
+}
+
+// The lane form with a given tile (for the tests and the bench): ADVCHAIN_ERR_UNSUPPORTED for a shape it does not take.
+int advchain_gauss_xy_lanes(const float* in, float* out, const float* aux, int64_t planes, int64_t C, int ndim,
+                            const int64_t* dims, const float* weights9, int pre, int post, float scale, void* stream,
+                            const float* in_hi, int64_t planes_lo, int ty, int nt) {
+  return gauss_xy_launch(in, out, aux, planes, C, ndim, dims, weights9, pre, post, scale, stream, in_hi, planes_lo, kGxyLanes, ty, nt);
+}
+
+// Host-only: what advchain_gauss_xy does with a launch (pointer alignment aside).  form: 0 -- not taken (the per-axis passes),
+// 1 -- the staged kernel, 2 -- the lane form; ty: rows per workgroup (after the clamp to short planes); nt: threads per
+// workgroup.  Returns 0, or -1 for bad arguments.
+int advchain_gauss_xy_plan(int ndim, const int64_t* dims, int64_t planes, int* form, int* ty, int* nt) {
+  if (!form || !ty || !nt || !fdims_ok(ndim, dims) || planes < 0) return -1;
+  *form = 0; *ty = 0; *nt = 0;
+  if (!advchain_gauss_xy_takes(ndim, dims, planes)) return 0;
+  const Dims d = fmake_dims(ndim, dims);
+  int t = 0, n = 0;
+  if (gauss_xy_lane_rule(d, planes, t, n)) {
+    *form = 2; *ty = gauss_xy_clamp_ty(t, d); *nt = n;
+    return 0;
+  }
+  int TY = 32;
+  while (TY > 8 && (size_t)(TY + 8) * (2 * d.s2 + 8) * 4 > 53248) TY >>= 1;
+  *form = 1; *ty = gauss_xy_clamp_ty(TY, d); *nt = kBlock;
+  return 0;
 }
 
 // All axes of a small plane in one launch (planes of at most 4096 voxels); pre = 0 | 1, no epilogue.

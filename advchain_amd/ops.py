@@ -197,6 +197,8 @@ WINDOW_STAGED = True  # deterministic mode, 2D: the window scatter stages its wi
                       # tools compare the two forms in one process
 WINDOW_STAGED_CHANNELS = (1, 2, 4)   # the channel counts that take the staged form (measured: profiles/r14/window_staged)
 BIAS_REDUCED = True   # the bias backward reduces its rows along x itself (advchain_bias_field_bwd_reduced); False: the two launches
+GAUSS_XY_LANES = True  # raw_gauss calls advchain_gauss_xy (the lane form for rows of 256 voxels); False: advchain_gauss_xy_staged,
+                      # the same bits.  Read at every call (the composite entries of demons_compose.cpp always call the former)
 
 # advchain_last_bwd_route (include/advchain_hip.h: ADVCHAIN_ROUTE_*)
 BWD_ROUTES = ("none", "general", "rows", "gather", "march", "window_float", "window_int64", "window_staged", "tiled")
@@ -526,7 +528,8 @@ def raw_gauss(x, C, pre=0, post=0, scale=1.0, aux=None, weights=None):
     cur = x
     # x and y in one launch where the shape allows (advchain_gauss_xy); post belongs to the last axis
     out = torch.empty(shape, device=x.device, dtype=torch.float32)
-    rc = lib.advchain_gauss_xy(_ptr(x), _ptr(out), _ptr(aux) if (post == 2 and nd == 2) else None, planes, C, nd, dims, w9,
+    gauss_xy = lib.advchain_gauss_xy if GAUSS_XY_LANES else lib.advchain_gauss_xy_staged
+    rc = gauss_xy(_ptr(x),_ptr(out), _ptr(aux) if (post == 2 and nd == 2) else None, planes, C, nd, dims, w9,
                                pre, post if nd == 2 else 0, float(scale) if pre == 1 else 1.0, _stream(), _ptr(x_hi),
                                x.shape[0] * x.shape[1])
     if rc == 0:

@@ -455,6 +455,22 @@ int advchain_gauss_axis_generic(const float* in, float* out, int64_t planes, int
 int advchain_gauss_xy(const float* in, float* out, const float* aux, int64_t planes, int64_t C, int ndim, const int64_t* dims,
                       const float* weights9, int pre, int post, float scale, void* stream, const float* in_hi,
                       int64_t planes_lo);
+/* advchain_gauss_xy has two kernels with the same results bit for bit.  The staged form (x pass LDS -> LDS) takes every shape
+ * above.  The lane form takes rows that never straddle a wave (rows of 8, 16, 32, 64, 128 or 256 voxels): the x taps come from
+ * the neighbouring lanes, half the LDS, one barrier; advchain_gauss_xy runs it where it was measured to win, rows of 256 voxels
+ * (32 rows and 512 threads a workgroup), and the staged form everywhere else.
+ * advchain_gauss_xy_staged: always the staged form (the reference of the tests).
+ * advchain_gauss_xy_lanes: the lane form with ty rows and nt threads a workgroup, (ty, nt) one of (16,256), (16,512), (32,256),
+ * (32,512), (64,1024); -2 for a shape the lane form does not take.
+ * advchain_gauss_xy_plan (host-only): what advchain_gauss_xy does with a launch, pointer alignment aside -- *form 0: not taken,
+ * 1: staged, 2: lanes; *ty rows and *nt threads a workgroup.  Returns 0, -1 for bad arguments.                             */
+int advchain_gauss_xy_staged(const float* in, float* out, const float* aux, int64_t planes, int64_t C, int ndim,
+                             const int64_t* dims, const float* weights9, int pre, int post, float scale, void* stream,
+                             const float* in_hi, int64_t planes_lo);
+int advchain_gauss_xy_lanes(const float* in, float* out, const float* aux, int64_t planes, int64_t C, int ndim,
+                            const int64_t* dims, const float* weights9, int pre, int post, float scale, void* stream,
+                            const float* in_hi, int64_t planes_lo, int ty, int nt);
+int advchain_gauss_xy_plan(int ndim, const int64_t* dims, int64_t planes, int* form, int* ty, int* nt);
 /* all axes of the same Gaussian in ONE launch for small planes (<= 4096 voxels: the low-resolution velocity grids,
  * adv_morph.py:462-463); pre = 0 | 1 (x * scale), no epilogue; same arithmetic as the per-axis calls.              */
 int advchain_gauss_small(const float* in, float* out, int64_t planes, int ndim, const int64_t* dims,

@@ -185,7 +185,14 @@ def main():
         add("expo_chain fwd x8, fused levels", lambda: chain_fwd(hints, True), (8 * n + 4) * d * NB * V)
         add("expo_chain bwd x8, separate launches", chain_bwd_steps, 12 * n * d * NB * V)
         add("expo_chain bwd x8, fused tail %s" % halos, chain_bwd, 12 * n * d * NB * V)
-    add("gauss %d passes (d ch, pre2/post1)" % d, lambda: ops.raw_gauss(q, d, pre=2, post=1), 8 * d * NV * d)
+    # one read and one write of the field per LAUNCH: x and y share one where advchain_gauss_xy takes the shape
+    from advchain_amd import _lib
+    form = ctypes.c_int(0)
+    _lib.check(_lib.load().advchain_gauss_xy_plan(d, _lib.dims_array(dims), N * d, ctypes.byref(form), ctypes.byref(ctypes.c_int(0)),
+                                          ctypes.byref(ctypes.c_int(0))), "gauss_xy_plan")
+    launches = d - 1 if form.value else d
+    add("gauss %d axes in %d launches, %d planes (d ch, pre2/post1)" % (d, launches, N * d), lambda: ops.raw_gauss(q, d, pre=2, post=1),
+        8 * d * NV * launches)
     add("affine_warp fwd C=1", lambda: ops.affine_warp(x1, theta), 8 * NV)
     add("affine_warp fwd C=4", lambda: ops.affine_warp(x4, theta), 32 * NV)
     xa, ta = x4.clone().requires_grad_(True), theta.clone().requires_grad_(True)
