@@ -5,12 +5,12 @@ raised.  The product path never routes through PyTorch reference ops or the CPU 
 """
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libadvchain_hip.so")
 
-_P, _I, _L, _F = c_void_p, c_int, c_int64, c_float
+_P, _I, _L, _F, _D = c_void_p, c_int, c_int64, c_float, c_double
 
 # name -> (restype, argtypes).  Must list every symbol of include/advchain_hip.h.
 PROTOTYPES = {
@@ -106,6 +106,8 @@ PROTOTYPES = {
     "advchain_edt": (_I, [_P, _I, _P, _I, _P, _L, _I, _P, _P]),
     "advchain_signed_maps_workspace": (_L, [_L, _L, _I, _P]),
     "advchain_signed_maps": (_I, [_P, _P, _P, _P, _L, _L, _I, _P, _P]),
+    "advchain_surface_metrics_workspace": (_L, [_L, _L, _I, _P]),
+    "advchain_surface_metrics": (_I, [_P, _P, _P, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _P]),
     "advchain_boundary_workspace": (_L, [_L, _L, _I, _P]),
     "advchain_boundary_fwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _P]),
     "advchain_boundary_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _P]),

@@ -1,0 +1,99 @@
+"""Validation metrics of label maps on the device (not in the reference; csrc/seg_surface.hip on the distance fields of csrc/edt.hip):
+``surface_distance_metrics`` / ``hausdorff_distance`` / ``average_surface_distance``.
+
+Definitions.  pred and target are int64 label maps (N, dims), dims = (H, W) or (D, H, W), K = num_classes.  For entry n and class
+k: A = {v : pred[n,v] == k} and B = {v : target[n,v] == k}.  A label outside [0, K), -100 included, belongs to no class (the rule
+of signed_distance_maps).  Labels are only compared with class indices; they are never used as an address.
+
+Border.  The border dS of a set S is the voxels of S that have a face neighbour (4 in 2D, 6 in 3D) outside S.  A position outside
+the image counts as outside S.  This is S ^ scipy.ndimage.binary_erosion(S) with scipy's defaults, i.e. MONAI's get_mask_edges.
+A voxel has one label per map, so "border of its own class" is one predicate per voxel and map: v is a border voxel of class
+pred[v] iff some face neighbour is outside the image or carries another label.
+
+Directed distances.  d(a, dB) = min over b in dB of |S (a - b)|, with S = diag(sampling) in axis order (unit spacing when sampling
+is None).  Direction 0 is the multiset {d(a, dB) : a in dA}, of size m0 = |dA|; direction 1 is {d(b, dA) : b in dB}, of size
+m1 = |dB|.
+
+Per direction: max, mean, percentile.  Let x_(0) <= ... <= x_(m-1) be the sorted distances.  For the percentile q in [0, 100]:
+h = (m - 1) * (q / 100) in float64, j = floor(h), g = h - j, and P_q = x_(j) + g * (x_(min(j+1, m-1)) - x_(j)), evaluated in
+float64.  This is numpy.percentile's default "linear" rule.
+
+Symmetric values.  hausdorff = max(max0, max1).  hausdorff_percentile = max(P_q of direction 0, P_q of direction 1): MONAI's
+definition, not the percentile of the pooled distances.  assd = (sum0 + sum1) / (m0 + m1).
+
+Empty borders.  If both dA and dB are empty (the class is in neither map of the entry), every distance of (n, k) is NaN.  If exactly
+one is empty, every distance of (n, k) is +inf.  The counts say which case it is.
+
+Overlap, from the same pass over the labels: the int64 counts |A|, |B|, |A n B|, and dice = 2 |A n B| / (|A| + |B|), NaN when both
+are empty.
+
+With unit spacing the squared distances are exact int32, roots, interpolation and means are taken in float64 and rounded to fp32
+once; every value is the same bits on every run, nothing is read back to the host, and the call can be captured in a graph.  There
+is no gradient: the inputs are detached."""
+import math
+
+import torch
+
+from .. import ops
+from ..ops import SurfaceMetrics  # noqa: F401
+from .loss import _check_num_classes, _check_sampling, _require_gpu
+
+
+def _check_maps(name, pred, target, num_classes, sampling):
+    for t, what in ((pred, "pred"), (target, "target")):
+        if not isinstance(t, torch.Tensor) or t.dim() not in (3, 4):
+            raise ValueError("%s expects 3-D (N,H,W) or 4-D (N,D,H,W) labels as %s" % (name, what))
+    if pred.shape != target.shape:
+        raise ValueError("%s: pred %s and target %s differ in shape" % (name, tuple(pred.shape), tuple(target.shape)))
+    if pred.numel() == 0:
+        raise ValueError("%s: empty label maps %s" % (name, tuple(pred.shape)))
+    _check_num_classes(name, num_classes)
+    return _check_sampling(name, sampling, pred.dim() - 1)
+
+
+def _check_percentile(name, q):
+    if isinstance(q, bool) or not isinstance(q, (int, float)) or not math.isfinite(q) or q < 0 or q > 100:
+        raise ValueError("%s: percentile must be a finite number in [0, 100], got %r" % (name, q))
+    return float(q)
+
+
+def surface_distance_metrics(pred, target, num_classes, sampling=None, percentile=95.0):
+    """Surface distance metrics of every class of a pair of label maps in one call (definitions: the module's docstring).
+    Returns SurfaceMetrics, a namedtuple of device tensors:
+
+        hausdorff             (N,K)      fp32   symmetric maximum
+        hausdorff_percentile  (N,K)      fp32   symmetric percentile
+        assd                  (N,K)      fp32   average symmetric surface distance
+        directed              (N,K,2,3)  fp32   direction x (max, percentile, mean)
+        surface_voxels        (N,K,2)    int64  m0, m1
+        max_squared           (N,K,2)    fp64   largest squared distance per direction; an exact integer with unit spacing;
+                                                NaN / inf as the distances
+        overlap               (N,K,3)    int64  |A|, |B|, |A n B|
+        dice                  (N,K)      fp32   Dice overlap
+
+    sampling: None or one positive finite number per spatial axis; percentile: a number in [0, 100]."""
+    sampling = _check_maps("surface_distance_metrics", pred, target, num_classes, sampling)
+    percentile = _check_percentile("surface_distance_metrics", percentile)
+    _require_gpu(pred, "pred")
+    _require_gpu(target, "target")
+    return ops.surface_distance_metrics(pred, target, num_classes, sampling=sampling, percentile=percentile)
+
+
+def hausdorff_distance(pred, target, num_classes, sampling=None, percentile=None):
+    """(N,K) fp32: `hausdorff` of :func:`surface_distance_metrics`, or `hausdorff_percentile` when a percentile is given."""
+    sampling = _check_maps("hausdorff_distance", pred, target, num_classes, sampling)
+    q = 95.0 if percentile is None else _check_percentile("hausdorff_distance", percentile)
+    _require_gpu(pred, "pred")
+    _require_gpu(target, "target")
+    m = ops.surface_distance_metrics(pred, target, num_classes, sampling=sampling, percentile=q)
+    return m.hausdorff if percentile is None else m.hausdorff_percentile
+
+
+def average_surface_distance(pred, target, num_classes, sampling=None, symmetric=True):
+    """(N,K) fp32: `assd` of :func:`surface_distance_metrics`, or with symmetric=False the mean of direction 0 (from pred's
+    border to target's)."""
+    sampling = _check_maps("average_surface_distance", pred, target, num_classes, sampling)
+    _require_gpu(pred, "pred")
+    _require_gpu(target, "target")
+    m = ops.surface_distance_metrics(pred, target, num_classes, sampling=sampling)
+    return m.assd if symmetric else m.directed[:, :, 0, 2]

@@ -2,6 +2,7 @@
 //
 //   advchain_edt                 <- common.loss.distance_transform_edt
 //   advchain_signed_maps         <- common.loss.signed_distance_maps (and boundary_loss with a label target)
+//   edt_label_fields             <- csrc/seg_surface.hip (csrc/edt_fields.h): field 0 of every class through the passes, not finished
 //
 // A field holds, per voxel, the squared distance to the nearest SEED of its line so far, or the sentinel "no seed yet".  It
 // is separable: one pass per axis, each in place.
@@ -27,8 +28,10 @@
 // host read-back: every word that is read was written by a kernel of the same call.  Labels are only COMPARED with class
 // indices.
 #include <math.h>
+#include <stdio.h>
 
 #include "common.h"
+#include "edt_fields.h"
 
 namespace advchain {
 namespace {
@@ -282,7 +285,62 @@ int edt_run(const void* src, int kind, T* g, float* out, int64_t N, int K, const
   return edt_axis<T, LAST>(g, labels, out, Q, K, 1, D, H * W, s[0], squared, st);
 }
 
+// the passes without a finish: field 0 (seeds are the members) of every class, left as squared distances with the sentinel
+template <typename T>
+int edt_fields_run(const int64_t* labels, T* g, int64_t N, int K, const EdtShape& sh, const float (&s)[3], hipStream_t st) {
+  const int64_t D = sh.d[0], H = sh.d[1], W = sh.d[2], R = D * H, Q = N * K;
+  if (N * R > 0x7fffffff) {
+    advchain_set_error_("edt: too many rows for one launch");
+    return ADVCHAIN_ERR_UNSUPPORTED;
+  }
+  const int chunks = (int)((W + 63) / 64);
+  const int group = kEdtBallots / chunks;
+  for (int k0 = 0; k0 < K; k0 += group) {
+    hipLaunchKernelGGL(k_edt_rows<T>, dim3((unsigned)(N * R)), dim3(kBlock), 0, st, (const void*)labels, (int)SRC_LABELS, g, K, 1, 0,
+                       (int)W, R, k0, K - k0 < group ? K - k0 : group, chunks, s[2]);
+    ADVCHAIN_LAUNCH_CHECK();
+  }
+  if (sh.nd == 2) return edt_axis<T, AXIS_PLAIN>(g, nullptr, nullptr, Q, 1, 1, H, W, s[1], 0, st);
+  const int rc = edt_axis<T, AXIS_PLAIN>(g, nullptr, nullptr, Q, 1, D, H, W, s[1], 0, st);
+  if (rc != ADVCHAIN_OK) return rc;
+  return edt_axis<T, AXIS_PLAIN>(g, nullptr, nullptr, Q, 1, 1, D, H * W, s[0], 0, st);
+}
+
 }  // namespace
+
+// ---- csrc/edt_fields.h -------------------------------------------------------------------------------------------------------
+int64_t edt_label_fields_words(int64_t entries, int64_t K, int ndim, const int64_t* dims) {
+  EdtShape sh;
+  if (entries < 1 || K < 1 || K > 65535 || edt_shape(ndim, dims, 2, &sh) != ADVCHAIN_OK) return -1;
+  if (entries > ((int64_t)1 << 40) / K) return -1;
+  return edt_words(entries * K, 1, sh);
+}
+
+int edt_label_fields(const int64_t* labels, const float* sampling, void* fields, int64_t entries, int64_t K, int ndim,
+                     const int64_t* dims, const char* what, hipStream_t st) {
+  char msg[256];
+  EdtShape sh;
+  const int rc = edt_shape(ndim, dims, 2, &sh);
+  if (rc == ADVCHAIN_ERR_ARG || entries < 1 || K < 1 || K > 65535 || !labels || !fields) {
+    snprintf(msg, sizeof(msg), "%s: bad pointer, N, K, ndim or dims", what);
+    advchain_set_error_(msg);
+    return ADVCHAIN_ERR_ARG;
+  }
+  if (rc != ADVCHAIN_OK || edt_label_fields_words(entries, K, ndim, dims) < 0) {
+    snprintf(msg, sizeof(msg), "%s: shape too large for the distance fields (an axis or the squared diagonal)", what);
+    advchain_set_error_(msg);
+    return ADVCHAIN_ERR_UNSUPPORTED;
+  }
+  float s[3];
+  if (!edt_spacing(sampling, sh, s)) {
+    snprintf(msg, sizeof(msg), "%s: sampling must be positive and finite (and the physical diagonal below 1e14)", what);
+    advchain_set_error_(msg);
+    return ADVCHAIN_ERR_ARG;
+  }
+  if (sampling) return edt_fields_run<float>(labels, (float*)fields, entries, (int)K, sh, s, st);
+  return edt_fields_run<int>(labels, (int*)fields, entries, (int)K, sh, s, st);
+}
+
 }  // namespace advchain
 
 using namespace advchain;

@@ -2207,6 +2207,42 @@ def signed_distance_maps(labels, num_classes, sampling=None):
     return out
 
 
+SurfaceMetrics = collections.namedtuple("SurfaceMetrics", ["hausdorff", "hausdorff_percentile", "assd", "directed", "surface_voxels",
+                                                          "max_squared", "overlap", "dice"])
+
+
+@_on_tensor_device
+def surface_distance_metrics(pred, target, num_classes, sampling=None, percentile=95.0):
+    """(N,dims) int64 label maps -> SurfaceMetrics of (N,K,...) device tensors: Hausdorff distance, its percentile, the average
+    symmetric surface distance, the directed values, counts and Dice of every class (include/advchain_hip.h:
+    advchain_surface_metrics).  No gradient."""
+    pred = _dev_labels(pred.detach() if isinstance(pred, torch.Tensor) else pred, "pred")
+    target = _dev_labels(target.detach() if isinstance(target, torch.Tensor) else target, "target")
+    _same_device(pred, target)
+    if pred.shape != target.shape:
+        raise ValueError("surface_distance_metrics: pred %s and target %s differ in shape" % (tuple(pred.shape), tuple(target.shape)))
+    N, K = pred.shape[0], int(num_classes)
+    sp = tuple(pred.shape[1:])
+    lib = _lib.load()
+    dims = _lib.dims_array(sp)
+    n = lib.advchain_surface_metrics_workspace(N, K, len(sp), dims)
+    if n < 0:
+        raise NotImplementedError("surface_distance_metrics: N=%d, K=%d, spatial shape %s is too large for the distance fields (an "
+                                  "axis above 32767 -- 8192 for the leading axes -- or a squared diagonal of 2^30 or more)" % (N, K, sp))
+    dev = pred.device
+    ws = torch.empty(int(n), device=dev, dtype=torch.float32)
+    f32 = [torch.empty(s, device=dev, dtype=torch.float32) for s in ((N, K), (N, K), (N, K), (N, K, 2, 3))]
+    voxels = torch.empty((N, K, 2), device=dev, dtype=torch.int64)
+    max_squared = torch.empty((N, K, 2), device=dev, dtype=torch.float64)
+    overlap = torch.empty((N, K, 3), device=dev, dtype=torch.int64)
+    dice = torch.empty((N, K), device=dev, dtype=torch.float32)
+    _edt_check(lib.advchain_surface_metrics(_ptr(pred), _ptr(target), _sampling_array(sampling, len(sp)), float(percentile),
+                                            _ptr(f32[0]), _ptr(f32[1]), _ptr(f32[2]), _ptr(f32[3]), _ptr(voxels), _ptr(max_squared),
+                                            _ptr(overlap), _ptr(dice), _ptr(ws), N, K, len(sp), dims, _stream()),
+               "surface_metrics", sp)
+    return SurfaceMetrics(f32[0], f32[1], f32[2], f32[3], voxels, max_squared, overlap, dice)
+
+
 class _Boundary(torch.autograd.Function):
     """1/(N V) sum omega_k softmax(x)_k maps_k over the counted voxels and classes (include/advchain_hip.h:
     advchain_boundary_fwd).  Differentiable w.r.t. the logits; the maps are a constant.  Two launches forward, one backward."""

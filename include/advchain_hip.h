@@ -806,6 +806,38 @@ int64_t advchain_signed_maps_workspace(int64_t N, int64_t K, int ndim, const int
 int advchain_signed_maps(const int64_t* labels, const float* sampling, float* out, float* workspace, int64_t N, int64_t K,
                          int ndim, const int64_t* dims, void* stream);
 
+/* ---- surface distance metrics of a pair of label maps, 2D and 3D (seg_surface.hip) -------------------------------------------
+ * Not in the reference.  pred, target (N, dims) int64; for entry n and class k, A = {v: pred[n,v] == k}, B = {v: target[n,v] ==
+ * k}; a label outside [0, K), -100 included, belongs to no class, and labels are only compared with class indices.  The border
+ * dS of a set is its voxels with a face neighbour (4 in 2D, 6 in 3D) outside it, a position outside the image counting as
+ * outside (S ^ binary_erosion(S)).  Direction 0 is the multiset {d(a, dB): a in dA} of size m0, direction 1 {d(b, dA): b in dB}
+ * of size m1, d the Euclidean distance under `sampling` (as for the transform above: NULL, or ndim host floats).  Per direction
+ * the maximum, the mean, and the percentile q in [0, 100] by numpy's linear rule: h = (m - 1) (q / 100), j = floor(h),
+ * P = x_(j) + (h - j) (x_(min(j+1, m-1)) - x_(j)) over the sorted distances, in fp64.  Outputs (all written, device memory):
+ *   hausdorff (N,K) fp32       max of the two maxima
+ *   hausdorff_pct (N,K) fp32   max of the two percentiles (not the percentile of the pooled distances)
+ *   assd (N,K) fp32            (sum0 + sum1) / (m0 + m1)
+ *   directed (N,K,2,3) fp32    direction x (maximum, percentile, mean)
+ *   surface_voxels (N,K,2) int64   m0, m1
+ *   max_squared (N,K,2) fp64   the largest squared distance per direction, an exact integer with unit spacing
+ *   overlap (N,K,3) int64      |A|, |B|, |A n B|
+ *   dice (N,K) fp32            2 |A n B| / (|A| + |B|), NaN when both are empty
+ * Both borders empty: every distance of (n, k) is NaN; exactly one empty: +inf.  With unit spacing the squared distances are
+ * int32 and exact, roots, interpolation and means are taken in fp64 and rounded to fp32 once.  One pass writes the two edge
+ * label maps (int64: the label at a border voxel, -1 elsewhere) and the counts; the passes of the transform give the squared
+ * distance of every voxel to the nearest border voxel of each class of each map; a border voxel then contributes one field word,
+ * and a four-digit radix select (LDS histograms, 64-bit integer atomics) finds the order statistics.  Sums are fp64 partials
+ * per workgroup added in a fixed order.  Integer atomics only, no memset, no host read-back: bitwise reproducible, capturable
+ * on one stream.  ADVCHAIN_ERR_UNSUPPORTED for the shapes advchain_signed_maps refuses, and for N above 65535.
+ * `workspace` (16-byte aligned, no clearing needed): advchain_surface_metrics_workspace 4-byte words, host-only query, -1 where
+ * the shape is refused; with V voxels per entry and c = min(ceil(V / 4096), 256) it is
+ *   2 N K V (fields) + 4 N V (edge maps) + 2 N K (512 + 2 + 2 c + 4) (histograms, ranks, partial sums, segment words).        */
+int64_t advchain_surface_metrics_workspace(int64_t N, int64_t K, int ndim, const int64_t* dims); /* 4-byte words */
+int advchain_surface_metrics(const int64_t* pred, const int64_t* target, const float* sampling, double q, float* hausdorff,
+                             float* hausdorff_pct, float* assd, float* directed, int64_t* surface_voxels, double* max_squared,
+                             int64_t* overlap, float* dice, void* workspace, int64_t N, int64_t K, int ndim,
+                             const int64_t* dims, void* stream);
+
 /* ---- boundary (surface) loss, 2D and 3D (seg_boundary.hip) -----------------------------------------------------------------
  * Not in the reference (Kervadec et al.).  logits (N,K,dims) fp32 (logits_bf16 = 0) or bf16 (1), maps (N,K,dims) fp32 signed
  * distance maps (a constant), p = softmax over K inside the kernel:
