@@ -282,6 +282,24 @@ extern "C" void advchain_set_route_(int route);
     }                                                    \
   } while (0)
 
+// (ndim, int64[ndim]) of the C ABI -> Dims.  dims_ok: 2 or 3 axes of 1 .. 2^24 each and at least `min_voxels` voxels in all (a
+// null pointer is a bad shape); make_dims only after dims_ok.
+static inline bool dims_ok(int ndim, const int64_t* s, int64_t min_voxels = 1) {
+  if (!s || (ndim != 2 && ndim != 3)) return false;
+  int64_t v = 1;
+  for (int i = 0; i < ndim; ++i) {
+    if (s[i] < 1 || s[i] > (1 << 24)) return false;
+    v *= s[i];
+  }
+  return v >= min_voxels;
+}
+static inline advchain::Dims make_dims(int ndim, const int64_t* s) {
+  advchain::Dims d;
+  if (ndim == 3) { d.s0 = (int)s[0]; d.s1 = (int)s[1]; d.s2 = (int)s[2]; }
+  else { d.s0 = 1; d.s1 = (int)s[0]; d.s2 = (int)s[1]; }
+  return d;
+}
+
 static inline int advchain_blocks(int64_t n, int per_block) { return (int)((n + per_block - 1) / per_block); }
 
 // Zero-fill as a kernel of this library rather than hipMemsetAsync: under stream capture a memset becomes a

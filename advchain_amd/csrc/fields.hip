@@ -1639,19 +1639,6 @@ struct advchain_update_desc {
   float step;
 };
 
-static inline bool fdims_ok(int ndim, const int64_t* s) {
-  if (ndim != 2 && ndim != 3) return false;
-  for (int i = 0; i < ndim; ++i)
-    if (s[i] < 1 || s[i] > (1 << 24)) return false;
-  return true;
-}
-static inline Dims fmake_dims(int ndim, const int64_t* s) {
-  Dims d;
-  if (ndim == 3) { d.s0 = (int)s[0]; d.s1 = (int)s[1]; d.s2 = (int)s[2]; }
-  else { d.s0 = 1; d.s1 = (int)s[0]; d.s2 = (int)s[1]; }
-  return d;
-}
-
 // Band-table buffers (device), built by the host (advchain_amd/bands.py):
 //   itab: for each axis a (3 axes; 2D passes a trivial leading axis):  start[S_a] | lo[g_a] | hi[g_a]
 //   ftab: for each axis a: w[S_a * B_a]
@@ -2027,10 +2014,10 @@ __global__ void __launch_bounds__(kBlock) k_gauss_axis_generic(const float* __re
 int advchain_gauss_axis_generic(const float* in, float* out, int64_t planes, int ndim, const int64_t* dims, int axis,
                                 const float* weights, int ntaps, float scale, void* stream) {
   ADVCHAIN_CHECK_ARG(in && out && in != out && weights, "gauss_axis_generic: null/aliased pointer");
-  ADVCHAIN_CHECK_ARG(fdims_ok(ndim, dims), "gauss_axis_generic: bad dims");
+  ADVCHAIN_CHECK_ARG(dims_ok(ndim, dims), "gauss_axis_generic: bad dims");
   ADVCHAIN_CHECK_ARG(axis >= 0 && axis < 3, "gauss_axis_generic: bad axis");
   ADVCHAIN_CHECK_ARG(ntaps >= 1 && ntaps <= kGenericMaxTaps && (ntaps & 1) == 1, "gauss_axis_generic: the window must have 1..129 taps, odd");
-  const Dims d = fmake_dims(ndim, dims);
+  const Dims d = make_dims(ndim, dims);
   ADVCHAIN_CHECK_ARG(d.voxels() < (1ll << 31), "gauss_axis_generic: volume too large");
   const int64_t total = planes * d.voxels();
   if (total == 0) return ADVCHAIN_OK;
@@ -2047,10 +2034,10 @@ int advchain_gauss_axis(const float* in, float* out, const float* aux, int64_t p
                         const int64_t* dims, int axis, const float* weights9, int pre, int post, float scale,
                         void* stream) {
   ADVCHAIN_CHECK_ARG(in && out && in != out && weights9, "gauss_axis: null/aliased pointer");
-  ADVCHAIN_CHECK_ARG(fdims_ok(ndim, dims), "gauss_axis: bad dims");
+  ADVCHAIN_CHECK_ARG(dims_ok(ndim, dims), "gauss_axis: bad dims");
   ADVCHAIN_CHECK_ARG(axis >= 0 && axis < 3 && C >= 1 && C <= 3, "gauss_axis: bad axis/C");
   ADVCHAIN_CHECK_ARG(pre >= 0 && pre <= 2 && post >= 0 && post <= 2 && (post != 2 || aux), "gauss_axis: bad pre/post");
-  const Dims d = fmake_dims(ndim, dims);
+  const Dims d = make_dims(ndim, dims);
   const int64_t total = planes * d.voxels();
   ADVCHAIN_CHECK_ARG(d.voxels() < (1ll << 31), "gauss_axis: volume too large");
   if (total == 0) return ADVCHAIN_OK;
@@ -2116,8 +2103,8 @@ int advchain_gauss_axis(const float* in, float* out, const float* aux, int64_t p
 // The shapes advchain_gauss_xy takes (pointer alignment aside): for callers that must know before they enqueue anything
 // (the composite entries of demons_compose.cpp).
 bool advchain_gauss_xy_takes(int ndim, const int64_t* dims, int64_t planes) {
-  if (!fdims_ok(ndim, dims)) return false;
-  const Dims d = fmake_dims(ndim, dims);
+  if (!dims_ok(ndim, dims)) return false;
+  const Dims d = make_dims(ndim, dims);
   if ((d.s2 & 3) != 0 || d.s2 < 8 || d.s2 > 512 || d.s1 < 8 || planes > 65535 || d.s0 > 65535) return false;
   int TY = 32;
   while (TY > 8 && (size_t)(TY + 8) * (2 * d.s2 + 8) * 4 > 53248) TY >>= 1;
@@ -2161,10 +2148,10 @@ static int gauss_xy_launch(const float* in, float* out, const float* aux, int64_
                            const float* weights9, int pre, int post, float scale, void* stream, const float* in_hi, int64_t planes_lo,
                            int want, int ty, int nt) {
   ADVCHAIN_CHECK_ARG(in && out && in != out && weights9, "gauss_xy: null/aliased pointer");
-  ADVCHAIN_CHECK_ARG(fdims_ok(ndim, dims), "gauss_xy: bad dims");
+  ADVCHAIN_CHECK_ARG(dims_ok(ndim, dims), "gauss_xy: bad dims");
   ADVCHAIN_CHECK_ARG(C >= 1 && C <= 3 && pre >= 0 && pre <= 2 && post >= 0 && post <= 2 && (post != 2 || aux), "gauss_xy: bad C/pre/post");
   ADVCHAIN_CHECK_ARG(post == 0 || ndim == 2, "gauss_xy: post belongs to the last axis");
-  const Dims d = fmake_dims(ndim, dims);
+  const Dims d = make_dims(ndim, dims);
   if ((d.s2 & 3) != 0 || d.s2 < 8 || d.s2 > 512 || d.s1 < 8 || planes > 65535 || d.s0 > 65535 ||
       ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(aux) |
         reinterpret_cast<uintptr_t>(in_hi)) & 15) != 0)
@@ -2256,10 +2243,10 @@ int advchain_gauss_xy_lanes(const float* in, float* out, const float* aux, int64
 // 1 -- the staged kernel, 2 -- the lane form; ty: rows per workgroup (after the clamp to short planes); nt: threads per
 // workgroup.  Returns 0, or -1 for bad arguments.
 int advchain_gauss_xy_plan(int ndim, const int64_t* dims, int64_t planes, int* form, int* ty, int* nt) {
-  if (!form || !ty || !nt || !fdims_ok(ndim, dims) || planes < 0) return -1;
+  if (!form || !ty || !nt || !dims_ok(ndim, dims) || planes < 0) return -1;
   *form = 0; *ty = 0; *nt = 0;
   if (!advchain_gauss_xy_takes(ndim, dims, planes)) return 0;
-  const Dims d = fmake_dims(ndim, dims);
+  const Dims d = make_dims(ndim, dims);
   int t = 0, n = 0;
   if (gauss_xy_lane_rule(d, planes, t, n)) {
     *form = 2; *ty = gauss_xy_clamp_ty(t, d); *nt = n;
@@ -2275,9 +2262,9 @@ int advchain_gauss_xy_plan(int ndim, const int64_t* dims, int64_t planes, int* f
 static int gauss_small_launch(const float* in, float* out, int64_t planes, int ndim, const int64_t* dims,
                               const float* weights9, int pre, float scale, int mirror, void* stream) {
   ADVCHAIN_CHECK_ARG(in && out && in != out && weights9, "gauss_small: null/aliased pointer");
-  ADVCHAIN_CHECK_ARG(fdims_ok(ndim, dims), "gauss_small: bad dims");
+  ADVCHAIN_CHECK_ARG(dims_ok(ndim, dims), "gauss_small: bad dims");
   ADVCHAIN_CHECK_ARG(pre == 0 || pre == 1, "gauss_small: pre must be 0 or 1");
-  const Dims d = fmake_dims(ndim, dims);
+  const Dims d = make_dims(ndim, dims);
   ADVCHAIN_CHECK_ARG(d.voxels() <= kGaussSmallMax, "gauss_small: plane larger than 4096 voxels");
   ADVCHAIN_CHECK_ARG(planes >= 0 && planes < (1ll << 30), "gauss_small: bad plane count");
   if (planes == 0) return ADVCHAIN_OK;

@@ -568,6 +568,7 @@ __device__ __forceinline__ float4 ld4(const Bf16* p) {
   return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
                      __uint_as_float(u.y & 0xffff0000u));
 }
+// (plane_io.h: to_bf16 keeps a NaN's payload; this one maps every NaN to 0x7fc0 -- another result, so it stays)
 __device__ __forceinline__ unsigned bf16_rne(float x) {          // round to nearest even; NaN stays NaN
   const unsigned b = __float_as_uint(x);
   return (x != x) ? 0x7fc0u : (b + 0x7fffu + ((b >> 16) & 1u)) >> 16;
@@ -1488,13 +1489,13 @@ static int consistency_fwd(const OrdCounts* oc, const float* pred, const float* 
                            float* sums, int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels,
                            int ref_is_prob, int want_edges, int want_kl, void* stream, ORD... ord) {
   ADVCHAIN_CHECK_ARG(pred && ref && P && D && sums, "consistency_fwd: null pointer");
-  ADVCHAIN_CHECK_ARG(ldims_ok(ndim, dims), "consistency_fwd: bad dims");
+  ADVCHAIN_CHECK_ARG(dims_ok(ndim, dims), "consistency_fwd: bad dims");
   ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && K >= 1 && K <= kMaxK, "consistency_fwd: bad N/K (K <= 16)");
   ADVCHAIN_CHECK_ARG(!mask || mask_channels == 1 || mask_channels == K, "consistency_fwd: mask must have 1 or K channels");
   if (oc)
     for (int r = 0; r < 4; ++r) oc->counts[r] = 0;
   if (N == 0) return ADVCHAIN_OK;
-  const Dims d = lmake_dims(ndim, dims);
+  const Dims d = make_dims(ndim, dims);
   ADVCHAIN_CHECK_ARG(d.voxels() < (1ll << 31), "consistency_fwd: volume too large");
   const int V = (int)d.voxels();
   dim3 g(advchain_blocks(V, kBlock), (unsigned)N), b(kBlock);
@@ -1548,13 +1549,13 @@ static int consistency_fused_fwd(const OrdCounts* oc, const float* pred, const f
                                  int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels, int ref_is_prob,
                                  int want_edges, int want_kl, void* stream, ORD... ord) {
   ADVCHAIN_CHECK_ARG(pred && ref && sums, "consistency_fused_fwd: null pointer");
-  ADVCHAIN_CHECK_ARG(ldims_ok(ndim, dims), "consistency_fused_fwd: bad dims");
+  ADVCHAIN_CHECK_ARG(dims_ok(ndim, dims), "consistency_fused_fwd: bad dims");
   ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && K >= 1 && K <= kMaxK, "consistency_fused_fwd: bad N/K (K <= 16)");
   // 3D: the y-marching kernel below was measured SLOWER than the three-kernel form (K = 4: 4 x 4 x 128 x 128 x 64 230 against
   // 199 us -- its z fold reads three planes per row) and is instantiated for 2D only since round 5; 3D takes
   // k_loss_fused_fwd3d_z (z-marching with the y neighbours through LDS; edges wanted, rows of at most 128 voxels)
   // or the unfused entries.
-  const Dims d = lmake_dims(ndim, dims);
+  const Dims d = make_dims(ndim, dims);
   const bool edges = want_edges && K > 1;
   const bool zmarch = ndim == 3 && z3_takes(d, edges);
   if ((ndim == 3 && !zmarch) || K < 2 || K > 4 || (mask && mask_channels != 1)) return ADVCHAIN_ERR_UNSUPPORTED;
@@ -1628,8 +1629,8 @@ int advchain_consistency_fwd(const float* pred, const float* ref, const float* m
 // aligned): the capacity `stride` of a row of the partial buffer.  Host-only.
 int64_t advchain_consistency_fwd_partials(int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels, int want_edges,
                                           int aligned16) {
-  if (!dims || !ldims_ok(ndim, dims) || N < 0 || N >= 65536 || K < 1 || K > kMaxK) return -1;
-  const Dims d = lmake_dims(ndim, dims);
+  if (!dims_ok(ndim, dims) || N < 0 || N >= 65536 || K < 1 || K > kMaxK) return -1;
+  const Dims d = make_dims(ndim, dims);
   if (d.voxels() >= (1ll << 31)) return -1;
   const int64_t V = d.voxels();
   const int64_t all = (int64_t)advchain_blocks(V, kBlock) * N;
@@ -1671,11 +1672,11 @@ int advchain_consistency_bwd(const float* P, const float* D, const float* R, con
                              int kl_is_gt, int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels,
                              void* stream) {
   ADVCHAIN_CHECK_ARG(P && D && grad_pred, "consistency_bwd: null pointer");
-  ADVCHAIN_CHECK_ARG(ldims_ok(ndim, dims), "consistency_bwd: bad dims");
+  ADVCHAIN_CHECK_ARG(dims_ok(ndim, dims), "consistency_bwd: bad dims");
   ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && K >= 1 && K <= kMaxK, "consistency_bwd: bad N/K (K <= 16)");
   ADVCHAIN_CHECK_ARG(!mask || mask_channels == 1 || mask_channels == K, "consistency_bwd: mask must have 1 or K channels");
   if (N == 0) return ADVCHAIN_OK;
-  const Dims d = lmake_dims(ndim, dims);
+  const Dims d = make_dims(ndim, dims);
   ADVCHAIN_CHECK_ARG(d.voxels() < (1ll << 31), "consistency_bwd: volume too large");
   dim3 g(advchain_blocks(d.voxels(), kBlock), (unsigned)N), b(kBlock);
   hipStream_t st = (hipStream_t)stream;
@@ -1704,8 +1705,8 @@ int advchain_consistency_fused_fwd(const float* pred, const float* ref, const fl
 // returns it (has_mask: a mask is given; aligned16: every tensor is 16-byte aligned).  Host-only.
 int64_t advchain_consistency_fused_fwd_partials(int64_t N, int64_t K, int ndim, const int64_t* dims, int has_mask, int mask_channels,
                                                 int want_edges, int aligned16) {
-  if (!dims || !ldims_ok(ndim, dims) || N < 0 || N >= 65536 || K < 1 || K > kMaxK) return -1;
-  const Dims d = lmake_dims(ndim, dims);
+  if (!dims_ok(ndim, dims) || N < 0 || N >= 65536 || K < 1 || K > kMaxK) return -1;
+  const Dims d = make_dims(ndim, dims);
   const bool edges = want_edges && K > 1;
   const bool zmarch = ndim == 3 && z3_takes(d, edges);
   if ((ndim == 3 && !zmarch) || K < 2 || K > 4 || (has_mask && mask_channels != 1)) return ADVCHAIN_ERR_UNSUPPORTED;
@@ -1746,10 +1747,10 @@ int advchain_consistency_fused_bwd(const float* pred, const float* ref, const fl
                                    int ref_is_prob, int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels,
                                    void* stream) {
   ADVCHAIN_CHECK_ARG(pred && ref && grad_pred, "consistency_fused_bwd: null pointer");
-  ADVCHAIN_CHECK_ARG(ldims_ok(ndim, dims), "consistency_fused_bwd: bad dims");
+  ADVCHAIN_CHECK_ARG(dims_ok(ndim, dims), "consistency_fused_bwd: bad dims");
   ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && K >= 1 && K <= kMaxK, "consistency_fused_bwd: bad N/K (K <= 16)");
   if (K < 2 || K > 4 || (mask && mask_channels != 1)) return ADVCHAIN_ERR_UNSUPPORTED;
-  const Dims d = lmake_dims(ndim, dims);
+  const Dims d = make_dims(ndim, dims);
   if (d.voxels() >= (1ll << 31) || !march4_ok(d, pred, ref, R, mask) || (reinterpret_cast<uintptr_t>(grad_pred) & 15) != 0)
     return ADVCHAIN_ERR_UNSUPPORTED;
   if (N == 0) return ADVCHAIN_OK;
@@ -1788,9 +1789,9 @@ int advchain_consistency_fused_bwd(const float* pred, const float* ref, const fl
 int advchain_consistency_fused_fwd_bf16(const void* pred, const void* ref, const float* mask, void* R, float* sums, int64_t N,
                                         int64_t K, int ndim, const int64_t* dims, void* stream) {
   ADVCHAIN_CHECK_ARG(pred && ref && sums, "consistency_fused_fwd_bf16: null pointer");
-  ADVCHAIN_CHECK_ARG(ldims_ok(ndim, dims), "consistency_fused_fwd_bf16: bad dims");
+  ADVCHAIN_CHECK_ARG(dims_ok(ndim, dims), "consistency_fused_fwd_bf16: bad dims");
   ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536, "consistency_fused_fwd_bf16: bad N");
-  const Dims d = lmake_dims(ndim, dims);
+  const Dims d = make_dims(ndim, dims);
   const uintptr_t al = reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(ref) | reinterpret_cast<uintptr_t>(R);
   if (ndim != 2 || K != 4 || d.s2 % 4 != 0 || d.s2 > 256 || (al & 7) != 0 || (reinterpret_cast<uintptr_t>(mask) & 15) != 0 ||
       d.voxels() >= (1ll << 31))
@@ -1807,9 +1808,9 @@ int advchain_consistency_fused_bwd_bf16(const void* pred, const void* ref, const
                                         const float* grad_scale, void* grad_pred, float c_mse, float c_a, float c_b, int64_t N,
                                         int64_t K, int ndim, const int64_t* dims, void* stream) {
   ADVCHAIN_CHECK_ARG(pred && ref && R && grad_pred, "consistency_fused_bwd_bf16: null pointer");
-  ADVCHAIN_CHECK_ARG(ldims_ok(ndim, dims), "consistency_fused_bwd_bf16: bad dims");
+  ADVCHAIN_CHECK_ARG(dims_ok(ndim, dims), "consistency_fused_bwd_bf16: bad dims");
   ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536, "consistency_fused_bwd_bf16: bad N");
-  const Dims d = lmake_dims(ndim, dims);
+  const Dims d = make_dims(ndim, dims);
   const uintptr_t al = reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(ref) | reinterpret_cast<uintptr_t>(R) |
                        reinterpret_cast<uintptr_t>(grad_pred);
   if (ndim != 2 || K != 4 || d.s2 % 4 != 0 || d.s2 > 256 || (al & 7) != 0 || (reinterpret_cast<uintptr_t>(mask) & 15) != 0 ||

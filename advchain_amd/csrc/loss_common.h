@@ -20,7 +20,7 @@ namespace advchain {
 __device__ __forceinline__ float hsm(int i) { return i == 1 ? 2.f : 1.f; }        // [1, 2, 1]
 __device__ __forceinline__ float hdf(int i) { return i == 0 ? 1.f : (i == 1 ? 0.f : -1.f); }  // [1, 0, -1]
 
-// stencil weights at tap (a0,a1,a2) in {0,1,2}^3 (a0 unused in 2D)
+// stencil weights at tap (a0,a1,a2) in {0,1,2}^3 (a0 unused in 2D); the contour loss of seg_loss.hip takes them from here too
 template <int DIM>
 __device__ __forceinline__ void stencil_w(int a0, int a1, int a2, float& wa, float& wb) {
   if (DIM == 2) {
@@ -174,19 +174,6 @@ __device__ __forceinline__ void stage_R(float (*buf)[WTile<DIM>::NH], const floa
       buf[1][e] = hv[j] >= 0 ? rb : 0.f;
     }
   }
-}
-
-static inline bool ldims_ok(int ndim, const int64_t* s) {
-  if (ndim != 2 && ndim != 3) return false;
-  for (int i = 0; i < ndim; ++i)
-    if (s[i] < 1 || s[i] > (1 << 24)) return false;
-  return true;
-}
-static inline Dims lmake_dims(int ndim, const int64_t* s) {
-  Dims d;
-  if (ndim == 3) { d.s0 = (int)s[0]; d.s1 = (int)s[1]; d.s2 = (int)s[2]; }
-  else { d.s0 = 1; d.s1 = (int)s[0]; d.s2 = (int)s[1]; }
-  return d;
 }
 
 }  // namespace advchain

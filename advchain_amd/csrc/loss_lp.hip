@@ -56,28 +56,12 @@
 #include <algorithm>
 
 #include "loss_common.h"
+#include "plane_io.h"
 
 namespace advchain {
 namespace {
 
 typedef unsigned short bf16_t;     // raw bf16 words
-
-__device__ __forceinline__ bf16_t lp_to_bf16(float x) {     // round to nearest even; NaN stays NaN
-  const unsigned u = __float_as_uint(x);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)((u >> 16) | 0x40u);
-  return (bf16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
-template <typename ST>
-__device__ __forceinline__ float ld1(const ST* __restrict__ p) {
-  if constexpr (sizeof(ST) == 4) return p[0];
-  else return __uint_as_float((unsigned)p[0] << 16);
-}
-template <typename ST>
-__device__ __forceinline__ void st1(ST* __restrict__ p, float x) {
-  if constexpr (sizeof(ST) == 4) p[0] = x;
-  else p[0] = lp_to_bf16(x);
-}
 
 // Class weights.  Each kernel ends in a parameter pack W... that is EMPTY (the lp entries: the unweighted loss, the very
 // kernel arguments and instructions it had without the pack) or ONE `const float*` (the cw entries: K device floats, w_k read
@@ -102,15 +86,10 @@ template <typename... T> struct lp_weighted<const float*, T...> { static constex
 template <typename ST, bool WIDE>
 __device__ __forceinline__ void ld4(const ST* __restrict__ p, int cnt, float (&x)[4]) {
   if constexpr (WIDE) {
-    if constexpr (sizeof(ST) == 4) {
-      const float4 a = *reinterpret_cast<const float4*>(p);
-      x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w;
-    } else {
-      const uint2 a = *reinterpret_cast<const uint2*>(p);
-      x[0] = __uint_as_float(a.x << 16); x[1] = __uint_as_float(a.x & 0xffff0000u);
-      x[2] = __uint_as_float(a.y << 16); x[3] = __uint_as_float(a.y & 0xffff0000u);
-    }
+    ld<ST, 4>(p, x);
   } else {
+    // The select form stays: the guarded form of seg_common.h (`if (q < cnt) x[q] = ...` over zeroed registers) compiles all 16
+    // k_lp_stats<..., false, ...> instantiations to other instructions, as this form does the scalar Dice and boundary kernels.
 #pragma unroll
     for (int q = 0; q < 4; ++q) x[q] = q < cnt ? ld1<ST>(p + q) : 0.f;
   }
@@ -460,7 +439,6 @@ k_lp_ref_grad(const PT* __restrict__ pred, const RT* __restrict__ ref, const flo
 
 inline bool lp_nk_ok(int64_t N, int64_t K) { return N >= 0 && N < 65536 && K >= 1 && K < 65536; }
 inline bool lp_flag_ok(int f) { return f == 0 || f == 1; }
-inline bool lp_aligned(const void* p, int bytes) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % bytes) == 0; }
 
 // w: nothing (the lp entries) or the K class weights in device memory (the cw entries), and behind them a SumsOrdered for the
 // *_fwd_ord entries; it selects the kernels' pack.  `oc` (the ord entries only): the partial buffer's capacity and the host
@@ -482,8 +460,8 @@ bool lp_launch_fwd(hipStream_t st, const OrdCounts* oc, const void* pred, const 
     if (want_kl) oc->set(3, g);
     if (edges) { oc->set(1, ge); oc->set(2, ge); }
   }
-  const bool wide = V % 4 == 0 && lp_aligned(pred, 4 * (int)sizeof(PT)) && lp_aligned(ref, 4 * (int)sizeof(RT)) &&
-                    lp_aligned(mask, 16) && lp_aligned(stats, 16);
+  const bool wide = V % 4 == 0 && aligned(pred, 4 * (int)sizeof(PT)) && aligned(ref, 4 * (int)sizeof(RT)) &&
+                    aligned(mask, 16) && aligned(stats, 16);
   if (wide)
     hipLaunchKernelGGL((k_lp_stats<PT, RT, true>), g, b, 0, st, p, r, mask, stats, sums, K, V, mask_ch, ref_is_prob, want_kl,
                        w...);
@@ -557,10 +535,10 @@ void lp_launch_ref(hipStream_t st, const void* pred, const void* ref, const floa
   ADVCHAIN_LP_CHECK(pred && ref && stats && out && dims, "null pointer");                                      \
   ADVCHAIN_LP_CHECK(!weighted || class_w, "null pointer (class_w)");                                           \
   ADVCHAIN_LP_CHECK(lp_flag_ok(pred_bf16) && lp_flag_ok(ref_bf16), "an operand is fp32 (0) or bf16 (1)");      \
-  ADVCHAIN_LP_CHECK(ldims_ok(ndim, dims), "bad dims");                                                         \
+  ADVCHAIN_LP_CHECK(dims_ok(ndim, dims), "bad dims");                                                          \
   ADVCHAIN_LP_CHECK(lp_nk_ok(N, K), "bad N/K (N < 65536, 1 <= K < 65536)");                                    \
   ADVCHAIN_LP_CHECK(!mask || mask_channels == 1 || mask_channels == K, "mask must have 1 or K channels");      \
-  const Dims d = lmake_dims(ndim, dims);                                                                       \
+  const Dims d = make_dims(ndim, dims);                                                                        \
   ADVCHAIN_LP_CHECK(d.voxels() < (1ll << 31), "volume too large")
 
 // `oc` == nullptr: the lp / cw entries (sums = the 4 x 64 slots).  Otherwise the ord entries: sums = the [4][oc->stride] partials.
@@ -646,8 +624,8 @@ int advchain_consistency_lp_ref_bwd(const void* pred, int pred_bf16, const void*
 // The most workgroups a launch of the two entries below (and of lp_fwd / cw_fwd, whose grids they share) has for these
 // arguments: the capacity `stride` of a row of their partial buffer.  Host-only.
 int64_t advchain_consistency_lp_fwd_partials(int64_t N, int64_t K, int ndim, const int64_t* dims, int want_edges) {
-  if (!dims || !ldims_ok(ndim, dims) || !lp_nk_ok(N, K)) return -1;
-  const Dims d = lmake_dims(ndim, dims);
+  if (!dims_ok(ndim, dims) || !lp_nk_ok(N, K)) return -1;
+  const Dims d = make_dims(ndim, dims);
   if (d.voxels() >= (1ll << 31)) return -1;
   int64_t w = (int64_t)advchain_blocks((d.voxels() + 3) / 4, kBlock) * N;
   if (want_edges && K > 1) w = std::max(w, (ndim == 3 ? WTile<3>::count(d) : WTile<2>::count(d)) * N);

@@ -244,10 +244,10 @@ int advchain_consistency_ref_bwd(const float* pred, const float* ref, const floa
                                  int ref_is_prob, int64_t N, int64_t K, int ndim, const int64_t* dims, int mask_channels,
                                  void* stream) {
   ADVCHAIN_CHECK_ARG(pred && ref && grad_ref && dims, "consistency_ref_bwd: null pointer");
-  ADVCHAIN_CHECK_ARG(ldims_ok(ndim, dims), "consistency_ref_bwd: bad dims");
+  ADVCHAIN_CHECK_ARG(dims_ok(ndim, dims), "consistency_ref_bwd: bad dims");
   ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && K >= 1 && K < 65536, "consistency_ref_bwd: bad N/K (N < 65536, 1 <= K < 65536)");
   ADVCHAIN_CHECK_ARG(!mask || mask_channels == 1 || mask_channels == K, "consistency_ref_bwd: mask must have 1 or K channels");
-  const Dims d = lmake_dims(ndim, dims);
+  const Dims d = make_dims(ndim, dims);
   ADVCHAIN_CHECK_ARG(d.voxels() < (1ll << 31), "consistency_ref_bwd: volume too large");
   if (N == 0) return ADVCHAIN_OK;
   hipStream_t st = (hipStream_t)stream;

@@ -905,23 +905,9 @@ static inline int det_warp_bits(int64_t out_voxels) {
 // the workspace of the deterministic warps: [int64 image: N x C x V][max |grad_out| per entry: N, padded to 4]
 static inline int64_t det_warp_image_ints(int64_t N, int64_t C, int64_t V) { return 2 * N * C * V; }
 
-// min_voxels = 2 for a tensor that is GATHERED from (the paired corner gathers read two neighbouring elements:
-// sampler_common.h); the output side of a resampling warp may be a single voxel
-static inline bool dims_ok(int ndim, const int64_t* s, int64_t min_voxels = 2) {
-  if (ndim != 2 && ndim != 3) return false;
-  int64_t v = 1;
-  for (int i = 0; i < ndim; ++i) {
-    if (s[i] < 1 || s[i] > (1 << 24)) return false;
-    v *= s[i];
-  }
-  return v >= min_voxels;
-}
-static inline Dims make_dims(int ndim, const int64_t* s) {
-  Dims d;
-  if (ndim == 3) { d.s0 = (int)s[0]; d.s1 = (int)s[1]; d.s2 = (int)s[2]; }
-  else { d.s0 = 1; d.s1 = (int)s[0]; d.s2 = (int)s[1]; }
-  return d;
-}
+// a tensor that is GATHERED from needs two voxels (the paired corner gathers read two neighbouring elements: sampler_common.h);
+// the output side of a resampling warp may be a single voxel: plain dims_ok
+static inline bool gathered_dims_ok(int ndim, const int64_t* s) { return dims_ok(ndim, s, 2); }
 
 // =============================================================================================
 // C ABI
@@ -945,7 +931,7 @@ int advchain_grid_sample_fwd(const float* in, const float* grid, float* out, int
   const int disp_hint = (clamp_grid >> 8) & 0xff;   // bits 8..15: displacement estimate in voxels (0 = unknown), a performance hint
   clamp_grid &= 1;
   ADVCHAIN_CHECK_ARG(in && grid && out, "grid_sample_fwd: null pointer");
-  ADVCHAIN_CHECK_ARG(dims_ok(ndim, in_dims) && dims_ok(ndim, out_dims, 1), "grid_sample_fwd: bad dims");
+  ADVCHAIN_CHECK_ARG(gathered_dims_ok(ndim, in_dims) && dims_ok(ndim, out_dims), "grid_sample_fwd: bad dims");
   ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && C >= 1, "grid_sample_fwd: bad N/C");
   ADVCHAIN_CHECK_ARG(interp == INTERP_LINEAR || interp == INTERP_NEAREST, "grid_sample_fwd: interp must be 0 (linear) or 1 (nearest)");
   ADVCHAIN_CHECK_ARG(padding >= 0 && padding <= 2, "grid_sample_fwd: padding must be 0/1/2");
@@ -969,7 +955,7 @@ int advchain_grid_sample_fwd_ride(const float* in, const float* grid, float* out
                                   int padding, int clamp_grid, int flags, void* stream) {
   ADVCHAIN_CHECK_ARG(ride_in && ride_out && ride_out != out, "grid_sample_fwd_ride: null/aliased rider");
   ADVCHAIN_CHECK_ARG((flags & ~1) == 0, "grid_sample_fwd_ride: unknown flags");
-  if (ndim == 2 && in && grid && out && dims_ok(ndim, in_dims) && dims_ok(ndim, out_dims, 1) && N > 0 && N < 65536 && C >= 1 &&
+  if (ndim == 2 && in && grid && out && gathered_dims_ok(ndim, in_dims) && dims_ok(ndim, out_dims) && N > 0 && N < 65536 && C >= 1 &&
       (interp == INTERP_LINEAR || interp == INTERP_NEAREST) && padding >= 0 && padding <= 2) {
     const Dims id = make_dims(ndim, in_dims), od = make_dims(ndim, out_dims);
     ADVCHAIN_CHECK_ARG(id.voxels() < (1ll << 31) && od.voxels() < (1ll << 31), "grid_sample_fwd_ride: per-sample volume too large");
@@ -992,7 +978,7 @@ static int grid_sample_bwd_routed(const float* grad_out, const float* in, const 
                                   int halo, void* stream, int32_t* stage_ws) {
   ADVCHAIN_CHECK_ARG(grad_out && in && grid, "grid_sample_bwd: null pointer");
   ADVCHAIN_CHECK_ARG(grad_in || grad_grid, "grid_sample_bwd: nothing to compute");
-  ADVCHAIN_CHECK_ARG(dims_ok(ndim, in_dims) && dims_ok(ndim, out_dims, 1), "grid_sample_bwd: bad dims");
+  ADVCHAIN_CHECK_ARG(gathered_dims_ok(ndim, in_dims) && dims_ok(ndim, out_dims), "grid_sample_bwd: bad dims");
   ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && C >= 1, "grid_sample_bwd: bad N/C");
   ADVCHAIN_CHECK_ARG(interp == INTERP_LINEAR || interp == INTERP_NEAREST, "grid_sample_bwd: interp");
   ADVCHAIN_CHECK_ARG(padding >= 0 && padding <= 2, "grid_sample_bwd: padding");
@@ -1039,7 +1025,7 @@ int advchain_grid_sample_bwd(const float* grad_out, const float* in, const float
 // Host-only size query: the staging buffer of the staged deterministic window scatter (2D, C in {1, 2, 4}); 0 where that form
 // does not exist (3D, other channel counts) -- such calls pass stage_ws = NULL.
 int64_t advchain_window_stage_workspace(int64_t N, int64_t C, int ndim, const int64_t* dims) {
-  if (!dims || !dims_ok(ndim, dims) || N < 0 || N >= 65536 || C < 1) return -1;
+  if (!gathered_dims_ok(ndim, dims) || N < 0 || N >= 65536 || C < 1) return -1;
   if (ndim != 2 || (C != 1 && C != 2 && C != 4)) return 0;
   return advchain_window_stage_ints(N, C, make_dims(ndim, dims));
 }
@@ -1060,7 +1046,7 @@ int advchain_grid_sample_bwd_staged(const float* grad_out, const float* in, cons
 }
 
 int64_t advchain_det_warp_workspace(int64_t N, int64_t C, int ndim, const int64_t* in_dims) {
-  if (!in_dims || !dims_ok(ndim, in_dims, 1) || N < 0 || C < 1) return -1;
+  if (!dims_ok(ndim, in_dims) || N < 0 || C < 1) return -1;
   return det_warp_image_ints(N, C, make_dims(ndim, in_dims).voxels()) + ((N + 3) & ~(int64_t)3);
 }
 
@@ -1073,7 +1059,7 @@ int advchain_grid_sample_bwd_det(const float* grad_out, const float* in, const f
   ADVCHAIN_CHECK_ARG(grad_out && in && grid, "grid_sample_bwd_det: null pointer");
   ADVCHAIN_CHECK_ARG(grad_in || grad_grid, "grid_sample_bwd_det: nothing to compute");
   ADVCHAIN_CHECK_ARG(!grad_in || det_ws, "grid_sample_bwd_det: det_ws required for grad_in (advchain_det_warp_workspace int32 elements)");
-  ADVCHAIN_CHECK_ARG(in_dims && out_dims && dims_ok(ndim, in_dims) && dims_ok(ndim, out_dims, 1), "grid_sample_bwd_det: bad dims");
+  ADVCHAIN_CHECK_ARG(gathered_dims_ok(ndim, in_dims) && dims_ok(ndim, out_dims), "grid_sample_bwd_det: bad dims");
   ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && C >= 1, "grid_sample_bwd_det: bad N/C");
   ADVCHAIN_CHECK_ARG(interp == INTERP_LINEAR || interp == INTERP_NEAREST, "grid_sample_bwd_det: interp");
   ADVCHAIN_CHECK_ARG(padding >= 0 && padding <= 2, "grid_sample_bwd_det: padding");
@@ -1104,7 +1090,7 @@ int advchain_compose_self_fwd(const float* phi, float* out, const float* phi0, i
   const int disp_hint = (final_mode >> 8) & 0xff;   // bits 8..15: displacement estimate of phi in voxels (0 = unknown), a performance hint
   final_mode &= 0xff;
   ADVCHAIN_CHECK_ARG(phi && out && phi != out, "compose_self_fwd: null/aliased pointer");
-  ADVCHAIN_CHECK_ARG(dims_ok(ndim, dims), "compose_self_fwd: bad dims");
+  ADVCHAIN_CHECK_ARG(gathered_dims_ok(ndim, dims), "compose_self_fwd: bad dims");
   ADVCHAIN_CHECK_ARG(final_mode == 0 || (final_mode == 1 && phi0), "compose_self_fwd: final_mode 1 needs phi0");
   ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536, "compose_self_fwd: bad N");
   if (N == 0) return ADVCHAIN_OK;
@@ -1151,7 +1137,7 @@ int advchain_compose_self_bwd(const float* grad_out, const float* phi, float* gr
 static int compose_self_bwd_impl(const float* grad_out, const float* phi, float* grad_phi, int32_t* workspace, int chain,
                                  int halo, int64_t N, int ndim, const int64_t* dims, void* stream, int rm_flags) {
   ADVCHAIN_CHECK_ARG(grad_out && phi && grad_phi, "compose_self_bwd: null pointer");
-  ADVCHAIN_CHECK_ARG(dims_ok(ndim, dims), "compose_self_bwd: bad dims");
+  ADVCHAIN_CHECK_ARG(gathered_dims_ok(ndim, dims), "compose_self_bwd: bad dims");
   ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536, "compose_self_bwd: bad N");
   if (N == 0) return ADVCHAIN_OK;
   const Dims d = make_dims(ndim, dims);
@@ -1195,7 +1181,7 @@ static int compose_self_bwd_impl(const float* grad_out, const float* phi, float*
 int advchain_affine_warp_fwd(const float* in, const float* theta, float* out, int64_t N, int64_t C, int ndim,
                              const int64_t* dims, int interp, int padding, void* stream) {
   ADVCHAIN_CHECK_ARG(in && theta && out, "affine_warp_fwd: null pointer");
-  ADVCHAIN_CHECK_ARG(dims_ok(ndim, dims), "affine_warp_fwd: bad dims");
+  ADVCHAIN_CHECK_ARG(gathered_dims_ok(ndim, dims), "affine_warp_fwd: bad dims");
   ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && C >= 1, "affine_warp_fwd: bad N/C");
   ADVCHAIN_CHECK_ARG(interp == INTERP_LINEAR || interp == INTERP_NEAREST, "affine_warp_fwd: interp");
   ADVCHAIN_CHECK_ARG(padding >= 0 && padding <= 2, "affine_warp_fwd: padding");
@@ -1245,7 +1231,7 @@ int advchain_affine_warp_fwd_ride(const float* in, const float* theta, float* ou
                                   void* stream) {
   ADVCHAIN_CHECK_ARG(ride_in && ride_out && ride_out != out, "affine_warp_fwd_ride: null/aliased rider");
   ADVCHAIN_CHECK_ARG((flags & ~1) == 0, "affine_warp_fwd_ride: unknown flags");
-  if (in && theta && out && dims_ok(ndim, dims) && N > 0 && N < 65536 && C >= 1 && interp == INTERP_LINEAR && padding == PAD_ZEROS) {
+  if (in && theta && out && gathered_dims_ok(ndim, dims) && N > 0 && N < 65536 && C >= 1 && interp == INTERP_LINEAR && padding == PAD_ZEROS) {
     const Dims d = make_dims(ndim, dims);
     if (d.voxels() < (1ll << 31) &&
         advchain_affine_box_fwd_launch(in, theta, out, N, C, ndim, d, (hipStream_t)stream, ride_in, ride_out, flags & 1)) {
@@ -1286,7 +1272,7 @@ static int fuse_rule(int n, const int32_t* hints, int* halos_out) {
 }
 
 int advchain_expo_chain_fused_levels(int64_t N, int ndim, const int64_t* dims, int n, const int32_t* hints) {
-  if (ndim != 2 || !hints || !dims_ok(ndim, dims) || n < 1 || n > 64) return 0;
+  if (ndim != 2 || !hints || !gathered_dims_ok(ndim, dims) || n < 1 || n > 64) return 0;
   int halos = 0;
   const int k = fuse_rule(n, hints, &halos);
   if (k < 2) return 0;
@@ -1296,7 +1282,7 @@ int advchain_expo_chain_fused_levels(int64_t N, int ndim, const int64_t* dims, i
 int advchain_expo_chain_fwd(const float* phi0, float* fields, float* pos, int64_t N, int ndim, const int64_t* dims, int n,
                             float* disp_rows, const int32_t* hints, float* fuse_flag, void* stream) {
   ADVCHAIN_CHECK_ARG(phi0 && pos && n >= 1 && n <= 64 && (n == 1 || fields), "expo_chain_fwd: null pointer / bad n");
-  ADVCHAIN_CHECK_ARG(dims_ok(ndim, dims), "expo_chain_fwd: bad dims");
+  ADVCHAIN_CHECK_ARG(gathered_dims_ok(ndim, dims), "expo_chain_fwd: bad dims");
   const int64_t F = N * ndim * make_dims(ndim, dims).voxels();
   const float* src = phi0;
   // 2D: the leading squarings whose inputs the hints put below one pixel run as ONE launch (expo_fused2d.hip: whole-row LDS
@@ -1359,7 +1345,7 @@ int advchain_expo_chain_bwd(const float* grad_pos, const float* phi0, const floa
                             void* stream) {
   ADVCHAIN_CHECK_ARG(grad_pos && phi0 && grad_phi0 && n >= 1 && n <= 64 && (n == 1 || (fields && scratch)) && halos,
                      "expo_chain_bwd: null pointer / bad n");
-  ADVCHAIN_CHECK_ARG(dims_ok(ndim, dims), "expo_chain_bwd: bad dims");
+  ADVCHAIN_CHECK_ARG(gathered_dims_ok(ndim, dims), "expo_chain_bwd: bad dims");
   ADVCHAIN_CHECK_ARG(grad_phi0 != scratch && grad_pos != grad_phi0 && grad_pos != scratch, "expo_chain_bwd: aliased buffers");
   const int64_t F = N * ndim * make_dims(ndim, dims).voxels();
   // 2D: the steps at the END of the backward (squarings kf-1 .. 0) whose inputs have an EXACT sub-pixel bound run as one
@@ -1411,7 +1397,7 @@ int advchain_expo_chain_bwd(const float* grad_pos, const float* phi0, const floa
 }
 
 int64_t advchain_affine_warp_bwd_workspace(int64_t N, int ndim, const int64_t* dims) {
-  if (!dims_ok(ndim, dims)) return -1;
+  if (!gathered_dims_ok(ndim, dims)) return -1;
   const Dims d = make_dims(ndim, dims);
   return N * (int64_t)affine_grid_blocks(d) * ndim * (ndim + 1) + N * (kGeoFloats + 1) + N * (int64_t)advchain_affine_box_tiles(ndim, d);  // floats
 }
@@ -1422,7 +1408,7 @@ int advchain_affine_warp_bwd(const float* grad_out, const float* in, const float
   ADVCHAIN_CHECK_ARG(grad_out && in && theta, "affine_warp_bwd: null pointer");
   ADVCHAIN_CHECK_ARG(grad_in || grad_theta, "affine_warp_bwd: nothing to compute");
   ADVCHAIN_CHECK_ARG(workspace, "affine_warp_bwd: workspace required (advchain_affine_warp_bwd_workspace floats)");
-  ADVCHAIN_CHECK_ARG(dims_ok(ndim, dims), "affine_warp_bwd: bad dims");
+  ADVCHAIN_CHECK_ARG(gathered_dims_ok(ndim, dims), "affine_warp_bwd: bad dims");
   ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && C >= 1, "affine_warp_bwd: bad N/C");
   ADVCHAIN_CHECK_ARG(interp == INTERP_LINEAR || interp == INTERP_NEAREST, "affine_warp_bwd: interp");
   ADVCHAIN_CHECK_ARG(padding >= 0 && padding <= 2, "affine_warp_bwd: padding");
@@ -1517,7 +1503,7 @@ int advchain_affine_warp_bwd_det(const float* grad_out, const float* in, const f
   ADVCHAIN_CHECK_ARG(grad_in || grad_theta, "affine_warp_bwd_det: nothing to compute");
   ADVCHAIN_CHECK_ARG(workspace, "affine_warp_bwd_det: workspace required (advchain_affine_warp_bwd_workspace floats)");
   ADVCHAIN_CHECK_ARG(!grad_in || det_ws, "affine_warp_bwd_det: det_ws required for grad_in (advchain_det_warp_workspace int32 elements)");
-  ADVCHAIN_CHECK_ARG(dims && dims_ok(ndim, dims), "affine_warp_bwd_det: bad dims");
+  ADVCHAIN_CHECK_ARG(gathered_dims_ok(ndim, dims), "affine_warp_bwd_det: bad dims");
   ADVCHAIN_CHECK_ARG(N >= 0 && N < 65536 && C >= 1, "affine_warp_bwd_det: bad N/C");
   ADVCHAIN_CHECK_ARG(interp == INTERP_LINEAR || interp == INTERP_NEAREST, "affine_warp_bwd_det: interp");
   ADVCHAIN_CHECK_ARG(padding >= 0 && padding <= 2, "affine_warp_bwd_det: padding");

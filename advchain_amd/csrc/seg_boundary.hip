@@ -13,7 +13,7 @@
 //                      an online max: s = sum exp(x_k - m) and a = sum omega_k phi_k exp(x_k - m) are rescaled together when the
 //                      maximum moves, so t(v) = sum_k omega_k phi_k p_k = a / s.  lse and t are kept for the backward; one partial
 //                      per workgroup.
-//   k_boundary_finish  one workgroup adds the partials in a fixed order and divides by N V.
+//   k_seg_finish       (seg_common.h) one workgroup adds the partials in a fixed order and divides by N V.
 // Backward, one launch: gx_j = gs / (N V) p_j (omega_j phi_j - t), zero at voxels that are not counted, rounded once to the
 // logits' dtype.  No float atomics, no host read-back, every output written by a kernel; compiled without contraction so that the
 // fp32 / bf16 and the vector / scalar instantiations round alike.
@@ -25,75 +25,20 @@
 namespace advchain {
 namespace {
 
-constexpr int kVox = 4;                      // voxels per lane
-constexpr int kTile = kBlock * kVox;         // voxels per workgroup
-
 enum { BOUNDARY_IGNORE_BACKGROUND = 1 };
-
-// the lane's voxels v0..v0+3 of one plane; `cnt` of them exist (VEC: 0 or 4), the others read as 0
-template <typename ST, bool VEC>
-__device__ __forceinline__ void ld4(const ST* __restrict__ p, int cnt, float (&x)[kVox]) {
-#pragma unroll
-  for (int q = 0; q < kVox; ++q) x[q] = 0.f;
-  if constexpr (VEC) {
-    if (cnt > 0) ld<ST, 4>(p, x);
-  } else {
-#pragma unroll
-    for (int q = 0; q < kVox; ++q)
-      if (q < cnt) {
-        float one[1];
-        ld<ST, 1>(p + q, one);
-        x[q] = one[0];
-      }
-  }
-}
-
-template <typename ST, bool VEC>
-__device__ __forceinline__ void st4(ST* __restrict__ p, int cnt, const float (&x)[kVox]) {
-  if constexpr (VEC) {
-    if (cnt > 0) st<ST, 4>(p, x);
-  } else {
-#pragma unroll
-    for (int q = 0; q < kVox; ++q)
-      if (q < cnt) {
-        const float one[1] = {x[q]};
-        st<ST, 1>(p + q, one);
-      }
-  }
-}
 
 // what a voxel contributes: 1 (counted), 0 (not counted: -100 or past the end), NaN (a label outside [0, K))
 template <bool VEC>
 __device__ __forceinline__ void voxel_gates(const int64_t* __restrict__ lab, int cnt, int K, float (&gate)[kVox]) {
   int64_t y[kVox];
 #pragma unroll
-  for (int q = 0; q < kVox; ++q) y[q] = -100;
-  if (lab) {
-    if constexpr (VEC) {
-      if (cnt > 0) ld_labels<4>(lab, y);
-    } else {
-#pragma unroll
-      for (int q = 0; q < kVox; ++q)
-        if (q < cnt) y[q] = lab[q];
-    }
-  }
+  for (int q = 0; q < kVox; ++q) y[q] = -100;                       // (defined without labels too; not read then)
+  if (lab) ld4_labels<VEC>(lab, cnt, y);
 #pragma unroll
   for (int q = 0; q < kVox; ++q) {
     if (!lab) gate[q] = q < cnt ? 1.f : 0.f;
     else gate[q] = y[q] == -100 ? 0.f : ((y[q] < 0 || y[q] >= K) ? qnan() : 1.f);
   }
-}
-
-__device__ __forceinline__ int lane_count(int64_t V, int64_t v0) {
-  const int64_t left = V - v0;
-  return left <= 0 ? 0 : (left >= kVox ? kVox : (int)left);
-}
-
-// sum of the counted raw weights, in class order (uniform)
-__device__ __forceinline__ float counted_weight_sum(const float* __restrict__ weight, int first, int K) {
-  float s = 0.f;
-  for (int c = first; c < K; ++c) s += weight ? weight[c] : 1.f;
-  return s;
 }
 
 template <typename ST, bool VEC>
@@ -143,15 +88,6 @@ k_boundary_fwd(const ST* __restrict__ x, const int64_t* __restrict__ lab, const 
   if (threadIdx.x == 0) part[n * gridDim.x + blockIdx.x] = sum[0];
 }
 
-__global__ void __launch_bounds__(kBlock)
-k_boundary_finish(const float* __restrict__ part, float* __restrict__ value, int64_t M, float denom) {
-  __shared__ float smem[4];
-  float s[1] = {0.f};
-  for (int64_t i = threadIdx.x; i < M; i += kBlock) s[0] += part[i];
-  block_sum<1>(s, smem);
-  if (threadIdx.x == 0) value[0] = s[0] / denom;
-}
-
 template <typename ST, bool VEC>
 __global__ void __launch_bounds__(kBlock)
 k_boundary_bwd(const ST* __restrict__ x, const int64_t* __restrict__ lab, const float* __restrict__ maps,
@@ -184,36 +120,6 @@ k_boundary_bwd(const ST* __restrict__ x, const int64_t* __restrict__ lab, const 
   }
 }
 
-// ---- host helpers -------------------------------------------------------------------------------------------------------
-int64_t boundary_voxels(int ndim, const int64_t* dims) {
-  if (!dims || (ndim != 2 && ndim != 3)) return -1;
-  int64_t V = 1;
-  for (int i = 0; i < ndim; ++i) {
-    if (dims[i] < 1 || dims[i] > (1 << 24)) return -1;
-    V *= dims[i];
-  }
-  return V <= ((int64_t)1 << 40) ? V : -1;
-}
-inline int64_t boundary_blocks(int64_t V) { return (V + kTile - 1) / kTile; }
-inline bool boundary_shape_ok(int64_t N, int64_t K, int64_t V) {
-  if (!(N >= 1 && N <= 65535 && K >= 1 && K <= 65535 && V >= 1 && boundary_blocks(V) <= 0x7fffffff)) return false;
-  return V <= (((int64_t)1 << 62) / 12) / (N * K);
-}
-
-template <typename ST>
-void launch_boundary_fwd(bool vec, dim3 grid, hipStream_t s, const void* x, const int64_t* lab, const float* maps, const float* w,
-                         float* saved, float* part, int K, int64_t V, int first) {
-  if (vec) hipLaunchKernelGGL((k_boundary_fwd<ST, true>), grid, dim3(kBlock), 0, s, (const ST*)x, lab, maps, w, saved, part, K, V, first);
-  else hipLaunchKernelGGL((k_boundary_fwd<ST, false>), grid, dim3(kBlock), 0, s, (const ST*)x, lab, maps, w, saved, part, K, V, first);
-}
-
-template <typename ST>
-void launch_boundary_bwd(bool vec, dim3 grid, hipStream_t s, const void* x, const int64_t* lab, const float* maps, const float* w,
-                         const float* saved, const float* gs, void* gx, int K, int64_t V, int first, float inv_denom) {
-  if (vec) hipLaunchKernelGGL((k_boundary_bwd<ST, true>), grid, dim3(kBlock), 0, s, (const ST*)x, lab, maps, w, saved, gs, (ST*)gx, K, V, first, inv_denom);
-  else hipLaunchKernelGGL((k_boundary_bwd<ST, false>), grid, dim3(kBlock), 0, s, (const ST*)x, lab, maps, w, saved, gs, (ST*)gx, K, V, first, inv_denom);
-}
-
 }  // namespace
 }  // namespace advchain
 
@@ -222,9 +128,9 @@ using namespace advchain;
 extern "C" {
 
 int64_t advchain_boundary_workspace(int64_t N, int64_t K, int ndim, const int64_t* dims) {
-  const int64_t V = boundary_voxels(ndim, dims);
-  if (V < 0 || !boundary_shape_ok(N, K, V)) return -1;
-  return N * boundary_blocks(V);
+  const int64_t V = seg_voxels(ndim, dims);
+  if (V < 0 || !seg_shape_ok(N, K, V)) return -1;
+  return N * seg_blocks(V);
 }
 
 int advchain_boundary_fwd(const void* logits, int logits_bf16, const int64_t* labels, const float* maps, const float* weight,
@@ -232,20 +138,23 @@ int advchain_boundary_fwd(const void* logits, int logits_bf16, const int64_t* la
                           int flags, void* stream) {
   ADVCHAIN_CHECK_ARG(logits && maps && workspace && value, "boundary_fwd: null pointer");
   ADVCHAIN_CHECK_ARG(K >= 1 && K <= 65535, "boundary_fwd: K must be in 1..65535");
-  const int64_t V = boundary_voxels(ndim, dims);
-  ADVCHAIN_CHECK_ARG(V > 0 && boundary_shape_ok(N, K, V), "boundary_fwd: bad N, ndim or dims");
+  const int64_t V = seg_voxels(ndim, dims);
+  ADVCHAIN_CHECK_ARG(V > 0 && seg_shape_ok(N, K, V), "boundary_fwd: bad N, ndim or dims");
   ADVCHAIN_CHECK_ARG(logits_bf16 == 0 || logits_bf16 == 1, "boundary_fwd: logits are fp32 (0) or bf16 (1)");
   ADVCHAIN_CHECK_ARG((flags & ~1) == 0, "boundary_fwd: unknown flags");
   const int first = (flags & BOUNDARY_IGNORE_BACKGROUND) ? 1 : 0;
   ADVCHAIN_CHECK_ARG(K > first, "boundary_fwd: no class left with ignore_background");
   const bool vec = V % 4 == 0 && aligned(logits, logits_bf16 ? 8 : 16) && aligned(labels, 16) && aligned(maps, 16) && aligned(saved, 16);
-  const int64_t nb = boundary_blocks(V);
+  const int64_t nb = seg_blocks(V);
   const dim3 grid((unsigned)nb, (unsigned)N);
   hipStream_t s = (hipStream_t)stream;
-  if (logits_bf16) launch_boundary_fwd<unsigned short>(vec, grid, s, logits, labels, maps, weight, saved, workspace, (int)K, V, first);
-  else launch_boundary_fwd<float>(vec, grid, s, logits, labels, maps, weight, saved, workspace, (int)K, V, first);
+  seg_dispatch(logits_bf16, false, vec, [&](auto st, auto, auto ve) {      // (no second flag)
+    using ST = typename decltype(st)::type;
+    hipLaunchKernelGGL((k_boundary_fwd<ST, decltype(ve)::value>), grid, dim3(kBlock), 0, s, (const ST*)logits, labels, maps, weight,
+                       saved, workspace, (int)K, V, first);
+  });
   ADVCHAIN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_boundary_finish, dim3(1), dim3(kBlock), 0, s, workspace, value, N * nb, (float)(N * V));
+  hipLaunchKernelGGL(k_seg_finish, dim3(1), dim3(kBlock), 0, s, workspace, N * nb, (float)(N * V), value);
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
 }
@@ -255,18 +164,21 @@ int advchain_boundary_bwd(const void* logits, int logits_bf16, const int64_t* la
                           const int64_t* dims, int flags, void* stream) {
   ADVCHAIN_CHECK_ARG(logits && maps && saved && grad_logits, "boundary_bwd: null pointer");
   ADVCHAIN_CHECK_ARG(K >= 1 && K <= 65535, "boundary_bwd: K must be in 1..65535");
-  const int64_t V = boundary_voxels(ndim, dims);
-  ADVCHAIN_CHECK_ARG(V > 0 && boundary_shape_ok(N, K, V), "boundary_bwd: bad N, ndim or dims");
+  const int64_t V = seg_voxels(ndim, dims);
+  ADVCHAIN_CHECK_ARG(V > 0 && seg_shape_ok(N, K, V), "boundary_bwd: bad N, ndim or dims");
   ADVCHAIN_CHECK_ARG(logits_bf16 == 0 || logits_bf16 == 1, "boundary_bwd: logits are fp32 (0) or bf16 (1)");
   ADVCHAIN_CHECK_ARG((flags & ~1) == 0, "boundary_bwd: unknown flags");
   const int first = (flags & BOUNDARY_IGNORE_BACKGROUND) ? 1 : 0;
   ADVCHAIN_CHECK_ARG(K > first, "boundary_bwd: no class left with ignore_background");
   const bool vec = V % 4 == 0 && aligned(logits, logits_bf16 ? 8 : 16) && aligned(labels, 16) && aligned(maps, 16) &&
                    aligned(saved, 16) && aligned(grad_logits, logits_bf16 ? 8 : 16);
-  const dim3 grid((unsigned)boundary_blocks(V), (unsigned)N);
+  const dim3 grid((unsigned)seg_blocks(V), (unsigned)N);
   hipStream_t s = (hipStream_t)stream;
-  if (logits_bf16) launch_boundary_bwd<unsigned short>(vec, grid, s, logits, labels, maps, weight, saved, grad_scale, grad_logits, (int)K, V, first, 1.f / (float)(N * V));
-  else launch_boundary_bwd<float>(vec, grid, s, logits, labels, maps, weight, saved, grad_scale, grad_logits, (int)K, V, first, 1.f / (float)(N * V));
+  seg_dispatch(logits_bf16, false, vec, [&](auto st, auto, auto ve) {
+    using ST = typename decltype(st)::type;
+    hipLaunchKernelGGL((k_boundary_bwd<ST, decltype(ve)::value>), grid, dim3(kBlock), 0, s, (const ST*)logits, labels, maps, weight,
+                       saved, grad_scale, (ST*)grad_logits, (int)K, V, first, 1.f / (float)(N * V));
+  });
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
 }

@@ -31,62 +31,9 @@
 namespace advchain {
 namespace {
 
-constexpr int kVox = 4;                      // voxels per lane
-constexpr int kTile = kBlock * kVox;         // voxels per workgroup
 constexpr int kChunk = 16;                   // classes between two barriers of sweep two
 
 enum { DICE_IGNORE_BACKGROUND = 1, DICE_BATCH = 2 };
-
-// the lane's voxels v0..v0+3 of one plane; `cnt` of them exist (VEC: 0 or 4), the others read as 0
-template <typename ST, bool VEC>
-__device__ __forceinline__ void ld4(const ST* __restrict__ p, int cnt, float (&x)[kVox]) {
-#pragma unroll
-  for (int q = 0; q < kVox; ++q) x[q] = 0.f;
-  if constexpr (VEC) {
-    if (cnt > 0) ld<ST, 4>(p, x);
-  } else {
-#pragma unroll
-    for (int q = 0; q < kVox; ++q)
-      if (q < cnt) {
-        float one[1];
-        ld<ST, 1>(p + q, one);
-        x[q] = one[0];
-      }
-  }
-}
-
-template <typename ST, bool VEC>
-__device__ __forceinline__ void st4(ST* __restrict__ p, int cnt, const float (&x)[kVox]) {
-  if constexpr (VEC) {
-    if (cnt > 0) st<ST, 4>(p, x);
-  } else {
-#pragma unroll
-    for (int q = 0; q < kVox; ++q)
-      if (q < cnt) {
-        const float one[1] = {x[q]};
-        st<ST, 1>(p + q, one);
-      }
-  }
-}
-
-// labels of the lane's voxels; a voxel that does not exist reads as -100 (not counted)
-template <bool VEC>
-__device__ __forceinline__ void ld4_labels(const int64_t* __restrict__ p, int cnt, int64_t (&y)[kVox]) {
-#pragma unroll
-  for (int q = 0; q < kVox; ++q) y[q] = -100;
-  if constexpr (VEC) {
-    if (cnt > 0) ld_labels<4>(p, y);
-  } else {
-#pragma unroll
-    for (int q = 0; q < kVox; ++q)
-      if (q < cnt) y[q] = p[q];
-  }
-}
-
-__device__ __forceinline__ int lane_count(int64_t V, int64_t v0) {
-  const int64_t left = V - v0;
-  return left <= 0 ? 0 : (left >= kVox ? kVox : (int)left);
-}
 
 // one-hot value of class c at a voxel labelled y: NaN for a label outside [0, K) (the caller leaves -100 out)
 __device__ __forceinline__ float one_hot_at(int64_t y, int c, bool bad) { return bad ? qnan() : (y == c ? 1.f : 0.f); }
@@ -322,53 +269,16 @@ k_dice_bwd(const ST* __restrict__ x, const int64_t* __restrict__ lab, const floa
 }
 
 // ---- host helpers -------------------------------------------------------------------------------------------------------
-// voxels per entry, or -1 for a bad shape
-int64_t dice_voxels(int ndim, const int64_t* dims) {
-  if (!dims || (ndim != 2 && ndim != 3)) return -1;
-  int64_t V = 1;
-  for (int i = 0; i < ndim; ++i) {
-    if (dims[i] < 1 || dims[i] > (1 << 24)) return -1;
-    V *= dims[i];
-  }
-  return V <= ((int64_t)1 << 40) ? V : -1;
-}
-inline int64_t dice_blocks(int64_t V) { return (V + kTile - 1) / kTile; }
-// (N K V bounded so that neither the element offsets nor the workspace size, at most 3 N K (V / 1024 + 1) + N + 3 N K + 3
-// floats, can leave int64)
-inline bool dice_shape_ok(int64_t N, int64_t K, int64_t V) {
-  if (!(N >= 1 && N <= 65535 && K >= 1 && K <= 65535 && V >= 1 && dice_blocks(V) <= 0x7fffffff)) return false;
-  return V <= (((int64_t)1 << 62) / 12) / (N * K);
-}
-
 struct DiceLayout {          // the workspace: triples per (workgroup, class) | CE partial per workgroup | sums per (row, class)
   int64_t nb, part, ce, sums;
   DiceLayout(int64_t N, int64_t K, int64_t V) {
-    nb = dice_blocks(V);
+    nb = seg_blocks(V);
     part = N * nb * K * 3;
     ce = (N * nb + 3) / 4 * 4;             // (keeps `sums` 16-byte aligned)
     sums = N * K * 3;
   }
   int64_t total() const { return part + ce + sums; }
 };
-
-template <typename ST, bool SOFT>
-void launch_dice_fwd(bool vec, dim3 grid, hipStream_t s, const void* x, const int64_t* lab, const float* soft, const float* w,
-                     float* lse, float* part, float* ce_part, int K, int64_t V, int want_ce) {
-  if (vec)
-    hipLaunchKernelGGL((k_dice_fwd<ST, SOFT, true>), grid, dim3(kBlock), 0, s, (const ST*)x, lab, soft, w, lse, part, ce_part, K, V, want_ce);
-  else
-    hipLaunchKernelGGL((k_dice_fwd<ST, SOFT, false>), grid, dim3(kBlock), 0, s, (const ST*)x, lab, soft, w, lse, part, ce_part, K, V, want_ce);
-}
-
-template <typename ST, bool SOFT>
-void launch_dice_bwd(bool vec, dim3 grid, hipStream_t s, const void* x, const int64_t* lab, const float* soft, const float* w,
-                     const float* lse, const float* coef, const float* gs, void* gx, float* gt, int K, int64_t V, float dice_w,
-                     float ce_scale) {
-  if (vec)
-    hipLaunchKernelGGL((k_dice_bwd<ST, SOFT, true>), grid, dim3(kBlock), 0, s, (const ST*)x, lab, soft, w, lse, coef, gs, (ST*)gx, gt, K, V, dice_w, ce_scale);
-  else
-    hipLaunchKernelGGL((k_dice_bwd<ST, SOFT, false>), grid, dim3(kBlock), 0, s, (const ST*)x, lab, soft, w, lse, coef, gs, (ST*)gx, gt, K, V, dice_w, ce_scale);
-}
 
 inline bool finite_nonneg(float v) { return v >= 0.f && v <= 3.40282347e38f; }   // false for NaN
 
@@ -380,8 +290,8 @@ using namespace advchain;
 extern "C" {
 
 int64_t advchain_dice_workspace(int64_t N, int64_t K, int ndim, const int64_t* dims) {
-  const int64_t V = dice_voxels(ndim, dims);
-  if (V < 0 || !dice_shape_ok(N, K, V)) return -1;
+  const int64_t V = seg_voxels(ndim, dims);
+  if (V < 0 || !seg_shape_ok(N, K, V)) return -1;
   return DiceLayout(N, K, V).total();
 }
 
@@ -391,8 +301,8 @@ int advchain_dice_fwd(const void* logits, int logits_bf16, const int64_t* labels
   ADVCHAIN_CHECK_ARG(logits && workspace && value, "dice_fwd: null pointer");
   ADVCHAIN_CHECK_ARG((labels != nullptr) != (soft != nullptr), "dice_fwd: exactly one of labels / soft target");
   ADVCHAIN_CHECK_ARG(K >= 1 && K <= 65535, "dice_fwd: K must be in 1..65535");
-  const int64_t V = dice_voxels(ndim, dims);
-  ADVCHAIN_CHECK_ARG(V > 0 && dice_shape_ok(N, K, V), "dice_fwd: bad N, ndim or dims");
+  const int64_t V = seg_voxels(ndim, dims);
+  ADVCHAIN_CHECK_ARG(V > 0 && seg_shape_ok(N, K, V), "dice_fwd: bad N, ndim or dims");
   ADVCHAIN_CHECK_ARG(logits_bf16 == 0 || logits_bf16 == 1, "dice_fwd: logits are fp32 (0) or bf16 (1)");
   ADVCHAIN_CHECK_ARG((flags & ~3) == 0, "dice_fwd: unknown flags");
   ADVCHAIN_CHECK_ARG(finite_nonneg(smooth), "dice_fwd: smooth must be finite and >= 0");
@@ -407,13 +317,11 @@ int advchain_dice_fwd(const void* logits, int logits_bf16, const int64_t* labels
                    aligned(lse, 16);
   const dim3 grid((unsigned)lay.nb, (unsigned)N);
   hipStream_t s = (hipStream_t)stream;
-  if (logits_bf16) {
-    if (soft) launch_dice_fwd<unsigned short, true>(vec, grid, s, logits, labels, soft, weight, lse, part, ce_part, (int)K, V, want_ce);
-    else launch_dice_fwd<unsigned short, false>(vec, grid, s, logits, labels, soft, weight, lse, part, ce_part, (int)K, V, want_ce);
-  } else {
-    if (soft) launch_dice_fwd<float, true>(vec, grid, s, logits, labels, soft, weight, lse, part, ce_part, (int)K, V, want_ce);
-    else launch_dice_fwd<float, false>(vec, grid, s, logits, labels, soft, weight, lse, part, ce_part, (int)K, V, want_ce);
-  }
+  seg_dispatch(logits_bf16, soft != nullptr, vec, [&](auto st, auto so, auto ve) {
+    using ST = typename decltype(st)::type;
+    hipLaunchKernelGGL((k_dice_fwd<ST, decltype(so)::value, decltype(ve)::value>), grid, dim3(kBlock), 0, s, (const ST*)logits,
+                       labels, soft, weight, lse, part, ce_part, (int)K, V, want_ce);
+  });
   ADVCHAIN_LAUNCH_CHECK();
   const int64_t R = (flags & DICE_BATCH) ? 1 : N, M = (flags & DICE_BATCH) ? N * lay.nb : lay.nb;
   hipLaunchKernelGGL(k_dice_reduce, dim3((unsigned)K, (unsigned)R), dim3(kBlock), 0, s, part, sums, (int)K, M);
@@ -432,21 +340,19 @@ int advchain_dice_bwd(const void* logits, int logits_bf16, const int64_t* labels
   ADVCHAIN_CHECK_ARG((labels != nullptr) != (soft != nullptr), "dice_bwd: exactly one of labels / soft target");
   ADVCHAIN_CHECK_ARG(!(labels && grad_soft), "dice_bwd: a label target has no gradient");
   ADVCHAIN_CHECK_ARG(K >= 1 && K <= 65535, "dice_bwd: K must be in 1..65535");
-  const int64_t V = dice_voxels(ndim, dims);
-  ADVCHAIN_CHECK_ARG(V > 0 && dice_shape_ok(N, K, V), "dice_bwd: bad N, ndim or dims");
+  const int64_t V = seg_voxels(ndim, dims);
+  ADVCHAIN_CHECK_ARG(V > 0 && seg_shape_ok(N, K, V), "dice_bwd: bad N, ndim or dims");
   ADVCHAIN_CHECK_ARG(logits_bf16 == 0 || logits_bf16 == 1, "dice_bwd: logits are fp32 (0) or bf16 (1)");
   const bool vec = V % 4 == 0 && aligned(logits, logits_bf16 ? 8 : 16) && aligned(labels, 16) && aligned(soft, 16) &&
                    aligned(lse, 16) && aligned(grad_logits, logits_bf16 ? 8 : 16) && aligned(grad_soft, 16);
-  const dim3 grid((unsigned)dice_blocks(V), (unsigned)N);
+  const dim3 grid((unsigned)seg_blocks(V), (unsigned)N);
   const float ce_scale = ce_w / (float)(N * V);
   hipStream_t s = (hipStream_t)stream;
-  if (logits_bf16) {
-    if (soft) launch_dice_bwd<unsigned short, true>(vec, grid, s, logits, labels, soft, weight, lse, coef, grad_scale, grad_logits, grad_soft, (int)K, V, dice_w, ce_scale);
-    else launch_dice_bwd<unsigned short, false>(vec, grid, s, logits, labels, soft, weight, lse, coef, grad_scale, grad_logits, grad_soft, (int)K, V, dice_w, ce_scale);
-  } else {
-    if (soft) launch_dice_bwd<float, true>(vec, grid, s, logits, labels, soft, weight, lse, coef, grad_scale, grad_logits, grad_soft, (int)K, V, dice_w, ce_scale);
-    else launch_dice_bwd<float, false>(vec, grid, s, logits, labels, soft, weight, lse, coef, grad_scale, grad_logits, grad_soft, (int)K, V, dice_w, ce_scale);
-  }
+  seg_dispatch(logits_bf16, soft != nullptr, vec, [&](auto st, auto so, auto ve) {
+    using ST = typename decltype(st)::type;
+    hipLaunchKernelGGL((k_dice_bwd<ST, decltype(so)::value, decltype(ve)::value>), grid, dim3(kBlock), 0, s, (const ST*)logits,
+                       labels, soft, weight, lse, coef, grad_scale, (ST*)grad_logits, grad_soft, (int)K, V, dice_w, ce_scale);
+  });
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
 }

@@ -19,6 +19,7 @@
 // Reductions: one partial per workgroup into the caller's workspace, then ONE workgroup adds them in a fixed order and applies
 // the normaliser -- no float atomics, the value is bitwise reproducible.  Two launches per direction at most.
 #include "common.h"
+#include "loss_common.h"
 #include "seg_common.h"
 
 namespace advchain {
@@ -136,25 +137,13 @@ k_ce_bwd(const ST* __restrict__ x, const int64_t* __restrict__ lab, const float*
   }
 }
 
-// value[0] = (sum of the nb partials, fixed order) / denom
-__global__ void __launch_bounds__(kBlock) k_seg_finish(const float* __restrict__ partial, int64_t nb, float denom,
-                                                       float* __restrict__ value) {
-  __shared__ float smem[4];
-  float s[1] = {0.f};
-  for (int64_t i = threadIdx.x; i < nb; i += kBlock) s[0] += partial[i];
-  block_sum<1>(s, smem);
-  if (threadIdx.x == 0) value[0] = s[0] / denom;
-}
-
 // ---- contour ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float hsm(int i) { return i == 1 ? 2.f : 1.f; }                     // [1, 2, 1]
-__device__ __forceinline__ float hdf(int i) { return i == 0 ? 1.f : (i == 1 ? 0.f : -1.f); }   // [1, 0, -1]
 // taps (a0, a1, a2) in {0,1,2}^3 of the cross-correlations (a0 unused in 2D): 2D A = Sobel-x, B = Sobel-y;
-// 3D (Q14) A = h (x) hp (x) h (conv_x and conv_y alike), B = h (x) h (x) hp
+// 3D (Q14) A = h (x) hp (x) h (conv_x and conv_y alike), B = h (x) h (x) hp -- the stencils of the consistency loss (loss_common.h)
 template <int DIM>
-__device__ __forceinline__ float tap_a(int a0, int a1, int a2) { return DIM == 2 ? hsm(a1) * hdf(a2) : hsm(a0) * hdf(a1) * hsm(a2); }
+__device__ __forceinline__ float tap_a(int a0, int a1, int a2) { float wa, wb; stencil_w<DIM>(a0, a1, a2, wa, wb); return wa; }
 template <int DIM>
-__device__ __forceinline__ float tap_b(int a0, int a1, int a2) { return DIM == 2 ? hdf(a1) * hsm(a2) : hsm(a0) * hsm(a1) * hdf(a2); }
+__device__ __forceinline__ float tap_b(int a0, int a1, int a2) { float wa, wb; stencil_w<DIM>(a0, a1, a2, wa, wb); return wb; }
 
 __device__ __forceinline__ int ring_slot(int z) { return (z + 3) % 3; }   // z >= -1
 
@@ -333,18 +322,6 @@ k_one_hot(const int64_t* __restrict__ lab, float* __restrict__ out, int64_t D, i
 }
 
 // ---- host helpers -------------------------------------------------------------------------------------------------------
-bool sdims_ok(int ndim, const int64_t* s) {
-  if (!s || (ndim != 2 && ndim != 3)) return false;
-  for (int i = 0; i < ndim; ++i)
-    if (s[i] < 1 || s[i] > (1 << 24)) return false;
-  return true;
-}
-Dims smake_dims(int ndim, const int64_t* s) {
-  Dims d;
-  if (ndim == 3) { d.s0 = (int)s[0]; d.s1 = (int)s[1]; d.s2 = (int)s[2]; }
-  else { d.s0 = 1; d.s1 = (int)s[0]; d.s2 = (int)s[1]; }
-  return d;
-}
 struct ContourGrid {
   int tiles_x, zc;
   dim3 grid;
@@ -365,27 +342,6 @@ inline int ce_vec(int64_t HW, int bf16, const void* x, const void* lab, const vo
           aligned(b, bf16 ? 8 : 16)) ? 4 : 1;
 }
 
-template <typename ST, bool SOFT>
-void launch_ce_fwd(int vec, int64_t blocks, hipStream_t s, const void* x, const int64_t* lab, const float* soft,
-                   const float* w, float* lse, float* ws, int K, int64_t HW, int64_t P) {
-  if (vec == 4)
-    hipLaunchKernelGGL((k_ce_fwd<ST, SOFT, 4>), dim3((unsigned)blocks), dim3(kBlock), 0, s, (const ST*)x, lab, soft, w, lse, ws, K, HW, P);
-  else
-    hipLaunchKernelGGL((k_ce_fwd<ST, SOFT, 1>), dim3((unsigned)blocks), dim3(kBlock), 0, s, (const ST*)x, lab, soft, w, lse, ws, K, HW, P);
-}
-
-template <typename ST, bool SOFT>
-void launch_ce_bwd(int vec, int64_t blocks, hipStream_t s, const void* x, const int64_t* lab, const float* soft,
-                   const float* w, const float* lse, const float* gs, void* gx, float* gt, int K, int64_t HW, int64_t P,
-                   float denom) {
-  if (vec == 4)
-    hipLaunchKernelGGL((k_ce_bwd<ST, SOFT, 4>), dim3((unsigned)blocks), dim3(kBlock), 0, s, (const ST*)x, lab, soft, w, lse, gs,
-                       (ST*)gx, gt, K, HW, P, denom);
-  else
-    hipLaunchKernelGGL((k_ce_bwd<ST, SOFT, 1>), dim3((unsigned)blocks), dim3(kBlock), 0, s, (const ST*)x, lab, soft, w, lse, gs,
-                       (ST*)gx, gt, K, HW, P, denom);
-}
-
 }  // namespace
 }  // namespace advchain
 
@@ -394,8 +350,8 @@ using namespace advchain;
 extern "C" {
 
 int64_t advchain_seg_loss_workspace(int64_t N, int ndim, const int64_t* dims) {
-  if (N < 0 || !sdims_ok(ndim, dims)) return -1;
-  const Dims d = smake_dims(ndim, dims);
+  if (N < 0 || !dims_ok(ndim, dims)) return -1;
+  const Dims d = make_dims(ndim, dims);
   const int64_t ce = advchain_blocks(N * d.voxels(), kBlock);           // VEC = 1 grid (the larger one)
   const int64_t cn = ContourGrid(N, ndim, d).blocks();
   return ce > cn ? ce : cn;
@@ -407,19 +363,17 @@ int advchain_ce2d_fwd(const void* logits, int logits_bf16, const int64_t* labels
   ADVCHAIN_CHECK_ARG(logits && workspace && value, "ce2d_fwd: null pointer");
   ADVCHAIN_CHECK_ARG((labels != nullptr) != (soft != nullptr), "ce2d_fwd: exactly one of labels / soft target");
   ADVCHAIN_CHECK_ARG(K >= 1 && K < (1 << 24), "ce2d_fwd: K must be >= 1");
-  ADVCHAIN_CHECK_ARG(N >= 1 && sdims_ok(2, dims), "ce2d_fwd: bad N or dims");
+  ADVCHAIN_CHECK_ARG(N >= 1 && dims_ok(2, dims), "ce2d_fwd: bad N or dims");
   ADVCHAIN_CHECK_ARG(logits_bf16 == 0 || logits_bf16 == 1, "ce2d_fwd: logits are fp32 (0) or bf16 (1)");
   const int64_t HW = dims[0] * dims[1], P = N * HW;
   const int vec = ce_vec(HW, logits_bf16, logits, labels ? (const void*)labels : nullptr, soft, lse, nullptr);
   const int64_t blocks = advchain_blocks(P, kBlock * vec);
   hipStream_t s = (hipStream_t)stream;
-  if (logits_bf16) {
-    if (soft) launch_ce_fwd<unsigned short, true>(vec, blocks, s, logits, labels, soft, weight, lse, workspace, (int)K, HW, P);
-    else launch_ce_fwd<unsigned short, false>(vec, blocks, s, logits, labels, soft, weight, lse, workspace, (int)K, HW, P);
-  } else {
-    if (soft) launch_ce_fwd<float, true>(vec, blocks, s, logits, labels, soft, weight, lse, workspace, (int)K, HW, P);
-    else launch_ce_fwd<float, false>(vec, blocks, s, logits, labels, soft, weight, lse, workspace, (int)K, HW, P);
-  }
+  seg_dispatch(logits_bf16, soft != nullptr, vec == 4, [&](auto st, auto so, auto ve) {
+    using ST = typename decltype(st)::type;
+    hipLaunchKernelGGL((k_ce_fwd<ST, decltype(so)::value, decltype(ve)::value ? 4 : 1>), dim3((unsigned)blocks), dim3(kBlock), 0, s,
+                       (const ST*)logits, labels, soft, weight, lse, workspace, (int)K, HW, P);
+  });
   ADVCHAIN_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_seg_finish, dim3(1), dim3(kBlock), 0, s, workspace, blocks, denom, value);
   ADVCHAIN_LAUNCH_CHECK();
@@ -434,20 +388,18 @@ int advchain_ce2d_bwd(const void* logits, int logits_bf16, const int64_t* labels
   ADVCHAIN_CHECK_ARG((labels != nullptr) != (soft != nullptr), "ce2d_bwd: exactly one of labels / soft target");
   ADVCHAIN_CHECK_ARG(!(labels && grad_soft), "ce2d_bwd: a label target has no gradient");
   ADVCHAIN_CHECK_ARG(K >= 1 && K < (1 << 24), "ce2d_bwd: K must be >= 1");
-  ADVCHAIN_CHECK_ARG(N >= 1 && sdims_ok(2, dims), "ce2d_bwd: bad N or dims");
+  ADVCHAIN_CHECK_ARG(N >= 1 && dims_ok(2, dims), "ce2d_bwd: bad N or dims");
   ADVCHAIN_CHECK_ARG(logits_bf16 == 0 || logits_bf16 == 1, "ce2d_bwd: logits are fp32 (0) or bf16 (1)");
   const int64_t HW = dims[0] * dims[1], P = N * HW;
   const int vec = ce_vec(HW, logits_bf16, logits, labels ? (const void*)labels : nullptr, soft, lse, grad_logits) == 4 &&
                   aligned(grad_soft, 16) ? 4 : 1;
   const int64_t blocks = advchain_blocks(P, kBlock * vec);
   hipStream_t s = (hipStream_t)stream;
-  if (logits_bf16) {
-    if (soft) launch_ce_bwd<unsigned short, true>(vec, blocks, s, logits, labels, soft, weight, lse, grad_scale, grad_logits, grad_soft, (int)K, HW, P, denom);
-    else launch_ce_bwd<unsigned short, false>(vec, blocks, s, logits, labels, soft, weight, lse, grad_scale, grad_logits, grad_soft, (int)K, HW, P, denom);
-  } else {
-    if (soft) launch_ce_bwd<float, true>(vec, blocks, s, logits, labels, soft, weight, lse, grad_scale, grad_logits, grad_soft, (int)K, HW, P, denom);
-    else launch_ce_bwd<float, false>(vec, blocks, s, logits, labels, soft, weight, lse, grad_scale, grad_logits, grad_soft, (int)K, HW, P, denom);
-  }
+  seg_dispatch(logits_bf16, soft != nullptr, vec == 4, [&](auto st, auto so, auto ve) {
+    using ST = typename decltype(st)::type;
+    hipLaunchKernelGGL((k_ce_bwd<ST, decltype(so)::value, decltype(ve)::value ? 4 : 1>), dim3((unsigned)blocks), dim3(kBlock), 0, s,
+                       (const ST*)logits, labels, soft, weight, lse, grad_scale, (ST*)grad_logits, grad_soft, (int)K, HW, P, denom);
+  });
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
 }
@@ -460,12 +412,12 @@ int advchain_contour_fwd(const float* input, const int64_t* labels, const float*
   ADVCHAIN_CHECK_ARG(K >= 1 && K < (1 << 24), "contour_fwd: K must be >= 1");
   ADVCHAIN_CHECK_ARG(first_class == 0 || first_class == 1, "contour_fwd: first_class is 0 or 1");
   ADVCHAIN_CHECK_ARG(K > first_class, "contour_fwd: no object class left");
-  ADVCHAIN_CHECK_ARG(N >= 1 && N < 65536 && sdims_ok(ndim, dims), "contour_fwd: bad N or dims");
+  ADVCHAIN_CHECK_ARG(N >= 1 && N < 65536 && dims_ok(ndim, dims), "contour_fwd: bad N or dims");
   const int oc = (int)K - first_class;
   // 2D: the conv output has |S| channels, which a mask of 2..|S|-1 channels does not broadcast against; 3D: one channel
   ADVCHAIN_CHECK_ARG(!mask || (mask_channels >= 1 && (ndim == 3 || mask_channels == 1 || mask_channels >= oc)),
                      "contour_fwd: a 2D mask needs 1 or >= K - first_class channels");
-  const Dims d = smake_dims(ndim, dims);
+  const Dims d = make_dims(ndim, dims);
   const ContourGrid cg(N, ndim, d);
   ADVCHAIN_CHECK_ARG(cg.ok(), "contour_fwd: bad dims");
   const int mask_used = mask ? (mask_channels < oc ? mask_channels : oc) : 0;
@@ -492,8 +444,8 @@ int advchain_contour_bwd(const float* R, const float* grad_scale, float* grad_in
   ADVCHAIN_CHECK_ARG(grad_input || grad_soft, "contour_bwd: null pointer (no gradient requested)");
   ADVCHAIN_CHECK_ARG(K >= 1 && K < (1 << 24), "contour_bwd: K must be >= 1");
   ADVCHAIN_CHECK_ARG(first_class == 0 || first_class == 1, "contour_bwd: first_class is 0 or 1");
-  ADVCHAIN_CHECK_ARG(N >= 1 && N < 65536 && sdims_ok(ndim, dims), "contour_bwd: bad N or dims");
-  const Dims d = smake_dims(ndim, dims);
+  ADVCHAIN_CHECK_ARG(N >= 1 && N < 65536 && dims_ok(ndim, dims), "contour_bwd: bad N or dims");
+  const Dims d = make_dims(ndim, dims);
   const ContourGrid cg(N, ndim, d);
   ADVCHAIN_CHECK_ARG(cg.ok(), "contour_bwd: bad dims");
   const float denom = (float)(N * d.voxels());

@@ -81,9 +81,15 @@ def _stream_obj():
     return s
 
 
-def _dev(t, name="tensor"):
+def _require_device(t, name):
+    """t, a device tensor, or AdvchainHipError."""
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise _lib.AdvchainHipError("%s must be a CUDA/ROCm tensor: the advchain_amd kernels have no CPU path" % name)
+    return t
+
+
+def _dev(t, name="tensor"):
+    _require_device(t, name)
     if t.dtype != torch.float32:
         raise _lib.AdvchainHipError("%s must be float32, got %s" % (name, t.dtype))
     return t if t.is_contiguous() else t.contiguous()
@@ -1955,19 +1961,49 @@ def consistency_sums(pred, ref, mask, coef, ref_is_prob=False, want_edges=True, 
 
 def _dev_logits(t, name="input"):
     """fp32 or bf16 (a model under autocast) logits; the kernels read bf16 natively."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise _lib.AdvchainHipError("%s must be a CUDA/ROCm tensor: the advchain_amd kernels have no CPU path" % name)
+    _require_device(t, name)
     if t.dtype not in (torch.float32, torch.bfloat16):
         raise _lib.AdvchainHipError("%s must be float32 or bfloat16, got %s" % (name, t.dtype))
     return t if t.is_contiguous() else t.contiguous()
 
 
 def _dev_labels(t, name="target"):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise _lib.AdvchainHipError("%s must be a CUDA/ROCm tensor: the advchain_amd kernels have no CPU path" % name)
+    _require_device(t, name)
     if t.dtype != torch.int64:
         raise RuntimeError("%s: expected labels of scalar type Long (int64), got %s" % (name, t.dtype))
     return t if t.is_contiguous() else t.contiguous()
+
+
+def _class_weight_tensor(weight, K, device):
+    """K class weights (tensor, list or array) as a flat fp32 tensor on `device`; None stays None."""
+    if weight is None:
+        return None
+    if isinstance(weight, torch.Tensor):
+        weight = weight.detach().to(device=device, dtype=torch.float32)
+    else:
+        weight = torch.as_tensor(weight, dtype=torch.float32).to(device)
+    weight = weight.reshape(-1).contiguous()
+    if weight.numel() != K:
+        raise ValueError("weight must have %d entries, got %d" % (K, weight.numel()))
+    return weight
+
+
+def _labels_or_soft(x, target, label_msg, neither_msg):
+    """(labels, None) for an int64 label target (N,dims) of the logits x (N,K,dims), (None, soft) for an fp32 soft target of x's
+    shape.  label_msg takes (expected shape, shape found); neither_msg is the NotImplementedError of any other rank."""
+    if target.dim() == x.dim() - 1:
+        want = (x.shape[0],) + tuple(x.shape[2:])
+        labels = _dev_labels(target, "target")
+        if tuple(labels.shape) != want:
+            raise ValueError(label_msg % (want, tuple(labels.shape)))
+        return labels, None
+    if target.dim() == x.dim():
+        _require_device(target, "target")
+        soft = _dev(target if target.dtype == torch.float32 else target.float(), "target")
+        if soft.shape != x.shape:
+            raise ValueError("soft target must have the input's shape %s, got %s" % (tuple(x.shape), tuple(soft.shape)))
+        return None, soft
+    raise NotImplementedError(neither_msg)
 
 
 def _seg_workspace(N, dims, device):
@@ -2021,27 +2057,9 @@ def cross_entropy_2d(x, target, weight=None, size_average=True):
     if x.dim() != 4:
         raise ValueError("cross_entropy_2D takes 4-D input (N,C,H,W), got %d-D" % x.dim())
     N, K, H, W = x.shape
-    labels = soft = None
-    if target.dim() == 3:
-        labels = _dev_labels(target, "target")
-        if tuple(labels.shape) != (N, H, W):
-            raise ValueError("label target must be (N,H,W) = %s, got %s" % ((N, H, W), tuple(labels.shape)))
-    elif target.dim() == 4:
-        if not isinstance(target, torch.Tensor) or not target.is_cuda:
-            raise _lib.AdvchainHipError("target must be a CUDA/ROCm tensor: the advchain_amd kernels have no CPU path")
-        soft = _dev(target if target.dtype == torch.float32 else target.float(), "target")
-        if soft.shape != x.shape:
-            raise ValueError("soft target must have the input's shape %s, got %s" % (tuple(x.shape), tuple(soft.shape)))
-    else:
-        raise NotImplementedError("cross_entropy_2D: target must be (N,H,W) labels or (N,C,H,W) soft targets")
-    if weight is not None:
-        if isinstance(weight, torch.Tensor):
-            weight = weight.detach().to(device=x.device, dtype=torch.float32)
-        else:
-            weight = torch.as_tensor(weight, dtype=torch.float32).to(x.device)
-        weight = weight.reshape(-1).contiguous()
-        if weight.numel() != K:
-            raise ValueError("weight must have %d entries, got %d" % (K, weight.numel()))
+    labels, soft = _labels_or_soft(x, target, "label target must be (N,H,W) = %s, got %s",
+                                   "cross_entropy_2D: target must be (N,H,W) labels or (N,C,H,W) soft targets")
+    weight = _class_weight_tensor(weight, K, x.device)
     _same_device(x, labels, soft, weight)
     denom = float(N * H * W) if size_average else 1.0
     return _CrossEntropy2D.apply(x, labels, soft, weight, denom)
@@ -2055,8 +2073,7 @@ def cross_entropy_3d(x, target, weight=None, size_average=True):
     x = _dev_logits(x, "input")
     if x.dim() != 5:
         raise ValueError("cross_entropy_3D takes 5-D input (N,C,D,H,W), got %d-D" % x.dim())
-    if not isinstance(target, torch.Tensor) or not target.is_cuda:
-        raise _lib.AdvchainHipError("target must be a CUDA/ROCm tensor: the advchain_amd kernels have no CPU path")
+    _require_device(target, "target")
     N, K, D, H, W = x.shape
     if target.dim() == 4:
         if tuple(target.shape) != (N, D, H, W):
@@ -2125,28 +2142,11 @@ def dice_loss(x, target, weight=None, ignore_background=False, batch_dice=False,
     x = _dev_logits(x, "input")
     if x.dim() not in (4, 5):
         raise ValueError("dice_loss takes 4-D (N,C,H,W) or 5-D (N,C,D,H,W) input, got %d-D" % x.dim())
-    if not isinstance(target, torch.Tensor) or not target.is_cuda:
-        raise _lib.AdvchainHipError("target must be a CUDA/ROCm tensor: the advchain_amd kernels have no CPU path")
+    _require_device(target, "target")
     N, K = x.shape[:2]
-    labels = soft = None
-    if target.dim() == x.dim() - 1:
-        labels = _dev_labels(target, "target")
-        if tuple(labels.shape) != (N,) + tuple(x.shape[2:]):
-            raise ValueError("label target must be %s, got %s" % ((N,) + tuple(x.shape[2:]), tuple(labels.shape)))
-    elif target.dim() == x.dim():
-        soft = _dev(target if target.dtype == torch.float32 else target.float(), "target")
-        if soft.shape != x.shape:
-            raise ValueError("soft target must have the input's shape %s, got %s" % (tuple(x.shape), tuple(soft.shape)))
-    else:
-        raise NotImplementedError("dice_loss: target must be (N,dims) labels or (N,C,dims) soft targets")
-    if weight is not None:
-        if isinstance(weight, torch.Tensor):
-            weight = weight.detach().to(device=x.device, dtype=torch.float32)
-        else:
-            weight = torch.as_tensor(weight, dtype=torch.float32).to(x.device)
-        weight = weight.reshape(-1).contiguous()
-        if weight.numel() != K:
-            raise ValueError("weight must have %d entries, got %d" % (K, weight.numel()))
+    labels, soft = _labels_or_soft(x, target, "label target must be %s, got %s",
+                                   "dice_loss: target must be (N,dims) labels or (N,C,dims) soft targets")
+    weight = _class_weight_tensor(weight, K, x.device)
     _same_device(x, labels, soft, weight)
     flags = (1 if ignore_background else 0) | (2 if batch_dice else 0)
     return _Dice.apply(x, labels, soft, weight, (flags, float(smooth), float(dice_weight), float(ce_weight)))
@@ -2172,8 +2172,7 @@ def _edt_check(rc, what, sp):
 def distance_transform_edt(mask, sampling=None, squared=False):
     """Exact Euclidean distance transform of every leading entry of mask (B,H,W) / (B,D,H,W) (bool, uint8, int64 or fp32;
     nonzero is foreground): fp32 distance to the nearest zero voxel (include/advchain_hip.h: advchain_edt)."""
-    if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
-        raise _lib.AdvchainHipError("mask must be a CUDA/ROCm tensor: the advchain_amd kernels have no CPU path")
+    _require_device(mask, "mask")
     if mask.dtype not in _MASK_KINDS:
         raise _lib.AdvchainHipError("mask must be bool, uint8, int64 or float32, got %s" % mask.dtype)
     mask = mask.detach()
@@ -2302,14 +2301,7 @@ def boundary_loss(x, target=None, weight=None, ignore_background=True, sampling=
         maps = _dev(dist_maps.detach() if isinstance(dist_maps, torch.Tensor) else dist_maps, "dist_maps")
         if maps.shape != x.shape:
             raise ValueError("dist_maps must have the input's shape %s, got %s" % (tuple(x.shape), tuple(maps.shape)))
-    if weight is not None:
-        if isinstance(weight, torch.Tensor):
-            weight = weight.detach().to(device=x.device, dtype=torch.float32)
-        else:
-            weight = torch.as_tensor(weight, dtype=torch.float32).to(x.device)
-        weight = weight.reshape(-1).contiguous()
-        if weight.numel() != K:
-            raise ValueError("weight must have %d entries, got %d" % (K, weight.numel()))
+    weight = _class_weight_tensor(weight, K, x.device)
     _same_device(x, labels, maps, weight)
     return _Boundary.apply(x, labels, maps, weight, 1 if ignore_background else 0)
 
@@ -2358,8 +2350,7 @@ def contour_energy(x, target, mask=None, first_class=1, one_hot_target=True):
     sp = tuple(x.shape[2:])
     labels = soft = None
     if one_hot_target:
-        if not isinstance(target, torch.Tensor) or not target.is_cuda:
-            raise _lib.AdvchainHipError("target must be a CUDA/ROCm tensor: the advchain_amd kernels have no CPU path")
+        _require_device(target, "target")
         labels = target if target.dtype == torch.int64 else target.long()
         if labels.numel() != N * (x.numel() // max(N * K, 1)):
             raise ValueError("label target of shape %s does not match the input %s" % (tuple(target.shape), tuple(x.shape)))
@@ -2369,8 +2360,7 @@ def contour_energy(x, target, mask=None, first_class=1, one_hot_target=True):
         if soft.shape != x.shape:
             raise ValueError("pred size: %s must match target size: %s" % (tuple(x.shape), tuple(soft.shape)))
     if mask is not None:
-        if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
-            raise _lib.AdvchainHipError("mask must be a CUDA/ROCm tensor: the advchain_amd kernels have no CPU path")
+        _require_device(mask, "mask")
         mask = _dev(mask.detach() if mask.dtype == torch.float32 else mask.detach().float(), "mask")
         if mask.dim() != x.dim() or mask.shape[0] != N or tuple(mask.shape[2:]) != sp:
             raise ValueError("mask must be (N, C', %s), got %s" % (sp, tuple(mask.shape)))

@@ -93,7 +93,7 @@ def kernel_times(step, steps):
         name = e.name
         if any(w in name.lower() for w in ("memcpy", "memset")):
             continue
-        for short in ("k_edt_rows", "k_boundary_fwd", "k_boundary_finish", "k_boundary_bwd"):
+        for short in ("k_edt_rows", "k_boundary_fwd", "k_seg_finish", "k_boundary_bwd"):
             if short in name:
                 name = short
         if "k_edt_axis" in name:                       # the template's MODE: 0 plain, 1 finish, 2 finish of the signed maps
