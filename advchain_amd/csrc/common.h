@@ -13,6 +13,11 @@
 
 namespace advchain {
 
+// The running maximum of an online softmax as it enters a subtraction.  Until a finite logit has come by (classes masked with
+// -inf in front) it is -inf, and -inf - (-inf) is NaN; read as the lowest finite float, x - max is -inf for such a class and its
+// exponential 0.  Every other value -- finite ones bit for bit, +inf and NaN, which must go on to poison the voxel -- is itself.
+__device__ __forceinline__ float sub_max(float m) { return m == -__builtin_inff() ? -3.402823466e38f : m; }
+
 enum { INTERP_LINEAR = 0, INTERP_NEAREST = 1 };
 enum { PAD_ZEROS = 0, PAD_BORDER = 1, PAD_REFLECTION = 2 };
 

@@ -68,9 +68,10 @@ struct OrdCounts {
 
 // ---- the run-time-K kernels (loss_lp.hip, loss_ref.hip) ----
 
-// running max / sum of exp(x - max): ONE exp per element (the other factor of the usual two is exp(0))
+// running max / sum of exp(x - max): ONE exp per element (the other factor of the usual two is exp(0)).  sub_max (common.h):
+// a second class masked with -inf in front adds exp(-inf) = 0 instead of exp(NaN).
 __device__ __forceinline__ void online_step(float x, float& mx, float& s) {
-  const float d = x - mx;
+  const float d = x - sub_max(mx);
   const float e = ADVCHAIN_SM_EXP(-fabsf(d));
   if (d > 0.f) { s = s * e + 1.f; mx = x; }
   else s += e;

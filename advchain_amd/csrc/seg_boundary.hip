@@ -66,8 +66,8 @@ k_boundary_fwd(const ST* __restrict__ x, const int64_t* __restrict__ lab, const 
     const float om = counted ? (weight ? weight[c] : 1.f) / wsum : 0.f;
 #pragma unroll
     for (int q = 0; q < kVox; ++q) {
-      const float mn = fmaxf(m[q], xc[q]);
-      const float sc = __expf(m[q] - mn), e = __expf(xc[q] - mn);
+      const float mn = fmaxf(m[q], xc[q]), ms = sub_max(mn);         // (a class masked with -inf in front: common.h)
+      const float sc = __expf(m[q] - ms), e = __expf(xc[q] - ms);
       s[q] = s[q] * sc + e;
       a[q] = a[q] * sc + (counted ? (om * fc[q]) * e : 0.f);
       m[q] = mn;

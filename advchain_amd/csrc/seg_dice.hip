@@ -76,8 +76,8 @@ k_dice_fwd(const ST* __restrict__ x, const int64_t* __restrict__ lab, const floa
     const float wc = want_ce ? class_weight(weight, c, wsum, Kf) : 1.f;
 #pragma unroll
     for (int q = 0; q < kVox; ++q) {
-      const float mn = fmaxf(m[q], xc[q]);
-      s[q] = s[q] * __expf(m[q] - mn) + __expf(xc[q] - mn);
+      const float mn = fmaxf(m[q], xc[q]), ms = sub_max(mn);         // (a class masked with -inf in front: common.h)
+      s[q] = s[q] * __expf(m[q] - ms) + __expf(xc[q] - ms);
       m[q] = mn;
       if constexpr (SOFT) {
         if (want_ce) {

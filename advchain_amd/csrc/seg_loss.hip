@@ -56,8 +56,8 @@ k_ce_fwd(const ST* __restrict__ x, const int64_t* __restrict__ lab, const float*
       const float wc = class_weight(weight, c, wsum, Kf);
 #pragma unroll
       for (int q = 0; q < VEC; ++q) {
-        const float mn = fmaxf(m[q], xc[q]);
-        s[q] = s[q] * __expf(m[q] - mn) + __expf(xc[q] - mn);
+        const float mn = fmaxf(m[q], xc[q]), ms = sub_max(mn);       // (a class masked with -inf in front: common.h)
+        s[q] = s[q] * __expf(m[q] - ms) + __expf(xc[q] - ms);
         m[q] = mn;
         if constexpr (SOFT) {
           const float wt = wc * tc[q];
