@@ -747,7 +747,7 @@ using namespace advchain;
 // scatter_tiled.hip
 int advchain_scatter_tiled_launch(bool self, const float* gout, const float* in, const float* grid, float* gin,
                                   float* ggrid, int64_t N, int64_t C, int ndim, Dims d, int padding, int clamp_grid,
-                                  int32_t* workspace, int chain, int halo, hipStream_t st);
+                                  int32_t* workspace, int halo, hipStream_t st);
 
 // adjoint_gather.hip
 int advchain_self_adjoint_gather_launch(const float* gout, const float* phi, float* gphi, int64_t N, int ndim, Dims d,
@@ -1006,7 +1006,7 @@ static int grid_sample_bwd_routed(const float* grad_out, const float* in, const 
     if (rw != ADVCHAIN_ERR_UNSUPPORTED) return rw;
     advchain_set_route_(ADVCHAIN_ROUTE_TILED);
     return advchain_scatter_tiled_launch(false, grad_out, in, grid, grad_in, grad_grid, N, C, ndim, id, padding,
-                                         clamp_grid, workspace, 0, halo < 0 ? -halo : halo, (hipStream_t)stream);
+                                         clamp_grid, workspace, halo < 0 ? -halo : halo, (hipStream_t)stream);
   }
   if (workspace && grad_in) advchain_zero_async(grad_in, sizeof(float) * N * C * id.voxels(), (hipStream_t)stream);
   advchain_set_route_(ADVCHAIN_ROUTE_GENERAL);
@@ -1162,7 +1162,7 @@ static int compose_self_bwd_impl(const float* grad_out, const float* phi, float*
                                                   0, halo, workspace, (hipStream_t)stream, workspace);   // source-tiled window
     if (rw != ADVCHAIN_ERR_UNSUPPORTED) return rw;
     return advchain_scatter_tiled_launch(true, grad_out, phi, phi, grad_phi, nullptr, N, ndim, ndim, d, PAD_BORDER, 0,
-                                         workspace, chain, halo < 0 ? -halo : halo, (hipStream_t)stream);
+                                         workspace, halo < 0 ? -halo : halo, (hipStream_t)stream);
   }
   const bool vec4 = use_unroll(V, ndim);
   dim3 g(advchain_blocks(V, kBlock * (vec4 ? 4 : 1)), (unsigned)N), b(kBlock);

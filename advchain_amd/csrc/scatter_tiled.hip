@@ -7,8 +7,9 @@
 // on this path are near-identity (|displacement| ~ 0.1-7 voxels), so:
 //
 //   * a workgroup OWNS a tile of the gradient tensor and accumulates it in LDS as 64-bit fixed point
-//     (value * 2^30 / max|grad_out|; exact integer adds => the result does not depend on the order of the
-//     deposits, i.e. the kernel is deterministic, unlike any float-atomic formulation);
+//     (value * 2^30 / max|grad_out| over the samples the workgroup reads; exact integer adds => the result does not
+//     depend on the order of the deposits, i.e. the kernel is deterministic, unlike any float-atomic formulation --
+//     nor on what else is in the batch);
 //   * wave w walks the rows w, w+NW, ... of the tile plus a halo of H voxels (lane = x), prefetching the next
 //     row while it processes the current one; it recomputes the taps of every sample and accumulates only
 //     the corners that fall inside its own tile -- halo samples are processed redundantly by the neighbouring
@@ -53,49 +54,12 @@ __device__ __forceinline__ void lds_add_fixed_wide(long long* p, float v) {
   atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)q);
 }
 
-__device__ __forceinline__ void atomic_max_abs(float* addr, float v) {
-  // non-negative floats order like their bit patterns.  Same-address atomics serialise at ~10 ns each on
-  // MI355X (measured: 8192 of them = 80 us), so skip the atomic when the plain read already dominates.
-  v = fabsf(v);
-  if (v > __builtin_nontemporal_load(addr)) atomicMax(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
-}
-
-// max over the workgroup (result valid in thread 0); smem >= NT/64 floats
-template <int NT>
-__device__ __forceinline__ float block_max(float m, float* smem) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  if ((threadIdx.x & 63) == 0) smem[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int w = 1; w < NT / 64; ++w) m = fmaxf(m, smem[w]);
-  return m;
-}
-
-// |x|_max of a buffer -> *out (caller zeroes *out).  `needed` (optional): skip the pass when *needed == 0.
-__global__ void __launch_bounds__(kBlock) k_absmax(const float* __restrict__ x, int64_t n, float* __restrict__ out, int vec,
-                                                   const int* __restrict__ needed) {
-  if (needed && *needed == 0) return;
-  float m = 0.f;
-  const int64_t n4 = vec ? (n >> 2) : 0;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kBlock) {
-    const float4 q = reinterpret_cast<const float4*>(x)[i];
-    m = fmaxf(fmaxf(m, fmaxf(fabsf(q.x), fabsf(q.y))), fmaxf(fabsf(q.z), fabsf(q.w)));
-  }
-  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) m = fmaxf(m, fabsf(x[i]));
-  __shared__ float smem[kBlock / 64];
-  m = block_max<kBlock>(m, smem);
-  if (threadIdx.x == 0 && m > 0.f) atomic_max_abs(out, m);
-}
-
-// workspace header: [0] overflow counter, [1] "max|grad_out| still to be computed", [2] max|grad_out|, [3] max|result|
-// ([3] == -1: the previous launch of the chain was one that does not track it -- the window scatter)
-__global__ void k_scatter_prepare(int32_t* ws, int chain) {
-  const bool have = chain && ws[3] != -1;
-  ws[2] = have ? ws[3] : 0;
-  ws[1] = have ? 0 : 1;
+// workspace header: [0] overflow counter; [3] = -1, the mark of a launch that leaves no max|result| behind (as the march and
+// window scatters write it).  [1] and [2] are not used: until round 24 they held the flag and the value of a whole-batch
+// max|grad_out| that scaled the fixed point; every workgroup now takes its scale from the samples it reads.
+__global__ void k_scatter_prepare(int32_t* ws) {
   ws[0] = 0;
-  ws[3] = 0;
+  ws[3] = -1;
 }
 
 template <int DIM, int C>
@@ -110,8 +74,7 @@ template <int DIM, int PAD, int C, bool SELF, bool NEED_GGRID, int NT>
 __global__ void __launch_bounds__(NT)
 k_scatter_rows(const float* __restrict__ gout, const float* __restrict__ in, const float* __restrict__ grid,
                float* __restrict__ gin, float* __restrict__ ggrid, Dims d, TileCfg tc, int clamp_grid,
-               const float* __restrict__ absmax_in, float* __restrict__ absmax_out, int* __restrict__ ovf_count,
-               int2* __restrict__ ovf_list, int ovf_cap) {
+               int* __restrict__ ovf_count, int2* __restrict__ ovf_list, int ovf_cap) {
   extern __shared__ long long acc[];
   constexpr int NW = NT / 64;
   const int V = (int)d.voxels();
@@ -124,9 +87,6 @@ k_scatter_rows(const float* __restrict__ gout, const float* __restrict__ in, con
   const int x0 = tx * tc.t2, y0 = ty * tc.t1, z0 = tz * tc.t0;
   const int tvox = tc.t0 * tc.t1 * tc.t2;
   for (int i = threadIdx.x; i < C * tvox; i += NT) acc[i] = 0;
-  const float amax = absmax_in[0];
-  const FixScale fs = fix_scale(amax, kFixedBits);
-  __syncthreads();
   // source region = tile + halo, clipped to the volume; lane <-> x
   const int rx0 = max(x0 - tc.h2, 0), rx1 = min(x0 + tc.t2 + tc.h2, d.s2);
   const int ry0 = max(y0 - tc.h1, 0), ry1 = min(y0 + tc.t1 + tc.h1, d.s1);
@@ -139,6 +99,26 @@ k_scatter_rows(const float* __restrict__ gout, const float* __restrict__ in, con
   const float* gn = grid + (int64_t)n * DIM * V;
   const float* inn = in + (int64_t)n * C * V;
   const float* gon = gout + (int64_t)n * C * V;
+
+  // Fixed-point scale: the largest |grad_out| among the samples of the source region -- every deposit into this tile's
+  // accumulator comes from one of them (the others go through the overflow list as floats).  One more pass over the region
+  // (L2 hits: the row walk below reads the same lines).  A maximum over the whole BATCH, as the header's [2] used to supply,
+  // makes an entry's bits depend on its neighbours and costs a small entry beside a large one its low bits.
+  float amax = 0.f;
+  if (xvalid)
+    for (int r = wave; r < nrows; r += NW) {
+      const int s = ((rz0 + r / rh) * d.s1 + ry0 + r % rh) * d.s2 + sx;
+#pragma unroll
+      for (int c = 0; c < C; ++c) amax = fmaxf(amax, fabsf(gon[(int64_t)c * V + s]));
+    }
+  __shared__ float region_max[NW];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+  if (lane == 0) region_max[wave] = amax;
+  __syncthreads();                       // (also: the accumulator is zero)
+#pragma unroll
+  for (int w = 0; w < NW; ++w) amax = fmaxf(amax, region_max[w]);
+  const FixScale fs = fix_scale(amax, kFixedBits);
 
   auto load_row = [&](int row, RowRegs<DIM, C>& r) {
     const int sy = ry0 + row % rh, sz = rz0 + row / rh;
@@ -235,9 +215,8 @@ k_scatter_rows(const float* __restrict__ gout, const float* __restrict__ in, con
     row = nrow;
   }
   __syncthreads();
-  // flush the tile (plain, coalesced along x) and track max|value| for the next launch of a chain
+  // flush the tile (plain, coalesced along x)
   float* ginn = gin + (int64_t)n * C * V;
-  float m = 0.f;
   for (int i = threadIdx.x; i < C * tvox; i += NT) {
     const int c = i / tvox;
     const int l = i - c * tvox;
@@ -247,15 +226,8 @@ k_scatter_rows(const float* __restrict__ gout, const float* __restrict__ in, con
     const int lz = q / tc.t1;
     const int ux = x0 + lx, uy = y0 + ly, uz = z0 + lz;
     if (ux < d.s2 && uy < d.s1 && uz < d.s0) {
-      const float v = fix_out((float)acc[i], fs);
-      ginn[(int64_t)c * V + (uz * d.s1 + uy) * d.s2 + ux] = v;
-      m = fmaxf(m, fabsf(v));
+      ginn[(int64_t)c * V + (uz * d.s1 + uy) * d.s2 + ux] = fix_out((float)acc[i], fs);
     }
-  }
-  if (absmax_out) {
-    __shared__ float smem[NT / 64];
-    m = block_max<NT>(m, smem);
-    if (threadIdx.x == 0 && m > 0.f) atomic_max_abs(absmax_out, m);
   }
 }
 
@@ -264,7 +236,7 @@ template <int DIM, int PAD>
 __global__ void __launch_bounds__(kBlock)
 k_scatter_overflow(const float* __restrict__ gout, const float* __restrict__ grid, float* __restrict__ gin, int C,
                    Dims d, TileCfg tc, int clamp_grid, const int* __restrict__ ovf_count,
-                   const int2* __restrict__ ovf_list, int ovf_cap, float* __restrict__ absmax_out) {
+                   const int2* __restrict__ ovf_list, int ovf_cap) {
   const int V = (int)d.voxels();
   const int count = min(*ovf_count, ovf_cap);
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < count; i += gridDim.x * kBlock) {
@@ -292,8 +264,7 @@ k_scatter_overflow(const float* __restrict__ gout, const float* __restrict__ gri
           const float wgt = t.w(cz, cy, cx);
           for (int c = 0; c < C; ++c) {
             const float v = wgt * gout[((int64_t)n * C + c) * V + s];
-            const float old = atomicAdd(gin + ((int64_t)n * C + c) * V + o, v);
-            if (absmax_out) atomic_max_abs(absmax_out, old + v);
+            atomicAdd(gin + ((int64_t)n * C + c) * V + o, v);
           }
         }
   }
@@ -345,14 +316,14 @@ static TileCfg choose_tiles(int ndim, const Dims& d, int C, int halo_hint) {
 template <int DIM, int PAD, int C>
 static void launch_rows(bool self, bool need_ggrid, dim3 g, size_t lds, hipStream_t st, const float* gout,
                         const float* in, const float* grid, float* gin, float* ggrid, Dims d, TileCfg tc,
-                        int clamp_grid, const float* amax_in, float* amax_out, int* cnt, int2* list, int cap) {
+                        int clamp_grid, int* cnt, int2* list, int cap) {
   // > 48 KiB of LDS leaves <= 3 workgroups per CU: use 8 waves per workgroup to keep the CU busy
   const bool big = lds > 40960, huge = lds > 65536;
 #define LAUNCH(SELF_, GG_, NT_)                                                                                      \
   do {                                                                                                               \
     auto kern = k_scatter_rows<DIM, PAD, C, SELF_, GG_, NT_>;                                                        \
     if (huge) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(kern, g, dim3(NT_), lds, st, gout, in, grid, gin, ggrid, d, tc, clamp_grid, amax_in, amax_out, \
+    hipLaunchKernelGGL(kern, g, dim3(NT_), lds, st, gout, in, grid, gin, ggrid, d, tc, clamp_grid, \
                        cnt, list, cap);                                                                              \
   } while (0)
   if (self) {
@@ -364,57 +335,45 @@ static void launch_rows(bool self, bool need_ggrid, dim3 g, size_t lds, hipStrea
   }
 #undef LAUNCH
   hipLaunchKernelGGL((k_scatter_overflow<DIM, PAD>), dim3(64), dim3(kBlock), 0, st, gout, grid, gin, C, d, tc,
-                     clamp_grid, cnt, list, cap, amax_out);
+                     clamp_grid, cnt, list, cap);
 }
 
 template <int DIM, int PAD>
 static bool launch_rows_c(int C, bool self, bool need_ggrid, dim3 g, size_t lds, hipStream_t st, const float* gout,
                           const float* in, const float* grid, float* gin, float* ggrid, Dims d, TileCfg tc,
-                          int clamp_grid, const float* amax_in, float* amax_out, int* cnt, int2* list, int cap) {
+                          int clamp_grid, int* cnt, int2* list, int cap) {
   switch (C) {
-    case 1: launch_rows<DIM, PAD, 1>(self, need_ggrid, g, lds, st, gout, in, grid, gin, ggrid, d, tc, clamp_grid, amax_in, amax_out, cnt, list, cap); return true;
-    case 2: launch_rows<DIM, PAD, 2>(self, need_ggrid, g, lds, st, gout, in, grid, gin, ggrid, d, tc, clamp_grid, amax_in, amax_out, cnt, list, cap); return true;
-    case 3: launch_rows<DIM, PAD, 3>(self, need_ggrid, g, lds, st, gout, in, grid, gin, ggrid, d, tc, clamp_grid, amax_in, amax_out, cnt, list, cap); return true;
-    case 4: launch_rows<DIM, PAD, 4>(self, need_ggrid, g, lds, st, gout, in, grid, gin, ggrid, d, tc, clamp_grid, amax_in, amax_out, cnt, list, cap); return true;
+    case 1: launch_rows<DIM, PAD, 1>(self, need_ggrid, g, lds, st, gout, in, grid, gin, ggrid, d, tc, clamp_grid, cnt, list, cap); return true;
+    case 2: launch_rows<DIM, PAD, 2>(self, need_ggrid, g, lds, st, gout, in, grid, gin, ggrid, d, tc, clamp_grid, cnt, list, cap); return true;
+    case 3: launch_rows<DIM, PAD, 3>(self, need_ggrid, g, lds, st, gout, in, grid, gin, ggrid, d, tc, clamp_grid, cnt, list, cap); return true;
+    case 4: launch_rows<DIM, PAD, 4>(self, need_ggrid, g, lds, st, gout, in, grid, gin, ggrid, d, tc, clamp_grid, cnt, list, cap); return true;
     default: return false;
   }
 }
 
 // Shared entry used by advchain_grid_sample_bwd / advchain_compose_self_bwd.
-// workspace (int32): [0] overflow counter, [1] flag "max|grad_out| still to be computed", [2] max|grad_out| (float),
-//                    [3] max|result| (float; the int -1 when the producing launch did not track it),
+// workspace (int32): [0] overflow counter, [1], [2] unused, [3] the int -1 (this launch leaves no max|result| behind),
 //                    [4..] (n, s) overflow pairs.
-// chain = 0: max|grad_out| is computed here (one streaming pass over grad_out);
-// chain = 1: the previous launch on this workspace produced grad_out and left max|grad_out| in [3]
-//            (or -1 there if it was a kernel that does not track it: then the pass runs after all).
+// The fixed-point scale is each workgroup's own (the largest |grad_out| of its source region): nothing is handed from one
+// launch of a chain to the next, and a chained call is an ordinary call.
 // Returns ADVCHAIN_ERR_UNSUPPORTED when C is outside 1..4 (caller falls back to the global-atomic kernels).
 int advchain_scatter_tiled_launch(bool self, const float* gout, const float* in, const float* grid, float* gin,
                                   float* ggrid, int64_t N, int64_t C, int ndim, Dims d, int padding, int clamp_grid,
-                                  int32_t* workspace, int chain, int halo, hipStream_t st) {
+                                  int32_t* workspace, int halo, hipStream_t st) {
   if (C < 1 || C > 4) return ADVCHAIN_ERR_UNSUPPORTED;
   const TileCfg tc = choose_tiles(ndim, d, (int)C, halo < 0 ? -halo : halo);   // sign = exactness, used by the gather form only
   const int64_t V = d.voxels();
   int* cnt = workspace;
-  float* amax = reinterpret_cast<float*>(workspace + 2);  // [0] = in, [1] = out
   int2* list = reinterpret_cast<int2*>(workspace + 4);
   const int64_t cap64 = N * V;
   const int cap = cap64 > 0x7fffffff ? 0x7fffffff : (int)cap64;
-  hipLaunchKernelGGL(k_scatter_prepare, dim3(1), dim3(1), 0, st, workspace, chain);   // header reset in one launch
-  {
-    // chain: the pass runs only if the previous launch left no max behind (decided on the device: header [1])
-    const int64_t total = N * C * V;
-    int blocks = (int)((total / 4 + kBlock - 1) / kBlock);
-    if (blocks > 1024) blocks = 1024;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(k_absmax, dim3(blocks), dim3(kBlock), 0, st, gout, total, amax,
-                       (int)((reinterpret_cast<uintptr_t>(gout) & 15) == 0), chain ? workspace + 1 : (const int*)nullptr);
-  }
+  hipLaunchKernelGGL(k_scatter_prepare, dim3(1), dim3(1), 0, st, workspace);   // header reset in one launch
   dim3 g((unsigned)(tc.n0 * tc.n1 * tc.n2), (unsigned)N);
   const size_t lds = (size_t)C * tc.t0 * tc.t1 * tc.t2 * sizeof(long long);
   const bool need_ggrid = ggrid != nullptr;
   bool ok;
 #define GO(DIM_, PAD_) \
-  ok = launch_rows_c<DIM_, PAD_>((int)C, self, need_ggrid, g, lds, st, gout, in, grid, gin, ggrid, d, tc, clamp_grid, amax, amax + 1, cnt, list, cap)
+  ok = launch_rows_c<DIM_, PAD_>((int)C, self, need_ggrid, g, lds, st, gout, in, grid, gin, ggrid, d, tc, clamp_grid, cnt, list, cap)
   if (ndim == 3) {
     switch (padding) {
       case PAD_ZEROS: GO(3, PAD_ZEROS); break;

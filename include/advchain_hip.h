@@ -176,7 +176,9 @@ int advchain_compose_self_fwd(const float* phi, float* out, const float* phi0, i
 /* grad_phi receives both the value path (scatter) and the coordinate path; overwritten when a
  * `workspace` (as above) is given, otherwise it must be pre-zeroed (global-atomic path).
  * chain != 0: grad_out is the grad_phi of the previous call on the same workspace (the backward of
- * consecutive squarings), whose max|.| is already in the workspace -- saves one pass over grad_out.
+ * consecutive squarings).  Accepted for callers that pass it; no formulation scales by a maximum handed from one call to
+ * the next any more (the LDS-tiled scatter, which did, takes its fixed-point scale -- 2^30 / max|grad_out| -- over the
+ * samples each workgroup reads, tile + halo: an entry's result does not depend on the rest of the batch).
  * halo > 0: an upper bound on |displacement| of phi in voxels -- a performance hint only: samples beyond it stay
  * correct through the overflow list (global atomics).  Small bounds (1 in 3D; 1..4 in 2D) select the gather-form
  * adjoint (no atomics, bit-reproducible); larger ones the source-tiled window scatter (float atomics between tiles; the
@@ -188,9 +190,9 @@ int advchain_compose_self_fwd(const float* phi, float* out, const float* phi0, i
  * entries) select the owner-computes scatters of scatter_march.hip: LDS 32-bit fixed-point accumulators scaled by the
  * max|grad_out| over the rows a workgroup visits, plain stores, no zero fill, bit-reproducible, relative error of the
  * accumulation <= 2^-23 / 2^-22 / 2^-21 (bounds of 2 / 3 / 4; 2^-18 for 5..8) of that local maximum per deposit; a NaN / inf in
- * grad_out turns the outputs of the workgroups that visit its row into NaN (it is not dropped).  (Launches that do not track max|result| -- strict gather,
- * window scatter, owner-computes scatters -- leave a marker in the workspace, and a chained scatter call after them
- * recomputes max|grad_out| on the device.) */
+ * grad_out turns the outputs of the workgroups that visit its row into NaN (it is not dropped).  (Workspace word [3]: the
+ * gather form leaves max|result| there, every scatter the mark -1; nothing reads it since the tiled scatter's scale became
+ * local.) */
 int advchain_compose_self_bwd(const float* grad_out, const float* phi, float* grad_phi, int32_t* workspace, int chain,
                               int halo, int64_t N, int ndim, const int64_t* dims, void* stream);
 /* replaces: the loops of vectorFieldExponentiation{2,3}D (adv_morph.py:132-135,165-168) and their autograd, n squarings

@@ -15,9 +15,10 @@ Routes, how a call reaches them, the kernels a rocprofv3 kernel trace of this mo
   rows2d   2D, halo = -H (3..16, squarings ..32): k_march_rowmax + k_scatter_rows2d.  Domain: the rows visited.
            b = 25 / 24 / 22 / 20 / 18 for H <= 2 / 4 / 8 / 16 / 32.  In advchain_expo_chain_bwd consecutive launches hand
            the row maxima of their output to the next one (no k_march_rowmax between them).
-  tiled    3D, halo = 0 (and 2D warps the window scatter does not take, C = 3): k_scatter_prepare + k_absmax + k_scatter_rows
-           (+ k_scatter_overflow).  Domain: the WHOLE grad_out tensor, every batch entry (or, chained after a tiled launch,
-           that launch's max|result|).  b = 30, 64-bit LDS cells.
+  tiled    3D, halo = 0 (and 2D warps the window scatter does not take, C = 3): k_scatter_prepare + k_scatter_rows
+           (+ k_scatter_overflow).  Domain: the samples of the workgroup's source region, tile + halo (until round 24 the WHOLE
+           grad_out tensor, every batch entry: tests/test_layout_gpu.py part C found an entry's bits depending on its
+           neighbours).  b = 30, 64-bit LDS cells.  A1 / A2 below still hold it to the bounds of the wider domain; A5 is bitwise.
   window   3D halo >= 2, every 2D halo the other routes decline: k_scatter_window2d / k_scatter_window3d.  Domain: the
            tile's own samples.  b = 20; tiles flush with float atomics, so results are not bitwise reproducible.
   det      the window route under ops.set_deterministic(True): k_det_absmax + k_scatter_window* + k_det_convert.  Domain:
@@ -31,14 +32,15 @@ the reference is float64, 2e-5 of the largest reference value, 5e-5 for the affi
 their sampling positions off the grid lines, where the fp32 and float64 positions could pick different cells):
   A1  no wraparound: per batch entry, max|got - ref| <= 2^-(b-6) * max|grad_out of that entry|.
   A2  the scale is local: cells farther than the route's reach (its row block + 2H + 2 rows) from every spike keep
-      2e-5 * |ref| + 2^-(b-4) * (the local max).  The tiled route's domain is the whole tensor: A1 against its maximum
-      instead.  The det route's domain is the entry: A1.
+      2e-5 * |ref| + 2^-(b-4) * (the local max).  The tiled route (domain "tensor" below, from when its scale was the
+      whole tensor's maximum): A1 against the tensor's maximum instead.  The det route's domain is the entry: A1.
   A3  zeros: where no non-zero sample reaches a cell the reference is exactly 0 and so is the result; an all-zero entry
       gives exact zeros, never NaN.
   A4  scale invariance: got(2^k g) == 2^k got(g) bit for bit for k = +-60 (the window route: to A1, its flush order
       varies); for k = -90, -100, -112, +100 the result is finite and meets A1 against 2^k ref.
   A5  entries are independent: entry 0's result is bitwise unchanged when entry 1 is 2^20 or 2^-20 times larger
-      (window: to A1 against entry 0's own maximum; tiled: its scale is shared across entries, A1 against the tensor max).
+      (window: to A1 against entry 0's own maximum; tiled: A1 against the tensor max, and bitwise as well since its scale
+      is the workgroup's own -- also tests/test_layout_gpu.py part C).
 """
 import ctypes
 import math
@@ -218,7 +220,7 @@ ROUTES = [
     Route("rows2d_warp_c1_h6", "warp", (140, 90), -6, _rows2d_bits(6), amp=2.4, shear=3.0, C=1, ty=_rows2d_ty(1, 90, 6)),
     Route("rows2d_warp_c4_h3", "warp", (130, 72), -3, _rows2d_bits(3), amp=1.1, shear=1.4, C=4, ty=_rows2d_ty(4, 72, 3),
           pad="border"),
-    # tiled: whole-tensor scale; chained after a tiled, a march and a window launch
+    # tiled (held to the bound of a whole-tensor scale, see the docstring); chained after a tiled, a march and a window launch
     Route("tiled_self_3d", "self", (6, 40, 40), 0, 30, amp=0.9, shear=0.6, domain="tensor"),
     Route("tiled_warp_3d_c2", "warp", (6, 40, 40), 0, 30, amp=0.9, shear=0.6, C=2, domain="tensor"),
     Route("tiled_warp_2d_c3", "warp", (40, 72), 0, 30, amp=2.0, shear=1.5, C=3, domain="tensor"),
@@ -379,9 +381,11 @@ def test_entry_contrast(route):
         got = route.run(gc)
         assert torch.isfinite(got).all(), (route.name, k)
         if route.domain == "tensor":
-            # documented: the tiled route's scale is max|grad_out| over the whole tensor, shared by the entries
+            # (the bound of a scale shared by the entries, which the tiled route had until round 24; its per-region scale meets it)
             _check_a1(route, got, ref0 * torch.tensor([1.0, 2.0 ** k], dtype=torch.float64).view(-1, *([1] * (got.dim() - 1))),
                       gc, "contrast %d" % k)
+            if route.bitwise:      # ... and, its scale being the workgroup's own since round 24, entry 0 keeps its bits
+                assert torch.equal(got[0], base[0]), (route.name, k, float((got[0] - base[0]).abs().max()))
         elif route.bitwise:
             assert torch.equal(got[0], base[0]), (route.name, k, float((got[0] - base[0]).abs().max()))
         else:

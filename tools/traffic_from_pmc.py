@@ -87,7 +87,7 @@ CHAIN_N = 8
 PAIRED_VOXELS = {"cfg2": (2, 64 * 256 * 256), "cfg3": (3, 8 * 128 * 128 * 64), "cfg4": (3, 16 * 128 * 128 * 64), "cfg5": (3, 8 * 160 * 160 * 80)}
 HBM_PEAK = 8.0e12
 WIDE = re.compile(r"k_expo_fused_fwd2d|k_adjoint_fused2d|k_band_reduce_rows|k_loss_fused|k_sample_march_flat<3, true|"r"k_adjoint_gather|k_adjoint_march|k_sample_tiled|k_sample_march<3, true|k_gauss_axis_v4|k_gauss_march_z|k_gauss_xy|k_max_displacement|"
-                  r"k_axpy|k_absmax|k_softmax_diff_v4|k_edge_fwd_march4|k_consistency_bwd_march4|k_affine_box_fwd|k_affine_box_gtheta|"
+                  r"k_axpy|k_softmax_diff_v4|k_edge_fwd_march4|k_consistency_bwd_march4|k_affine_box_fwd|k_affine_box_gtheta|"
                   r"k_scatter_march3d_wide|k_march_rowmax64|k_sample_ring")   # 16 B / lane
 MIXED = {r"k_sample_march<1, false": 1.41, r"k_sample_march<4, false": 1.7,
          r"k_sample_march_flat<1, false": 1.41, r"k_sample_march_flat<4, false": 1.7}   # image 16 B/lane + 3 grid channels 4 B/lane
