@@ -108,6 +108,10 @@ PROTOTYPES = {
     "advchain_signed_maps": (_I, [_P, _P, _P, _P, _L, _L, _I, _P, _P]),
     "advchain_surface_metrics_workspace": (_L, [_L, _L, _I, _P]),
     "advchain_surface_metrics": (_I, [_P, _P, _P, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _P]),
+    "advchain_components_workspace": (_L, [_L, _I, _P]),
+    "advchain_components": (_I, [_P, _P, _P, _P, _P, _L, _I, _P, _I, _L, _L, _P]),
+    "advchain_keep_largest": (_I, [_P, _P, _P, _P, _L, _L, _I, _P, _I, _L, _P]),
+    "advchain_remove_small": (_I, [_P, _P, _P, _L, _I, _P, _I, _L, _L, _L, _P]),
     "advchain_boundary_workspace": (_L, [_L, _L, _I, _P]),
     "advchain_boundary_fwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _P]),
     "advchain_boundary_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _P]),

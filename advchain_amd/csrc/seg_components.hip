@@ -1,0 +1,510 @@
+// Connected components of label maps and the filters on top of them, 2D and 3D, for gfx950:
+//
+//   advchain_components      <- common.postprocess.connected_components
+//   advchain_keep_largest    <- common.postprocess.keep_largest_component
+//   advchain_remove_small    <- common.postprocess.remove_small_components
+//
+// Two voxels of an entry are adjacent when their offsets differ by at most 1 on every axis and on at most `connectivity` axes
+// (scipy's generate_binary_structure); adjacent voxels are connected when they carry the same label and that label is
+// foreground: not `background` and, with a class count K, inside [0, K).  Labels are only compared.  A label-equivalence
+// union-find over `parent` (int32 per voxel: an entry-local linear index, -1 on background):
+//   k_cc_tile      a workgroup stages a tile of 2048 labels in LDS (each int64 label is read once), unites connected voxels
+//                  inside the tile (a run of equal labels in a row by one ballot, run with run by LDS atomic minima, the first
+//                  pair of two runs that touch only) and writes the tile-local root of every voxel -- the smallest linear index of
+//                  its tile-local component -- and, at that root, the voxel count of the tile-local component (0 elsewhere).
+//   k_cc_seam      the voxels on the low faces of a tile re-read their label and those of their neighbours in OTHER tiles (a few
+//                  per cent of the voxels) and unite across the seam in global memory: faces, and with connectivity 2 / 3 the
+//                  pairs that touch only across a tile edge or corner.
+//   k_cc_flatten   parent[v] becomes the root; counts the roots per chunk of 2048 voxels; a tile-local root that is not the root
+//                  adds its count to the root's (one integer atomic per tile a component touches, not per voxel).
+//   k_cc_scan      exclusive scan of the chunk counts per entry (two levels: no workgroup waits on another), count[n].
+//   k_cc_number    root -> 1 + the number of roots in front of it in C order: components are numbered by their smallest voxel.
+//   k_cc_gather    labels and sizes of the root to every voxel.
+//   k_cc_winner    per (entry, class) the 64-bit maximum of (size << 32) | ~root: the largest component, ties to the earlier.
+//   k_cc_keep, k_cc_small   the filtered copies of the input.
+// Invariant of the union-find: parent[x] <= x in every state a thread can observe (a parent is only ever lowered, by an atomic
+// minimum, to the index of a voxel of the same component), so a walk towards the root moves to a strictly smaller index each
+// step and ends after fewer steps than there are voxels.  No kernel waits on a value that another workgroup writes.  Integer
+// atomics only: the result is a function of the input alone, the same bits on every run.  Every word that is read was written
+// by a kernel of the same call: no memset, no host read-back, capturable on one stream.
+#include "common.h"
+
+namespace advchain {
+namespace {
+
+typedef unsigned long long u64;
+typedef unsigned int u32;
+
+constexpr int kTileX = 64;                   // a wave per tile row
+constexpr int kTileY2 = 32;                  // 2D tiles: 32 x 64
+constexpr int kTileZ3 = 4, kTileY3 = 8;      // 3D tiles: 4 x 8 x 64 (a z-slab of four slices); ops.COMPONENTS_TILE mirrors these
+constexpr int kTileVox = 2048;               // voxels of a tile, and of a chunk of the passes that run over linear indices
+constexpr int kPerThread = kTileVox / kBlock;
+
+struct Shape {
+  int D, H, W;         // D == 1 for 2D
+  int TZ, TY;          // tile sizes along z and y (powers of two)
+  int conn;            // 1 .. ndim
+};
+
+__device__ __forceinline__ bool foreground(int64_t y, int64_t background, int64_t K) {
+  return y != background && (K < 0 || (y >= 0 && y < K));
+}
+
+// ---- union-find ---------------------------------------------------------------------------------------------------------------
+// parent[x] <= x always, and every parent is a voxel of the same component.  SCOPE: workgroup for a tile in LDS, agent for the
+// seams in global memory (a relaxed agent-scope load is served by L2; an older value is still a valid ancestor, so staleness
+// costs steps, never correctness: the atomic minimum below is what decides).
+template <int SCOPE>
+__device__ __forceinline__ int uf_find(int* parent, int x) {
+  int y;
+  while ((y = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, SCOPE)) != x) x = y;       // y < x: strictly decreasing, ends at a root
+  return x;
+}
+
+// Lock-free union: lower the parent of the larger root to the smaller root.  If the larger one was no root any more, the atomic
+// returns its parent `old` < a, which is still to be united with b: max(a, b) strictly decreases from one turn to the next, so
+// the loop ends after fewer turns than there are voxels.  It never waits for another thread.
+template <int SCOPE>
+__device__ __forceinline__ void uf_unite(int* parent, int a, int b) {
+  a = uf_find<SCOPE>(parent, a);
+  b = uf_find<SCOPE>(parent, b);
+  while (a != b) {
+    if (a < b) { const int t = a; a = b; b = t; }
+    const int old = __hip_atomic_fetch_min(parent + a, b, __ATOMIC_RELAXED, SCOPE);      // b < a: parent[a] <= a stays true
+    if (old == a) break;                                                                 // a was a root and now hangs below b
+    a = uf_find<SCOPE>(parent, old);                                                     // old < a
+    b = uf_find<SCOPE>(parent, b);
+  }
+}
+
+// ---- tile pass ----------------------------------------------------------------------------------------------------------------
+// blockIdx.x = ((n tiles_z + z tile) tiles_y + y tile) tiles_x + x tile.  The local index (lz TY + ly) 64 + lx orders the voxels
+// of a tile as their linear indices do, so the smallest local index of a component is its smallest linear index in the tile.
+__global__ void __launch_bounds__(kBlock)
+k_cc_tile(const int64_t* __restrict__ labels, int* __restrict__ parent, int* __restrict__ sizes, u64* __restrict__ winners,
+          int64_t NK, int64_t background, int64_t K, Shape s, int tiles_z, int tiles_y, int tiles_x) {
+  __shared__ int64_t lab[kTileVox];
+  __shared__ int par[kTileVox];
+  __shared__ int cnt[kTileVox];
+  if (winners) {                                           // (keep_largest: the maxima of k_cc_winner start at 0)
+    const int64_t threads = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < NK; i += threads) winners[i] = 0ull;
+  }
+  int64_t b = blockIdx.x;
+  const int bx = (int)(b % tiles_x); b /= tiles_x;
+  const int by = (int)(b % tiles_y); b /= tiles_y;
+  const int bz = (int)(b % tiles_z);
+  const int64_t n = b / tiles_z, V = (int64_t)s.D * s.H * s.W;
+  const int z0 = bz * s.TZ, y0 = by * s.TY, x0 = bx * kTileX;
+  const int sy = kTileX, sz = kTileX * s.TY;
+
+#pragma unroll
+  for (int j = 0; j < kPerThread; ++j) {
+    const int i = j * kBlock + threadIdx.x;
+    const int lx = i & (kTileX - 1), ly = (i / kTileX) & (s.TY - 1), lz = i / sz;
+    const int z = z0 + lz, y = y0 + ly, x = x0 + lx;
+    const bool in = z < s.D && y < s.H && x < s.W;
+    const int64_t v = in ? labels[n * V + ((int64_t)z * s.H + y) * s.W + x] : background;
+    lab[i] = v;
+    // a wave holds one tile row: a voxel starts below the first voxel of its run of equal labels in the row (lane lx), which
+    // is the union of the run without an atomic
+    const int64_t left = __shfl_up(v, 1, 64);                                            // (every lane takes part: not behind ||)
+    const u64 heads = __ballot(lx == 0 || left != v);
+    const int start = 63 - __clzll(heads & ((2ull << lx) - 1ull));                       // (bit 0 is set: lane 0 is a head)
+    par[i] = (in && foreground(v, background, K)) ? i - lx + start : -1;
+    cnt[i] = 0;
+  }
+  __syncthreads();
+
+  // unite with the connected neighbours in front (in C order) that lie in this tile; the others are the seam pass's.  Offset
+  // q = (dz + 1) 9 + (dy + 1) 3 + dx + 1: the 12 offsets below (0, 0, -1) (q = 12: the runs above) are the ones in front in
+  // another row; 2D starts at dz = 0.  A pair whose left neighbours are the same pair of runs is left to them: the first pair
+  // of two runs that touch unites them.
+#pragma unroll 1
+  for (int j = 0; j < kPerThread; ++j) {
+    const int i = j * kBlock + threadIdx.x;
+    if (par[i] < 0) continue;                              // (foreground or not never changes)
+    const int lx = i & (kTileX - 1), ly = (i / kTileX) & (s.TY - 1), lz = i / sz;
+    const int64_t mine = lab[i];
+#pragma unroll 1
+    for (int q = s.TZ > 1 ? 0 : 9; q < 12; ++q) {
+      const int dz = q / 9 - 1, dy = (q / 3) % 3 - 1, dx = q % 3 - 1;
+      if ((dz != 0) + (dy != 0) + (dx != 0) > s.conn) continue;
+      if (lz + dz < 0 || ly + dy < 0 || ly + dy >= s.TY || lx + dx < 0 || lx + dx >= kTileX) continue;
+      const int o = i + dz * sz + dy * sy + dx;
+      if (lab[o] != mine) continue;                                                       // (equal to a foreground label: foreground)
+      if (lx > 0 && lx + dx > 0 && lab[i - 1] == mine && lab[o - 1] == mine) continue;
+      uf_unite<__HIP_MEMORY_SCOPE_WORKGROUP>(par, i, o);
+    }
+  }
+  __syncthreads();
+
+  int root[kPerThread];
+#pragma unroll
+  for (int j = 0; j < kPerThread; ++j) {
+    const int i = j * kBlock + threadIdx.x;
+    root[j] = par[i] < 0 ? -1 : uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(par, i);
+    if (root[j] >= 0) atomicAdd(&cnt[root[j]], 1);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < kPerThread; ++j) {
+    const int i = j * kBlock + threadIdx.x;
+    const int lx = i & (kTileX - 1), ly = (i / kTileX) & (s.TY - 1), lz = i / sz;
+    const int z = z0 + lz, y = y0 + ly, x = x0 + lx;
+    if (z >= s.D || y >= s.H || x >= s.W) continue;
+    const int64_t at = n * V + ((int64_t)z * s.H + y) * s.W + x;
+    int r = -1;
+    if (root[j] >= 0) {
+      const int rx = root[j] & (kTileX - 1), ry = (root[j] / kTileX) & (s.TY - 1), rz = root[j] / sz;
+      r = (int)(((int64_t)(z0 + rz) * s.H + y0 + ry) * s.W + x0 + rx);                   // (inside the image: it is foreground)
+    }
+    parent[at] = r;
+    if (sizes) sizes[at] = cnt[i];
+  }
+}
+
+// ---- the passes over linear indices: blockIdx.x = n chunks + chunk, a chunk is 2048 consecutive voxels of an entry ------------
+struct Chunked {
+  int64_t n, base;     // entry, first voxel of the chunk
+};
+__device__ __forceinline__ Chunked chunk_of(int64_t chunks) {
+  Chunked c;
+  c.n = blockIdx.x / chunks;
+  c.base = (blockIdx.x - c.n * chunks) * kTileVox;
+  return c;
+}
+
+__device__ __forceinline__ bool low_face(int z, int y, int x, const Shape& s) {
+  return (x > 0 && (x & (kTileX - 1)) == 0) || (y > 0 && (y & (s.TY - 1)) == 0) || (z > 0 && (z & (s.TZ - 1)) == 0);
+}
+
+// Every connected pair whose voxels lie in different tiles has a voxel on a low face of its tile (along an axis on which the
+// tiles differ, the voxel with the larger coordinate).  That voxel unites the pair; when both are on a low face, the later one.
+__global__ void __launch_bounds__(kBlock)
+k_cc_seam(const int64_t* __restrict__ labels, int* parent, int64_t background, int64_t K, Shape s, int64_t V, int64_t chunks) {
+  const Chunked c = chunk_of(chunks);
+  const int64_t* L = labels + c.n * V;
+  int* P = parent + c.n * V;
+  for (int j = 0; j < kPerThread; ++j) {
+    const int64_t v = c.base + j * kBlock + threadIdx.x;
+    if (v >= V) break;
+    const int x = (int)(v % s.W), y = (int)((v / s.W) % s.H), z = (int)(v / ((int64_t)s.W * s.H));
+    if (!low_face(z, y, x, s)) continue;
+    const int64_t mine = L[v];
+    if (!foreground(mine, background, K)) continue;
+#pragma unroll 1
+    for (int q = s.TZ > 1 ? 0 : 9; q < (s.TZ > 1 ? 27 : 18); ++q) {                     // offsets as in k_cc_tile, all around
+      const int dz = q / 9 - 1, dy = (q / 3) % 3 - 1, dx = q % 3 - 1;
+      if (q == 13 || (dz != 0) + (dy != 0) + (dx != 0) > s.conn) continue;
+      const int z1 = z + dz, y1 = y + dy, x1 = x + dx;
+      if (z1 < 0 || z1 >= s.D || y1 < 0 || y1 >= s.H || x1 < 0 || x1 >= s.W) continue;
+      if ((z1 & -s.TZ) == (z & -s.TZ) && (y1 & -s.TY) == (y & -s.TY) && (x1 & -kTileX) == (x & -kTileX)) continue;
+      const int64_t u = ((int64_t)z1 * s.H + y1) * s.W + x1;
+      if (u > v && low_face(z1, y1, x1, s)) continue;                                   // (that voxel takes the pair)
+      if (L[u] != mine) continue;
+      // the left neighbours are the same pair of tiles and of runs, on the same faces: the pair is theirs
+      if ((x & (kTileX - 1)) != 0 && (x1 & (kTileX - 1)) != 0 && L[v - 1] == mine && L[u - 1] == mine) continue;
+      uf_unite<__HIP_MEMORY_SCOPE_AGENT>(P, (int)v, (int)u);
+    }
+  }
+}
+
+// parent[v] <- root.  Other workgroups shorten their own chains meanwhile: whatever value a walk reads is an ancestor in the
+// final forest (the unions are over), parent[x] <= x still holds.  counts[chunk] = roots in the chunk.  SIZES: sizes[v] is the
+// voxel count of v's tile-local component at a tile-local root and 0 elsewhere; only roots are added to, and only the words of
+// voxels that are no root are read, so the adds of other workgroups cannot be seen half-way.
+template <bool SIZES>
+__global__ void __launch_bounds__(kBlock)
+k_cc_flatten(int* parent, int* sizes, int* __restrict__ counts, int64_t V, int64_t chunks) {
+  __shared__ int roots;
+  const Chunked c = chunk_of(chunks);
+  int* P = parent + c.n * V;
+  int* S = sizes + c.n * V;
+  if (threadIdx.x == 0) roots = 0;
+  __syncthreads();
+  int mine = 0;
+  for (int j = 0; j < kPerThread; ++j) {
+    const int64_t v = c.base + j * kBlock + threadIdx.x;
+    if (v >= V) break;
+    const int p = P[v];
+    if (p < 0) continue;
+    if (p == (int)v) { ++mine; continue; }
+    const int r = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(P, p);
+    if (r != p) P[v] = r;
+    if (SIZES) {
+      const int t = S[v];
+      if (t) atomicAdd(S + r, t);
+    }
+  }
+  if (mine) atomicAdd(&roots, mine);
+  __syncthreads();
+  if (threadIdx.x == 0) counts[blockIdx.x] = roots;
+}
+
+// One workgroup per entry: counts[n][c] <- the sum of the counts in front of chunk c, count[n] <- their total.
+__global__ void __launch_bounds__(kBlock)
+k_cc_scan(int* __restrict__ counts, int64_t* __restrict__ count, int64_t chunks) {
+  __shared__ int scan[2][kBlock];
+  const int t = threadIdx.x;
+  int* C = counts + (int64_t)blockIdx.x * chunks;
+  int carry = 0;
+  for (int64_t c0 = 0; c0 < chunks; c0 += kBlock) {
+    const int x = c0 + t < chunks ? C[c0 + t] : 0;
+    scan[0][t] = x;
+    __syncthreads();
+    int cur = 0;
+    for (int o = 1; o < kBlock; o <<= 1) {
+      scan[cur ^ 1][t] = scan[cur][t] + (t >= o ? scan[cur][t - o] : 0);
+      cur ^= 1;
+      __syncthreads();
+    }
+    if (c0 + t < chunks) C[c0 + t] = carry + scan[cur][t] - x;
+    carry += scan[cur][kBlock - 1];
+    __syncthreads();
+  }
+  if (t == 0) count[blockIdx.x] = carry;
+}
+
+// out[root] <- 1 + the number of roots of the entry in front of it
+__global__ void __launch_bounds__(kBlock)
+k_cc_number(const int* __restrict__ parent, const int* __restrict__ counts, int* __restrict__ out, int64_t V, int64_t chunks) {
+  __shared__ int waves[kBlock / 64];
+  const Chunked c = chunk_of(chunks);
+  const int* P = parent + c.n * V;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int before = counts[blockIdx.x];
+  for (int j = 0; j < kPerThread; ++j) {                                                  // (uniform: no early exit, barriers inside)
+    const int64_t v = c.base + j * kBlock + threadIdx.x;
+    const bool is_root = v < V && P[v] == (int)v;
+    const u64 m = __ballot(is_root);
+    if (lane == 0) waves[wave] = __popcll(m);
+    __syncthreads();
+    int ahead = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < kBlock / 64; ++w) {
+      ahead += w < wave ? waves[w] : 0;
+      all += waves[w];
+    }
+    if (is_root) out[c.n * V + v] = before + ahead + __popcll(m & ((1ull << lane) - 1ull)) + 1;
+    before += all;
+    __syncthreads();
+  }
+}
+
+// labels: the number of the root, 0 on background (the roots hold theirs already; only they are read).  sizes_out: the root's.
+__global__ void __launch_bounds__(kBlock)
+k_cc_gather(const int* __restrict__ parent, const int* __restrict__ sizes, int* out, int* __restrict__ sizes_out, int64_t V,
+            int64_t chunks) {
+  const Chunked c = chunk_of(chunks);
+  const int64_t e = c.n * V;
+  for (int j = 0; j < kPerThread; ++j) {
+    const int64_t v = c.base + j * kBlock + threadIdx.x;
+    if (v >= V) break;
+    const int p = parent[e + v];
+    if (p != (int)v) out[e + v] = p < 0 ? 0 : out[e + p];
+    if (sizes_out) sizes_out[e + v] = p < 0 ? 0 : sizes[e + p];
+  }
+}
+
+__device__ __forceinline__ u64 wave_max_u64(u64 v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const u64 w = __shfl_xor(v, o, 64);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+
+// A root re-reads its label (the class index: in [0, K) since the voxel is foreground) and offers (size << 32) | ~root; the
+// roots of one class in a wave are reduced first, one turn per class among them, so a map of specks does not queue one atomic
+// per speck on one word.
+__global__ void __launch_bounds__(kBlock)
+k_cc_winner(const int64_t* __restrict__ labels, const int* __restrict__ parent, const int* __restrict__ sizes,
+            u64* __restrict__ winners, int64_t K, int64_t V, int64_t chunks) {
+  const Chunked c = chunk_of(chunks);
+  const int64_t e = c.n * V;
+  const int lane = threadIdx.x & 63;
+  for (int j = 0; j < kPerThread; ++j) {
+    const int64_t v = c.base + j * kBlock + threadIdx.x;
+    const bool is_root = v < V && parent[e + v] == (int)v;
+    const int k = is_root ? (int)labels[e + v] : -1;
+    const u64 key = is_root ? ((u64)(u32)sizes[e + v] << 32) | (u64)(0xffffffffu - (u32)v) : 0ull;
+    u64 todo = __ballot(is_root);
+    while (todo) {                                                                       // one turn per class: todo loses bits
+      const int k1 = __shfl(k, __builtin_ctzll(todo), 64);
+      const bool same = k == k1;
+      const u64 best = wave_max_u64(same ? key : 0ull);
+      if (lane == 0) atomicMax(winners + c.n * K + k1, best);
+      todo &= ~__ballot(same);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kBlock)
+k_cc_keep(const int64_t* __restrict__ labels, const int* __restrict__ parent, const u64* __restrict__ winners,
+          int64_t* __restrict__ out, int64_t background, int64_t K, int64_t V, int64_t chunks) {
+  const Chunked c = chunk_of(chunks);
+  const int64_t e = c.n * V;
+  for (int j = 0; j < kPerThread; ++j) {
+    const int64_t v = c.base + j * kBlock + threadIdx.x;
+    if (v >= V) break;
+    const int64_t y = labels[e + v];
+    const int p = parent[e + v];
+    bool keep = true;
+    if (p >= 0) keep = 0xffffffffu - (u32)winners[c.n * K + y] == (u32)p;                 // (p >= 0: y is a class index)
+    out[e + v] = keep ? y : background;
+  }
+}
+
+__global__ void __launch_bounds__(kBlock)
+k_cc_small(const int64_t* __restrict__ labels, const int* __restrict__ parent, const int* __restrict__ sizes,
+           int64_t* __restrict__ out, int64_t background, int64_t min_size, int64_t V, int64_t chunks) {
+  const Chunked c = chunk_of(chunks);
+  const int64_t e = c.n * V;
+  for (int j = 0; j < kPerThread; ++j) {
+    const int64_t v = c.base + j * kBlock + threadIdx.x;
+    if (v >= V) break;
+    const int p = parent[e + v];
+    const bool drop = p >= 0 && (int64_t)sizes[e + p] < min_size;
+    out[e + v] = drop ? background : labels[e + v];
+  }
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------------
+struct Plan {
+  Shape s;
+  int64_t V, chunks, tiles_z, tiles_y, tiles_x;
+  int64_t total;                                 // 4-byte words: parent N V, sizes N V, chunk counts N chunks
+};
+
+bool components_plan(int64_t N, int ndim, const int64_t* dims, Plan* p) {
+  if (N < 1 || !dims_ok(ndim, dims)) return false;
+  const Dims d = make_dims(ndim, dims);
+  p->V = d.voxels();
+  if (p->V > 0x7fffffffLL) return false;                                  // a parent is an int32 index into its entry
+  p->s.D = d.s0; p->s.H = d.s1; p->s.W = d.s2;
+  p->s.TZ = ndim == 3 ? kTileZ3 : 1;
+  p->s.TY = ndim == 3 ? kTileY3 : kTileY2;
+  p->s.conn = 1;
+  p->chunks = (p->V + kTileVox - 1) / kTileVox;
+  p->tiles_z = (d.s0 + p->s.TZ - 1) / p->s.TZ;
+  p->tiles_y = (d.s1 + p->s.TY - 1) / p->s.TY;
+  p->tiles_x = (d.s2 + kTileX - 1) / kTileX;
+  if (N > 0x7fffffffLL / p->V) return false;
+  p->total = 2 * N * p->V + N * p->chunks;
+  return p->total <= 0x7fffffffLL;                                        // (then every grid below fits one launch as well)
+}
+
+struct Work {
+  int* parent;
+  int* sizes;
+  int* counts;
+};
+
+// the passes every entry point shares: tile, seam, flatten
+template <bool SIZES>
+int components_label(const int64_t* labels, void* workspace, u64* winners, int64_t NK, int64_t N, const Plan& p,
+                     int64_t background, int64_t K, Work* w, hipStream_t st) {
+  w->parent = (int*)workspace;
+  w->sizes = w->parent + N * p.V;
+  w->counts = w->sizes + N * p.V;
+  const int64_t tiles = N * p.tiles_z * p.tiles_y * p.tiles_x;           // at most N V
+  const unsigned chunked = (unsigned)(N * p.chunks);
+  hipLaunchKernelGGL(k_cc_tile, dim3((unsigned)tiles), dim3(kBlock), 0, st, labels, w->parent, SIZES ? w->sizes : (int*)nullptr,
+                     winners, NK, background, K, p.s, (int)p.tiles_z, (int)p.tiles_y, (int)p.tiles_x);
+  ADVCHAIN_LAUNCH_CHECK();
+  if (p.tiles_z * p.tiles_y * p.tiles_x > 1) {
+    hipLaunchKernelGGL(k_cc_seam, dim3(chunked), dim3(kBlock), 0, st, labels, w->parent, background, K, p.s, p.V, p.chunks);
+    ADVCHAIN_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_cc_flatten<SIZES>, dim3(chunked), dim3(kBlock), 0, st, w->parent, w->sizes, w->counts, p.V, p.chunks);
+  ADVCHAIN_LAUNCH_CHECK();
+  return ADVCHAIN_OK;
+}
+
+}  // namespace
+}  // namespace advchain
+
+using namespace advchain;
+
+#define COMPONENTS_CHECK_SHAPE(what)                                                                                          \
+  ADVCHAIN_CHECK_ARG(N >= 1, what ": bad N");                                                                                 \
+  ADVCHAIN_CHECK_ARG(dims && (ndim == 2 || ndim == 3), what ": bad ndim or dims");                                            \
+  for (int a = 0; a < ndim; ++a) ADVCHAIN_CHECK_ARG(dims[a] >= 1, what ": bad ndim or dims");                                 \
+  ADVCHAIN_CHECK_ARG(connectivity >= 1 && connectivity <= ndim, what ": connectivity must be in 1..ndim");                    \
+  Plan p;                                                                                                                     \
+  if (!components_plan(N, ndim, dims, &p)) {                                                                                  \
+    advchain_set_error_(what ": more than 2^31 - 1 voxels in an entry, or a workspace of more than 2^31 - 1 words");          \
+    return ADVCHAIN_ERR_UNSUPPORTED;                                                                                          \
+  }                                                                                                                           \
+  p.s.conn = connectivity;                                                                                                    \
+  hipStream_t st = (hipStream_t)stream
+
+extern "C" {
+
+int64_t advchain_components_workspace(int64_t N, int ndim, const int64_t* dims) {
+  Plan p;
+  return components_plan(N, ndim, dims, &p) ? p.total : -1;
+}
+
+int advchain_components(const int64_t* labels, int32_t* out_labels, int64_t* count, int32_t* sizes, void* workspace, int64_t N,
+                        int ndim, const int64_t* dims, int connectivity, int64_t background, int64_t num_classes, void* stream) {
+  ADVCHAIN_CHECK_ARG(labels && out_labels && count && workspace, "components: null pointer");
+  COMPONENTS_CHECK_SHAPE("components");
+  const int64_t K = num_classes < 0 ? -1 : num_classes;
+  Work w;
+  const int rc = sizes ? components_label<true>(labels, workspace, nullptr, 0, N, p, background, K, &w, st)
+                       : components_label<false>(labels, workspace, nullptr, 0, N, p, background, K, &w, st);
+  if (rc != ADVCHAIN_OK) return rc;
+  const unsigned chunked = (unsigned)(N * p.chunks);
+  hipLaunchKernelGGL(k_cc_scan, dim3((unsigned)N), dim3(kBlock), 0, st, w.counts, count, p.chunks);
+  ADVCHAIN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_cc_number, dim3(chunked), dim3(kBlock), 0, st, (const int*)w.parent, (const int*)w.counts, out_labels, p.V,
+                     p.chunks);
+  ADVCHAIN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_cc_gather, dim3(chunked), dim3(kBlock), 0, st, (const int*)w.parent, (const int*)w.sizes, out_labels, sizes,
+                     p.V, p.chunks);
+  ADVCHAIN_LAUNCH_CHECK();
+  return ADVCHAIN_OK;
+}
+
+int advchain_keep_largest(const int64_t* labels, int64_t* out, void* workspace, void* winners, int64_t N, int64_t K, int ndim,
+                          const int64_t* dims, int connectivity, int64_t background, void* stream) {
+  ADVCHAIN_CHECK_ARG(labels && out && workspace && winners, "keep_largest: null pointer");
+  ADVCHAIN_CHECK_ARG(labels != out, "keep_largest: out must not be the input");
+  ADVCHAIN_CHECK_ARG(((uintptr_t)winners & 7) == 0, "keep_largest: winners must be 8-byte aligned");
+  ADVCHAIN_CHECK_ARG(K >= 1 && K <= 65535, "keep_largest: K must be in 1..65535");
+  COMPONENTS_CHECK_SHAPE("keep_largest");
+  ADVCHAIN_CHECK_ARG(N <= ((int64_t)1 << 39) / K, "keep_largest: bad N");
+  Work w;
+  const int rc = components_label<true>(labels, workspace, (u64*)winners, N * K, N, p, background, K, &w, st);
+  if (rc != ADVCHAIN_OK) return rc;
+  const unsigned chunked = (unsigned)(N * p.chunks);
+  hipLaunchKernelGGL(k_cc_winner, dim3(chunked), dim3(kBlock), 0, st, labels, (const int*)w.parent, (const int*)w.sizes,
+                     (u64*)winners, K, p.V, p.chunks);
+  ADVCHAIN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_cc_keep, dim3(chunked), dim3(kBlock), 0, st, labels, (const int*)w.parent, (const u64*)winners, out,
+                     background, K, p.V, p.chunks);
+  ADVCHAIN_LAUNCH_CHECK();
+  return ADVCHAIN_OK;
+}
+
+int advchain_remove_small(const int64_t* labels, int64_t* out, void* workspace, int64_t N, int ndim, const int64_t* dims,
+                          int connectivity, int64_t background, int64_t num_classes, int64_t min_size, void* stream) {
+  ADVCHAIN_CHECK_ARG(labels && out && workspace, "remove_small: null pointer");
+  ADVCHAIN_CHECK_ARG(labels != out, "remove_small: out must not be the input");
+  ADVCHAIN_CHECK_ARG(min_size >= 1, "remove_small: min_size must be at least 1");
+  COMPONENTS_CHECK_SHAPE("remove_small");
+  const int64_t K = num_classes < 0 ? -1 : num_classes;
+  Work w;
+  const int rc = components_label<true>(labels, workspace, nullptr, 0, N, p, background, K, &w, st);
+  if (rc != ADVCHAIN_OK) return rc;
+  hipLaunchKernelGGL(k_cc_small, dim3((unsigned)(N * p.chunks)), dim3(kBlock), 0, st, labels, (const int*)w.parent,
+                     (const int*)w.sizes, out, background, min_size, p.V, p.chunks);
+  ADVCHAIN_LAUNCH_CHECK();
+  return ADVCHAIN_OK;
+}
+
+}  // extern "C"

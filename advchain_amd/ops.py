@@ -2242,6 +2242,72 @@ def surface_distance_metrics(pred, target, num_classes, sampling=None, percentil
     return SurfaceMetrics(f32[0], f32[1], f32[2], f32[3], voxels, max_squared, overlap, dice)
 
 
+# ---- connected components and the filters on them (csrc/seg_components.hip) ------------------------------------------------------
+
+Components = collections.namedtuple("Components", ["labels", "count", "sizes"])
+# The tiles the labelling resolves in LDS, by number of spatial axes (kTileY2 / kTileZ3, kTileY3, kTileX of the source): pairs
+# that straddle them go through the seam pass.
+COMPONENTS_TILE = {2: (32, 64), 3: (4, 8, 64)}
+
+
+def _components_workspace(name, labels):
+    """(labels contiguous, N, spatial shape, dims array, int32 workspace) or NotImplementedError for a refused shape."""
+    labels = _dev_labels(labels.detach() if isinstance(labels, torch.Tensor) else labels, "labels")
+    N, sp = labels.shape[0], tuple(labels.shape[1:])
+    dims = _lib.dims_array(sp)
+    n = _lib.load().advchain_components_workspace(N, len(sp), dims)
+    if n < 0:
+        raise NotImplementedError("%s: N=%d, spatial shape %s is too large (more than 2^31 - 1 voxels in an entry, or a workspace "
+                                  "of more than 2^31 - 1 words)" % (name, N, sp))
+    return labels, N, sp, dims, torch.empty(int(n), device=labels.device, dtype=torch.int32)
+
+
+def _components_check(rc, what):
+    if rc == -2:
+        raise NotImplementedError("%s: %s" % (what, _lib.load().advchain_last_error().decode()))
+    _lib.check(rc, what)
+
+
+@_on_tensor_device
+def connected_components(labels, connectivity=1, background=0, num_classes=None, return_sizes=False):
+    """(N,dims) int64 labels -> Components(labels int32 (N,dims), count int64 (N,), sizes int32 (N,dims) or None): the connected
+    components of every entry, numbered from 1 in the order of their smallest voxel (include/advchain_hip.h:
+    advchain_components).  No gradient."""
+    labels, N, sp, dims, ws = _components_workspace("connected_components", labels)
+    out = torch.empty(labels.shape, device=labels.device, dtype=torch.int32)
+    count = torch.empty((N,), device=labels.device, dtype=torch.int64)
+    sizes = torch.empty(labels.shape, device=labels.device, dtype=torch.int32) if return_sizes else None
+    _components_check(_lib.load().advchain_components(_ptr(labels), _ptr(out), _ptr(count), _ptr(sizes), _ptr(ws), N, len(sp), dims,
+                                                      int(connectivity), int(background),
+                                                      -1 if num_classes is None else int(num_classes), _stream()), "components")
+    return Components(out, count, sizes)
+
+
+@_on_tensor_device
+def keep_largest_component(labels, num_classes, connectivity=1, background=0):
+    """(N,dims) int64 labels -> the same with every class but `background` reduced to its largest component per entry
+    (include/advchain_hip.h: advchain_keep_largest).  No gradient."""
+    labels, N, sp, dims, ws = _components_workspace("keep_largest_component", labels)
+    K = int(num_classes)
+    out = torch.empty_like(labels)
+    winners = torch.empty((N, K), device=labels.device, dtype=torch.int64)
+    _components_check(_lib.load().advchain_keep_largest(_ptr(labels), _ptr(out), _ptr(ws), _ptr(winners), N, K, len(sp), dims,
+                                                        int(connectivity), int(background), _stream()), "keep_largest")
+    return out
+
+
+@_on_tensor_device
+def remove_small_components(labels, min_size, connectivity=1, background=0, num_classes=None):
+    """(N,dims) int64 labels -> the same with the components of fewer than min_size voxels set to `background`
+    (include/advchain_hip.h: advchain_remove_small).  No gradient."""
+    labels, N, sp, dims, ws = _components_workspace("remove_small_components", labels)
+    out = torch.empty_like(labels)
+    _components_check(_lib.load().advchain_remove_small(_ptr(labels), _ptr(out), _ptr(ws), N, len(sp), dims, int(connectivity),
+                                                        int(background), -1 if num_classes is None else int(num_classes),
+                                                        int(min_size), _stream()), "remove_small")
+    return out
+
+
 class _Boundary(torch.autograd.Function):
     """1/(N V) sum omega_k softmax(x)_k maps_k over the counted voxels and classes (include/advchain_hip.h:
     advchain_boundary_fwd).  Differentiable w.r.t. the logits; the maps are a constant.  Two launches forward, one backward."""

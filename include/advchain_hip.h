@@ -840,6 +840,37 @@ int advchain_surface_metrics(const int64_t* pred, const int64_t* target, const f
                              int64_t* overlap, float* dice, void* workspace, int64_t N, int64_t K, int ndim,
                              const int64_t* dims, void* stream);
 
+/* ---- connected components of label maps and the filters on them, 2D and 3D (seg_components.hip) -----------------------------
+ * Not in the reference.  labels (N, dims) int64, dims = (H, W) or (D, H, W).  Two voxels of an entry are adjacent when their
+ * offsets differ by at most 1 on every axis and on at most `connectivity` axes (1 .. ndim: scipy's generate_binary_structure);
+ * adjacent voxels are connected when they carry the same label and that label is foreground: not `background` and, with
+ * num_classes >= 0, inside [0, num_classes) (-100 is then background; a negative num_classes means no class count).  Labels are
+ * only compared; keep_largest alone uses one as an index, after that range check.  Components never span entries.  A
+ * label-equivalence union-find: a tile of 2048 voxels is resolved in LDS (each label read once), the tile seams -- edges and
+ * corners included -- are united in global memory with a lock-free atomic minimum, every voxel is pointed at its root, the
+ * smallest linear index (C order, within the entry) of its component.  Integer atomics only, no workgroup waits on another, no
+ * memset, no host read-back: the same bits on every run, capturable on one stream.  ADVCHAIN_ERR_UNSUPPORTED for more than
+ * 2^31 - 1 voxels in an entry or a workspace of more than 2^31 - 1 words.
+ * `workspace` (no clearing needed): advchain_components_workspace 4-byte words, host-only query, -1 where the shape is refused;
+ * with V voxels per entry it is N (2 V + ceil(V / 2048)): parents, sizes, root counts per chunk of 2048 voxels.
+ * advchain_components: out_labels (N, dims) int32: 0 on background, else the number of the voxel's component, 1 .. count[n], the
+ *           components of an entry in the order of their smallest linear index; count (N) int64; sizes (N, dims) int32 or NULL:
+ *           the voxel count of the component of each voxel, 0 on background.                                                 */
+int64_t advchain_components_workspace(int64_t N, int ndim, const int64_t* dims); /* 4-byte words */
+int advchain_components(const int64_t* labels, int32_t* out_labels, int64_t* count, int32_t* sizes, void* workspace, int64_t N,
+                        int ndim, const int64_t* dims, int connectivity, int64_t background, int64_t num_classes, void* stream);
+/* advchain_keep_largest: out (N, dims) int64, not the input: for every entry and class k in [0, K) other than `background`, a voxel
+ *           of class k outside the largest component of class k of its entry becomes `background`; ties go to the component
+ *           with the smaller smallest linear index (one 64-bit atomic maximum of (size << 32) | (2^32 - 1 - root) per class);
+ *           every other voxel, labels outside [0, K) included, is copied.  `winners`: N K 8-byte words, 8-byte aligned, no
+ *           clearing needed.  K in 1 .. 65535.                                                                              */
+int advchain_keep_largest(const int64_t* labels, int64_t* out, void* workspace, void* winners, int64_t N, int64_t K, int ndim,
+                          const int64_t* dims, int connectivity, int64_t background, void* stream);
+/* advchain_remove_small: out (N, dims) int64, not the input: the voxels of components of fewer than min_size (>= 1) voxels become
+ *           `background`, every other voxel is copied -- also a label that num_classes makes background: it is in no component. */
+int advchain_remove_small(const int64_t* labels, int64_t* out, void* workspace, int64_t N, int ndim, const int64_t* dims,
+                          int connectivity, int64_t background, int64_t num_classes, int64_t min_size, void* stream);
+
 /* ---- boundary (surface) loss, 2D and 3D (seg_boundary.hip) -----------------------------------------------------------------
  * Not in the reference (Kervadec et al.).  logits (N,K,dims) fp32 (logits_bf16 = 0) or bf16 (1), maps (N,K,dims) fp32 signed
  * distance maps (a constant), p = softmax over K inside the kernel:
