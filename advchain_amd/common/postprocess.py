@@ -1,5 +1,5 @@
 """Post-processing of label maps on the device (not in the reference; csrc/seg_components.hip): ``connected_components``,
-``keep_largest_component``, ``remove_small_components`` -- the step between ``argmax`` and
+``keep_largest_component``, ``remove_small_components``, ``fill_holes``, ``find_holes`` -- the step between ``argmax`` and
 ``common.metrics.surface_distance_metrics`` in a validation loop.
 
 Definitions.  labels is an int64 label map (N, dims), dims = (H, W) or (D, H, W).
@@ -20,12 +20,27 @@ binary mask in the same order; here all label values of an entry share one numbe
 Largest component.  For entry n and class k the largest component is the one with the most voxels; among equals the one with the
 smaller smallest linear index.
 
+Holes (``fill_holes``, ``find_holes``: scipy.ndimage.binary_fill_holes per class, MONAI's FillHoles as its docstring has it).
+Here ``connectivity`` is the adjacency OF THE BACKGROUND, scipy's ``structure`` argument; the default 1 is scipy's.  A background
+component is a class of the transitive closure of "adjacent and both equal to ``background``", within one entry.  It touches
+the border when one of its voxels has a coordinate equal to 0 or to size - 1 on any spatial axis.  Its enclosing labels are the
+labels of all voxels that are adjacent, under the same connectivity, to a voxel of the component and are not ``background``.  A
+hole is a background component that does not touch the border and whose enclosing labels are all one value k with 0 <= k < K =
+``num_classes``: its voxels become k.  A component enclosed by two different labels stays background ("enclosed by a single
+class"), and so does one adjacent to a label outside [0, K) (-100, K + 3).  Every voxel that is not background is copied
+unchanged, labels outside [0, K) included.  With ``max_size`` = m only holes of at most m voxels are filled (skimage's
+remove_small_holes).  Consequences: for a map with values in {0, 1}, K = 2 and background 0 the result is
+scipy.ndimage.binary_fill_holes(mask, structure=generate_binary_structure(ndim, connectivity)) per entry; the result depends on
+the map alone, not on any processing order; fill_holes(fill_holes(x)) == fill_holes(x).  MONAI's implementation, unlike its
+docstring, floods ``img != label`` from the border once per label: it overwrites other classes that lie inside a class and
+depends on the order of the labels.  That is not reproduced.
+
 Every value is an integer and the same bits on every run; nothing is read back to the host, and every call can be captured in a
 graph.  There is no gradient: the input is detached."""
 import torch
 
 from .. import ops
-from ..ops import Components  # noqa: F401
+from ..ops import Components, Holes  # noqa: F401
 from .loss import _check_num_classes, _require_gpu
 
 
@@ -80,3 +95,32 @@ def remove_small_components(labels, min_size, connectivity=1, background=0, num_
     _require_gpu(labels, "labels")
     return ops.remove_small_components(labels, min(min_size, 2 ** 62), connectivity=connectivity, background=background,
                                        num_classes=num_classes)
+
+
+def _check_holes(name, labels, num_classes, connectivity, background, max_size):
+    _check_labels(name, labels, connectivity, background)
+    _check_num_classes(name, num_classes)
+    if max_size is not None and (isinstance(max_size, bool) or not isinstance(max_size, int) or max_size < 1):
+        raise ValueError("%s: max_size must be None or a positive integer, got %r" % (name, max_size))
+    _require_gpu(labels, "labels")
+    return None if max_size is None else min(max_size, 2 ** 62)
+
+
+def fill_holes(labels, num_classes, connectivity=1, background=0, max_size=None):
+    """int64 (N, dims): the voxels of every hole -- a component of ``background`` under ``connectivity`` that does not touch the
+    border of its entry and whose enclosing labels are all one class k in [0, num_classes) -- become k; with ``max_size`` only
+    holes of at most that many voxels.  Every other voxel is copied unchanged (definitions: the module's docstring).  Equal to
+    ``torch.where(h.fill >= 0, h.fill, labels)`` with h = find_holes(...)."""
+    max_size = _check_holes("fill_holes", labels, num_classes, connectivity, background, max_size)
+    return ops.fill_holes(labels, num_classes, connectivity=connectivity, background=background, max_size=max_size)
+
+
+def find_holes(labels, num_classes, connectivity=1, background=0, max_size=None):
+    """What fill_holes would fill, and a quality report ("the model left 14 holes in class 2").  Returns Holes, a namedtuple of
+    device tensors:
+
+        fill    (N, dims)  int64   the class a voxel would be filled with, -1 where nothing is filled
+        count   (N, K)     int64   holes filled, per entry and enclosing class
+        voxels  (N, K)     int64   voxels filled, per entry and enclosing class"""
+    max_size = _check_holes("find_holes", labels, num_classes, connectivity, background, max_size)
+    return ops.find_holes(labels, num_classes, connectivity=connectivity, background=background, max_size=max_size)

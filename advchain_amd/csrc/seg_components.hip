@@ -3,6 +3,7 @@
 //   advchain_components      <- common.postprocess.connected_components
 //   advchain_keep_largest    <- common.postprocess.keep_largest_component
 //   advchain_remove_small    <- common.postprocess.remove_small_components
+//   advchain_fill_holes      <- common.postprocess.fill_holes, find_holes
 //
 // Two voxels of an entry are adjacent when their offsets differ by at most 1 on every axis and on at most `connectivity` axes
 // (scipy's generate_binary_structure); adjacent voxels are connected when they carry the same label and that label is
@@ -22,6 +23,9 @@
 //   k_cc_gather    labels and sizes of the root to every voxel.
 //   k_cc_winner    per (entry, class) the 64-bit maximum of (size << 32) | ~root: the largest component, ties to the earlier.
 //   k_cc_keep, k_cc_small   the filtered copies of the input.
+//   k_hole_enclose, k_hole_fill   fill_holes: k_cc_tile, k_cc_seam and k_cc_flatten label the background instead (HOLES), then per
+//                  background component the smallest and largest code of what encloses it, then the filled copy and the counts
+//                  (see "hole filling" below).
 // Invariant of the union-find: parent[x] <= x in every state a thread can observe (a parent is only ever lowered, by an atomic
 // minimum, to the index of a voxel of the same component), so a walk towards the root moves to a strictly smaller index each
 // step and ends after fewer steps than there are voxels.  No kernel waits on a value that another workgroup writes.  Integer
@@ -47,7 +51,11 @@ struct Shape {
   int conn;            // 1 .. ndim
 };
 
+// HOLES: the passes label the background instead (advchain_fill_holes): the voxels equal to `background` are the ones united, K
+// is not looked at.  They all carry one label, so the equality tests that unite runs and pairs are the same.
+template <bool HOLES>
 __device__ __forceinline__ bool foreground(int64_t y, int64_t background, int64_t K) {
+  if (HOLES) return y == background;
   return y != background && (K < 0 || (y >= 0 && y < K));
 }
 
@@ -81,15 +89,22 @@ __device__ __forceinline__ void uf_unite(int* parent, int a, int b) {
 // ---- tile pass ----------------------------------------------------------------------------------------------------------------
 // blockIdx.x = ((n tiles_z + z tile) tiles_y + y tile) tiles_x + x tile.  The local index (lz TY + ly) 64 + lx orders the voxels
 // of a tile as their linear indices do, so the smallest local index of a component is its smallest linear index in the tile.
+// HOLES: `winners` and `winners2` are the hole counts and voxel counts (zeroed here), and `state` gets the empty enclosure state
+// (smallest code INT_MAX, largest code -1) at every tile-local root: the root of a component is the tile-local root of its tile.
+template <bool HOLES>
 __global__ void __launch_bounds__(kBlock)
 k_cc_tile(const int64_t* __restrict__ labels, int* __restrict__ parent, int* __restrict__ sizes, u64* __restrict__ winners,
-          int64_t NK, int64_t background, int64_t K, Shape s, int tiles_z, int tiles_y, int tiles_x) {
+          u64* __restrict__ winners2, int* __restrict__ state, int64_t NK, int64_t background, int64_t K, Shape s, int tiles_z,
+          int tiles_y, int tiles_x) {
   __shared__ int64_t lab[kTileVox];
   __shared__ int par[kTileVox];
   __shared__ int cnt[kTileVox];
   if (winners) {                                           // (keep_largest: the maxima of k_cc_winner start at 0)
     const int64_t threads = (int64_t)gridDim.x * kBlock;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < NK; i += threads) winners[i] = 0ull;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < NK; i += threads) {
+      winners[i] = 0ull;
+      if (HOLES) winners2[i] = 0ull;
+    }
   }
   int64_t b = blockIdx.x;
   const int bx = (int)(b % tiles_x); b /= tiles_x;
@@ -105,14 +120,15 @@ k_cc_tile(const int64_t* __restrict__ labels, int* __restrict__ parent, int* __r
     const int lx = i & (kTileX - 1), ly = (i / kTileX) & (s.TY - 1), lz = i / sz;
     const int z = z0 + lz, y = y0 + ly, x = x0 + lx;
     const bool in = z < s.D && y < s.H && x < s.W;
-    const int64_t v = in ? labels[n * V + ((int64_t)z * s.H + y) * s.W + x] : background;
+    // (outside the image: a label that is in no component, whichever label the passes unite)
+    const int64_t v = in ? labels[n * V + ((int64_t)z * s.H + y) * s.W + x] : (HOLES ? ~background : background);
     lab[i] = v;
     // a wave holds one tile row: a voxel starts below the first voxel of its run of equal labels in the row (lane lx), which
     // is the union of the run without an atomic
     const int64_t left = __shfl_up(v, 1, 64);                                            // (every lane takes part: not behind ||)
     const u64 heads = __ballot(lx == 0 || left != v);
     const int start = 63 - __clzll(heads & ((2ull << lx) - 1ull));                       // (bit 0 is set: lane 0 is a head)
-    par[i] = (in && foreground(v, background, K)) ? i - lx + start : -1;
+    par[i] = (in && foreground<HOLES>(v, background, K)) ? i - lx + start : -1;
     cnt[i] = 0;
   }
   __syncthreads();
@@ -162,6 +178,10 @@ k_cc_tile(const int64_t* __restrict__ labels, int* __restrict__ parent, int* __r
     }
     parent[at] = r;
     if (sizes) sizes[at] = cnt[i];
+    if (HOLES && root[j] == i) {
+      state[2 * at] = 0x7fffffff;
+      state[2 * at + 1] = -1;
+    }
   }
 }
 
@@ -182,6 +202,7 @@ __device__ __forceinline__ bool low_face(int z, int y, int x, const Shape& s) {
 
 // Every connected pair whose voxels lie in different tiles has a voxel on a low face of its tile (along an axis on which the
 // tiles differ, the voxel with the larger coordinate).  That voxel unites the pair; when both are on a low face, the later one.
+template <bool HOLES>
 __global__ void __launch_bounds__(kBlock)
 k_cc_seam(const int64_t* __restrict__ labels, int* parent, int64_t background, int64_t K, Shape s, int64_t V, int64_t chunks) {
   const Chunked c = chunk_of(chunks);
@@ -193,7 +214,7 @@ k_cc_seam(const int64_t* __restrict__ labels, int* parent, int64_t background, i
     const int x = (int)(v % s.W), y = (int)((v / s.W) % s.H), z = (int)(v / ((int64_t)s.W * s.H));
     if (!low_face(z, y, x, s)) continue;
     const int64_t mine = L[v];
-    if (!foreground(mine, background, K)) continue;
+    if (!foreground<HOLES>(mine, background, K)) continue;
 #pragma unroll 1
     for (int q = s.TZ > 1 ? 0 : 9; q < (s.TZ > 1 ? 27 : 18); ++q) {                     // offsets as in k_cc_tile, all around
       const int dz = q / 9 - 1, dy = (q / 3) % 3 - 1, dx = q % 3 - 1;
@@ -372,6 +393,173 @@ k_cc_small(const int64_t* __restrict__ labels, const int* __restrict__ parent, c
   }
 }
 
+// ---- hole filling -------------------------------------------------------------------------------------------------------------
+// The passes above with HOLES label the background; a hole is a background component that does not touch the border of its entry
+// and whose neighbours that are not background all carry one class k in [0, K).  Per root two words at state[2 root]: the
+// smallest and the largest code seen, kept with atomic minimum and maximum.  The code of a class label is the label; a voxel on a
+// face of the entry and a neighbouring label outside [0, K) give kPoison (above every class index: K <= 65535).  A component is
+// a hole iff both words are equal and in [0, K).
+constexpr int kPoison = 0x10000;
+
+__device__ __forceinline__ int wave_min_int(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ int wave_max_int(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// Every background voxel (parent >= 0: its root, after k_cc_flatten) looks all around it.  A neighbour with a parent is
+// background and needs no label read; the voxels inside the outside component read 4-byte parents only.  The contributions of a
+// wave are reduced per distinct root among its lanes first (the pattern of k_cc_winner): on a real map the outside is one
+// component with hundreds of thousands of contributing voxels.  A lane drops out before that when a relaxed load shows its root
+// as decided "no hole" (poisoned, or two different codes): every later contribution lowers the minimum or raises the maximum,
+// which leaves that decision as it is.  The raw words therefore may differ from run to run; whether they are equal and in
+// [0, K), and their value if so, do not, and k_hole_fill looks at nothing else.
+// One voxel per thread, blockIdx.x = n rows + row of kBlock voxels, and the neighbourhood (ND axes, CONN) unrolled at compile
+// time: a voxel's work is a chain of dependent accesses (its parent, its neighbours' parents, their labels, the root's state).
+// Eight voxels per thread in turn, each neighbour in turn, left one wave per SIMD waiting on every access; now the parents of
+// all neighbours are one batch of loads and the labels of those that are not background a second one (a background neighbour
+// re-reads the voxel's own label instead, the line is there: no branch between the loads).
+template <int ND, int CONN>
+__global__ void __launch_bounds__(kBlock)
+k_hole_enclose(const int64_t* __restrict__ labels, const int* __restrict__ parent, int* state, int64_t K, Shape s, int64_t V,
+               int64_t rows) {
+  constexpr int kFirst = ND == 3 ? 0 : 9, kLast = ND == 3 ? 27 : 18;                      // offsets as in k_cc_seam
+  const int64_t n = blockIdx.x / rows;
+  const int64_t* L = labels + n * V;
+  const int* P = parent + n * V;
+  int* S = state + 2 * n * V;
+  const int lane = threadIdx.x & 63;
+  const int64_t HW = (int64_t)s.H * s.W;
+  {
+    const int64_t v = (blockIdx.x - n * rows) * kBlock + threadIdx.x;                     // (no early exit: the ballots need every lane)
+    const int r = v < V ? P[v] : -1;
+    int lo = 0x7fffffff, hi = -1;
+    if (r >= 0) {
+      const u32 row = (u32)v / (u32)s.W;                                                  // (v < V < 2^31: 32-bit divisions)
+      const int x = (int)((u32)v - row * (u32)s.W), y = (int)(row % (u32)s.H), z = (int)(row / (u32)s.H);
+      if (x == 0 || x == s.W - 1 || y == 0 || y == s.H - 1 || (ND == 3 && (z == 0 || z == s.D - 1))) {
+        lo = hi = kPoison;
+      } else {                                                                            // (every neighbour is inside the entry)
+        int pu[27];
+        bool any = false;
+#pragma unroll
+        for (int q = kFirst; q < kLast; ++q) {
+          const int dz = q / 9 - 1, dy = (q / 3) % 3 - 1, dx = q % 3 - 1;
+          if (q == 13 || (dz != 0) + (dy != 0) + (dx != 0) > CONN) continue;
+          pu[q] = P[v + dz * HW + dy * s.W + dx];
+          any |= pu[q] < 0;
+        }
+        if (any) {
+          int64_t t[27];
+#pragma unroll
+          for (int q = kFirst; q < kLast; ++q) {
+            const int dz = q / 9 - 1, dy = (q / 3) % 3 - 1, dx = q % 3 - 1;
+            if (q == 13 || (dz != 0) + (dy != 0) + (dx != 0) > CONN) continue;
+            t[q] = L[pu[q] < 0 ? v + dz * HW + dy * s.W + dx : v];
+          }
+#pragma unroll
+          for (int q = kFirst; q < kLast; ++q) {
+            const int dz = q / 9 - 1, dy = (q / 3) % 3 - 1, dx = q % 3 - 1;
+            if (q == 13 || (dz != 0) + (dy != 0) + (dx != 0) > CONN) continue;
+            const int code = t[q] >= 0 && t[q] < K ? (int)t[q] : kPoison;
+            lo = min(lo, pu[q] < 0 ? code : 0x7fffffff);
+            hi = max(hi, pu[q] < 0 ? code : -1);
+          }
+        }
+      }
+    }
+    if (hi >= 0) {
+      // every lane looks at its root's state first, all lanes at once (inside the turns below the loads would follow one another):
+      // it has nothing to offer when the root is decided, or when its codes lie between the two words -- they only move outwards
+      const int seen_lo = __hip_atomic_load(S + 2 * (int64_t)r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const int seen_hi = __hip_atomic_load(S + 2 * (int64_t)r + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (seen_hi >= kPoison || seen_lo < seen_hi || (lo >= seen_lo && hi <= seen_hi)) hi = -1;
+    }
+    u64 todo = __ballot(hi >= 0);
+    while (todo) {                                                                        // one turn per root: todo loses bits
+      const int r1 = __shfl(r, __builtin_ctzll(todo), 64);
+      const bool same = hi >= 0 && r == r1;
+      const u64 group = __ballot(same);
+      int mn = lo, mx = hi;
+      if (group & (group - 1ull)) {                                                       // (uniform; a single lane offers its own)
+        mn = wave_min_int(same ? lo : 0x7fffffff);
+        mx = wave_max_int(same ? hi : -1);
+      }
+      if (lane == __builtin_ctzll(todo)) {
+        atomicMin(S + 2 * (int64_t)r1, mn);
+        atomicMax(S + 2 * (int64_t)r1 + 1, mx);
+      }
+      todo &= ~group;
+    }
+  }
+}
+
+// out: the filled copy; fill: the class a voxel is filled with, -1 elsewhere.  A root that is filled adds 1 and its size to
+// count[n][k] and voxels[n][k] (zeroed by k_cc_tile): the roots of one class in a wave together, and those of the first class that
+// turns up in the workgroup (on most maps the only one) summed in LDS and added once per workgroup -- a map of specks has tens of
+// thousands of holes per entry, all of one class, and their adds would queue on one word.
+__global__ void __launch_bounds__(kBlock)
+k_hole_fill(const int64_t* __restrict__ labels, const int* __restrict__ parent, const int* __restrict__ sizes,
+            const int* __restrict__ state, int64_t* __restrict__ out, int64_t* __restrict__ fill, u64* __restrict__ count,
+            u64* __restrict__ voxels, int64_t K, int64_t max_size, int64_t V, int64_t chunks) {
+  __shared__ int first_k;
+  __shared__ u64 first_count, first_voxels;
+  const Chunked c = chunk_of(chunks);
+  const int64_t e = c.n * V;
+  const int lane = threadIdx.x & 63;
+  if (threadIdx.x == 0) {
+    first_k = -1;
+    first_count = first_voxels = 0ull;
+  }
+  __syncthreads();
+  for (int j = 0; j < kPerThread; ++j) {
+    if (c.base + j * kBlock >= V) break;                                                  // (uniform)
+    const int64_t v = c.base + j * kBlock + threadIdx.x;
+    const int p = v < V ? parent[e + v] : -1;
+    int k = -1, size = 0;
+    if (p >= 0) {
+      const int lo = state[2 * (e + p)], hi = state[2 * (e + p) + 1];
+      size = sizes[e + p];
+      if (lo == hi && lo >= 0 && lo < K && (max_size < 0 || size <= max_size)) k = lo;
+    }
+    if (v < V) {
+      if (out) out[e + v] = k >= 0 ? (int64_t)k : labels[e + v];
+      if (fill) fill[e + v] = k;
+    }
+    if (!count) continue;                                                                 // (uniform)
+    const bool root = k >= 0 && p == (int)v;
+    u64 todo = __ballot(root);
+    while (todo) {                                                                        // one turn per class
+      const int k1 = __shfl(k, __builtin_ctzll(todo), 64);
+      const u64 same = __ballot(root && k == k1);
+      u64 total = root && k == k1 ? (u64)size : 0ull;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) total += __shfl_xor(total, o, 64);
+      if (lane == 0) {
+        const int held = atomicCAS(&first_k, -1, k1);
+        if (held == -1 || held == k1) {
+          atomicAdd(&first_count, (u64)__popcll(same));
+          atomicAdd(&first_voxels, total);
+        } else {
+          atomicAdd(count + c.n * K + k1, (u64)__popcll(same));
+          atomicAdd(voxels + c.n * K + k1, total);
+        }
+      }
+      todo &= ~same;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && first_k >= 0) {
+    atomicAdd(count + c.n * K + first_k, first_count);
+    atomicAdd(voxels + c.n * K + first_k, first_voxels);
+  }
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------------
 struct Plan {
   Shape s;
@@ -401,22 +589,27 @@ struct Work {
   int* parent;
   int* sizes;
   int* counts;
+  int* state;          // fill_holes only: two words per voxel
 };
 
-// the passes every entry point shares: tile, seam, flatten
-template <bool SIZES>
+// the passes every entry point shares: tile, seam, flatten.  HOLES: of the background; winners2 and the state words (behind the
+// chunk counts in the workspace) as k_cc_tile says.
+template <bool SIZES, bool HOLES = false>
 int components_label(const int64_t* labels, void* workspace, u64* winners, int64_t NK, int64_t N, const Plan& p,
-                     int64_t background, int64_t K, Work* w, hipStream_t st) {
+                     int64_t background, int64_t K, Work* w, hipStream_t st, u64* winners2 = nullptr) {
   w->parent = (int*)workspace;
   w->sizes = w->parent + N * p.V;
   w->counts = w->sizes + N * p.V;
+  w->state = HOLES ? w->counts + N * p.chunks : nullptr;
   const int64_t tiles = N * p.tiles_z * p.tiles_y * p.tiles_x;           // at most N V
   const unsigned chunked = (unsigned)(N * p.chunks);
-  hipLaunchKernelGGL(k_cc_tile, dim3((unsigned)tiles), dim3(kBlock), 0, st, labels, w->parent, SIZES ? w->sizes : (int*)nullptr,
-                     winners, NK, background, K, p.s, (int)p.tiles_z, (int)p.tiles_y, (int)p.tiles_x);
+  hipLaunchKernelGGL((k_cc_tile<HOLES>), dim3((unsigned)tiles), dim3(kBlock), 0, st, labels, w->parent,
+                     SIZES ? w->sizes : (int*)nullptr, winners, winners2, w->state, NK, background, K, p.s, (int)p.tiles_z,
+                     (int)p.tiles_y, (int)p.tiles_x);
   ADVCHAIN_LAUNCH_CHECK();
   if (p.tiles_z * p.tiles_y * p.tiles_x > 1) {
-    hipLaunchKernelGGL(k_cc_seam, dim3(chunked), dim3(kBlock), 0, st, labels, w->parent, background, K, p.s, p.V, p.chunks);
+    hipLaunchKernelGGL((k_cc_seam<HOLES>), dim3(chunked), dim3(kBlock), 0, st, labels, w->parent, background, K, p.s, p.V,
+                       p.chunks);
     ADVCHAIN_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(k_cc_flatten<SIZES>, dim3(chunked), dim3(kBlock), 0, st, w->parent, w->sizes, w->counts, p.V, p.chunks);
@@ -503,6 +696,42 @@ int advchain_remove_small(const int64_t* labels, int64_t* out, void* workspace, 
   if (rc != ADVCHAIN_OK) return rc;
   hipLaunchKernelGGL(k_cc_small, dim3((unsigned)(N * p.chunks)), dim3(kBlock), 0, st, labels, (const int*)w.parent,
                      (const int*)w.sizes, out, background, min_size, p.V, p.chunks);
+  ADVCHAIN_LAUNCH_CHECK();
+  return ADVCHAIN_OK;
+}
+
+int64_t advchain_fill_holes_workspace(int64_t N, int ndim, const int64_t* dims) {
+  Plan p;
+  return components_plan(N, ndim, dims, &p) ? p.total + 2 * N * p.V : -1;
+}
+
+int advchain_fill_holes(const int64_t* labels, int64_t* out, int64_t* fill, int64_t* count, int64_t* voxels, void* workspace,
+                        int64_t N, int64_t K, int ndim, const int64_t* dims, int connectivity, int64_t background,
+                        int64_t max_size, void* stream) {
+  ADVCHAIN_CHECK_ARG(labels && workspace, "fill_holes: null pointer");
+  ADVCHAIN_CHECK_ARG((count == nullptr) == (voxels == nullptr), "fill_holes: count and voxels must be null together");
+  ADVCHAIN_CHECK_ARG(out || fill || count, "fill_holes: no output");
+  ADVCHAIN_CHECK_ARG(labels != out && labels != fill, "fill_holes: out and fill must not be the input");
+  ADVCHAIN_CHECK_ARG((((uintptr_t)count | (uintptr_t)voxels) & 7) == 0, "fill_holes: count and voxels must be 8-byte aligned");
+  ADVCHAIN_CHECK_ARG(K >= 1 && K <= 65535, "fill_holes: K must be in 1..65535");
+  ADVCHAIN_CHECK_ARG(max_size != 0, "fill_holes: max_size must be at least 1, or negative for none");
+  COMPONENTS_CHECK_SHAPE("fill_holes");
+  ADVCHAIN_CHECK_ARG(N <= ((int64_t)1 << 39) / K, "fill_holes: bad N");
+  Work w;
+  const int rc = components_label<true, true>(labels, workspace, (u64*)count, count ? N * K : 0, N, p, background, K, &w, st,
+                                              (u64*)voxels);
+  if (rc != ADVCHAIN_OK) return rc;
+  const unsigned chunked = (unsigned)(N * p.chunks);
+  const int64_t rows = (p.V + kBlock - 1) / kBlock;                                       // (N rows <= N V: fits one launch)
+  void (*enclose)(const int64_t*, const int*, int*, int64_t, Shape, int64_t, int64_t) =
+      ndim == 2 ? (connectivity == 1 ? k_hole_enclose<2, 1> : k_hole_enclose<2, 2>)
+                : (connectivity == 1 ? k_hole_enclose<3, 1> : connectivity == 2 ? k_hole_enclose<3, 2> : k_hole_enclose<3, 3>);
+  hipLaunchKernelGGL(enclose, dim3((unsigned)(N * rows)), dim3(kBlock), 0, st, labels, (const int*)w.parent, w.state, K, p.s, p.V,
+                     rows);
+  ADVCHAIN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_hole_fill, dim3(chunked), dim3(kBlock), 0, st, labels, (const int*)w.parent, (const int*)w.sizes,
+                     (const int*)w.state, out, fill, (u64*)count, (u64*)voxels, K, max_size < 0 ? (int64_t)-1 : max_size, p.V,
+                     p.chunks);
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
 }

@@ -2308,6 +2308,45 @@ def remove_small_components(labels, min_size, connectivity=1, background=0, num_
     return out
 
 
+Holes = collections.namedtuple("Holes", ["fill", "count", "voxels"])
+
+
+def _fill_holes(name, labels, num_classes, connectivity, background, max_size, want_out, want_report):
+    labels = _dev_labels(labels.detach() if isinstance(labels, torch.Tensor) else labels, "labels")
+    N, sp = labels.shape[0], tuple(labels.shape[1:])
+    dims = _lib.dims_array(sp)
+    lib = _lib.load()
+    n = lib.advchain_fill_holes_workspace(N, len(sp), dims)
+    if n < 0:
+        raise NotImplementedError("%s: N=%d, spatial shape %s is too large (more than 2^31 - 1 voxels in an entry, or a "
+                                  "components workspace of more than 2^31 - 1 words)" % (name, N, sp))
+    ws = torch.empty(int(n), device=labels.device, dtype=torch.int32)
+    K = int(num_classes)
+    out = torch.empty_like(labels) if want_out else None
+    fill = torch.empty_like(labels) if want_report else None
+    count = torch.empty((N, K), device=labels.device, dtype=torch.int64) if want_report else None
+    voxels = torch.empty((N, K), device=labels.device, dtype=torch.int64) if want_report else None
+    _components_check(lib.advchain_fill_holes(_ptr(labels), _ptr(out), _ptr(fill), _ptr(count), _ptr(voxels), _ptr(ws), N, K,
+                                              len(sp), dims, int(connectivity), int(background),
+                                              -1 if max_size is None else int(max_size), _stream()), "fill_holes")
+    return out, Holes(fill, count, voxels)
+
+
+@_on_tensor_device
+def fill_holes(labels, num_classes, connectivity=1, background=0, max_size=None):
+    """(N,dims) int64 labels -> the same with every hole -- a component of `background` that does not touch the border of its entry
+    and is enclosed by one class in [0, num_classes) -- set to that class (include/advchain_hip.h: advchain_fill_holes).  No
+    gradient."""
+    return _fill_holes("fill_holes", labels, num_classes, connectivity, background, max_size, True, False)[0]
+
+
+@_on_tensor_device
+def find_holes(labels, num_classes, connectivity=1, background=0, max_size=None):
+    """(N,dims) int64 labels -> Holes(fill int64 (N,dims): the class a voxel would be filled with, -1 elsewhere; count, voxels
+    int64 (N,K): the holes and their voxels per entry and enclosing class).  No gradient."""
+    return _fill_holes("find_holes", labels, num_classes, connectivity, background, max_size, False, True)[1]
+
+
 class _Boundary(torch.autograd.Function):
     """1/(N V) sum omega_k softmax(x)_k maps_k over the counted voxels and classes (include/advchain_hip.h:
     advchain_boundary_fwd).  Differentiable w.r.t. the logits; the maps are a constant.  Two launches forward, one backward."""

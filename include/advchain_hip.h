@@ -870,6 +870,23 @@ int advchain_keep_largest(const int64_t* labels, int64_t* out, void* workspace, 
  *           `background`, every other voxel is copied -- also a label that num_classes makes background: it is in no component. */
 int advchain_remove_small(const int64_t* labels, int64_t* out, void* workspace, int64_t N, int ndim, const int64_t* dims,
                           int connectivity, int64_t background, int64_t num_classes, int64_t min_size, void* stream);
+/* advchain_fill_holes: the same passes label the BACKGROUND: a background component is a class of the transitive closure of
+ *           "adjacent under `connectivity` and both equal to `background`" within an entry.  It touches the border when one of
+ *           its voxels has a coordinate 0 or size - 1 on a spatial axis; its enclosing labels are those of the voxels adjacent
+ *           (same connectivity) to one of its voxels that are not `background`.  A hole is a background component that does not
+ *           touch the border, whose enclosing labels are all one value k in [0, K), and, with max_size >= 1, that has at most
+ *           max_size voxels (max_size < 0: no limit; 0 is refused).  A component enclosed by two labels, or adjacent to a label
+ *           outside [0, K), stays.  out (N, dims) int64 or NULL: the input with the voxels of every hole set to its k, every
+ *           other voxel copied; fill (N, dims) int64 or NULL: k on the voxels of a hole, -1 elsewhere; neither is the input.
+ *           count, voxels (N, K) int64, 8-byte aligned, NULL together, no clearing needed: the holes filled and their voxels
+ *           per entry and enclosing class.  At least one output.  K in 1 .. 65535.  Per root a smallest and a largest enclosing
+ *           code kept by integer atomic minimum and maximum, one turn per distinct root of a wave.
+ * `workspace`: advchain_fill_holes_workspace 4-byte words, -1 exactly where advchain_components_workspace is: that workspace
+ *           and 2 N V words of enclosure state.                                                                               */
+int64_t advchain_fill_holes_workspace(int64_t N, int ndim, const int64_t* dims); /* 4-byte words */
+int advchain_fill_holes(const int64_t* labels, int64_t* out, int64_t* fill, int64_t* count, int64_t* voxels, void* workspace,
+                        int64_t N, int64_t K, int ndim, const int64_t* dims, int connectivity, int64_t background,
+                        int64_t max_size, void* stream);
 
 /* ---- boundary (surface) loss, 2D and 3D (seg_boundary.hip) -----------------------------------------------------------------
  * Not in the reference (Kervadec et al.).  logits (N,K,dims) fp32 (logits_bf16 = 0) or bf16 (1), maps (N,K,dims) fp32 signed
