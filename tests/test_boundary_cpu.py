@@ -1,7 +1,9 @@
 """distance_transform_edt / signed_distance_maps / boundary_loss of common.loss without a GPU: the public names and signatures,
 the brute-force forms of tests/edt_forms.py against scipy, against plain loops and against autograd (the formulas the kernels
 implement), what fp32 arithmetic reaches at the cases of tests/test_boundary_gpu.py, the host-side argument checks of the Python
-layer and of the C entries, and no CPU path."""
+layer and of the C entries, and no CPU path.  For the edge cases of tests/test_edt_edges_gpu.py: that each takes the dispatch
+branch it is listed for (by edt_plan, the plain-Python mirror of the host loops of csrc/edt.hip), that together the cases run
+every tile width, that no pattern leaves a trivial answer, what fp32 reaches there, and where the entries stop accepting."""
 import ctypes
 import inspect
 import warnings
@@ -9,9 +11,11 @@ import warnings
 import pytest
 import torch
 
-from tests.edt_forms import (EDT_PATTERNS, EDT_SHAPES, LOSS_SHAPES, SAMPLING, SAMPLING_TOL, boundary_closed, boundary_gradient,
-                             boundary_loop, boundary_scale, edt_brute, gate_of, label_case, loss_case, loss_weights, mask_pattern,
-                             omega_of, signed_maps_brute)
+from tests.edt_forms import (EDGE_EDT_CASES, EDGE_EDT_LIMITS, EDGE_MAP_CASES, EDGE_MAP_LIMITS, EDGE_SURFACE_CASES, EDT_PATTERNS,
+                             EDT_SHAPES, LOSS_SHAPES, MAP_CASES, SAMPLING, SAMPLING_TOL, boundary_closed, boundary_gradient,
+                             boundary_loop, boundary_scale, edge_case_id, edge_edt_reference, edge_label_case, edge_surface_pair,
+                             edt_axis_passes, edt_brute, edt_case_plan, edt_plan, gate_of, label_case, loss_case, loss_weights,
+                             mask_pattern, omega_of, signed_maps_brute)
 
 E = inspect.Parameter.empty
 
@@ -287,3 +291,151 @@ def test_c_entries_reject_bad_arguments_on_the_host():
         assert rc < 0, (i, word)
         assert word in lib.advchain_last_error(), (i, word, lib.advchain_last_error())
     assert edt(dims=_lib.dims_array((8, 40000))) == -2 and maps(dims=_lib.dims_array((9000, 8))) == -2
+
+
+# ---- the edge cases of tests/test_edt_edges_gpu.py -------------------------------------------------------------------------------
+
+def test_the_plan_mirror_at_the_figures_of_the_source():
+    """edt_plan against the numbers the header of csrc/edt.hip and its constants give by hand."""
+    assert edt_plan(70, 300, 12, 70, 1)[:3] == (2, 1024, 1)                 # the largest K * chunks of the older tests: 600
+    assert edt_plan(1900, 70, 3, 1900, 2)[:3] == (30, 68, 2)
+    assert edt_plan(32767, 5, 2, 32767, 2)[:3] == (512, 4, 2)
+    assert edt_plan(32767, 4, 2, 32767, 2)[2] == 1 and edt_plan(64, 2048, 2, 64, 1)[:3] == (1, 2048, 1)
+    for L, TX in ((64, 64), (65, 32), (128, 32), (129, 16), (1024, 16), (1025, 8), (2048, 8), (2049, 4), (4096, 4), (4097, 2),
+                  (8192, 2), (8193, 1), (16384, 1)):                           # one field, lines wide apart
+        assert edt_plan(64, 1, L, 4096, 1)[3] == TX, L
+        if L % 2 == 0:
+            assert edt_plan(64, 1, L // 2, 4096, 2)[3] == TX, L               # two fields: every limit half as long
+    for I, TX in ((1, 1), (2, 2), (3, 4), (4, 4), (5, 8), (8, 8), (9, 16), (16, 16), (17, 32), (32, 32), (33, 64)):
+        assert edt_plan(64, 1, 8, I, 1)[3] == TX, I                           # the loop that narrows because TX / 2 >= I
+    assert edt_plan(2, 1, 16384, 2, 1)[3:] == (1, 65536) and edt_plan(2, 2, 8192, 2, 2)[3:] == (1, 65536)
+
+
+ALL_EDGE = [(1, c[0], c[2], 1) for c in EDGE_EDT_CASES] + [(c[0], c[1], c[2], 2) for c in EDGE_MAP_CASES] + \
+           [(c[0], c[1], c[2], 1) for c in EDGE_SURFACE_CASES]
+
+
+@pytest.mark.parametrize("K,shape,claim,NF", ALL_EDGE, ids=["%s-nf%d" % (edge_case_id((K, sh)), nf) for K, sh, _, nf in ALL_EDGE])
+def test_edge_cases_take_the_branch_they_are_listed_for(K, shape, claim, NF):
+    plan = edt_case_plan(K, shape[1:], NF)
+    assert claim, shape
+    for key, want in claim.items():
+        assert plan[key] == want, (shape, key, plan)
+
+
+def test_edge_case_lists_hold_every_branch_they_are_there_for():
+    plans = {c[0]: edt_case_plan(1, c[0][1:], 1) for c in EDGE_EDT_CASES}
+    maps = {(c[0], c[1]): edt_case_plan(c[0], c[1][1:], 2) for c in EDGE_MAP_CASES}
+    assert sorted({p["TX"] for p in plans.values()} & {8, 4, 2, 1}) == [1, 2, 4, 8]
+    assert sorted({p["TX"] for p in maps.values()} & {8, 2, 1}) == [1, 2, 8]
+    assert all(plans[s]["lds"] == 65536 or plans[s]["chunks"] == 512 for s in EDGE_EDT_LIMITS)
+    assert plans[(1, 16384, 2)]["lds"] == 65536 and maps[(2, (1, 8192, 2))]["lds"] == 65536
+    assert all(case in maps for case in EDGE_MAP_LIMITS)
+    assert sum(p["launches"] == 2 for p in maps.values()) == 2
+    assert any(p["chunks"] > 4 and p["chunks"] % 4 for p in plans.values()) and any(p["chunks"] > 8 for p in plans.values())
+    assert any(s[-1] % 64 == 0 and s[-1] > 64 for s in plans) and any(s[-1] == 64 for s in plans)     # rows without a tail
+    assert all(any(s[1 + a] == 1 for s in plans if len(s) == 1 + nd) for nd in (2, 3) for a in range(nd))   # every axis 1-wide
+    assert edt_case_plan(300, (3, 400), 1)["launches"] == 2 and all(p["launches"] == 1 for p in plans.values())
+
+
+def test_old_and_edge_cases_together_run_every_tile_width():
+    """AXIS_FINISH at every TX from 64 down to 1, AXIS_FINISH_SIGNED at 32, 8, 2 and 1 at least, and AXIS_PLAIN (the second pass
+    of a 3D call) at 64, 8 and 1."""
+    finish = {edt_case_plan(1, s[1:], 1)["TX"] for s in EDT_SHAPES + [c[0] for c in EDGE_EDT_CASES]}
+    assert finish == {64, 32, 16, 8, 4, 2, 1}, finish
+    signed = {edt_case_plan(K, s[1:], 2)["TX"] for K, s in MAP_CASES + [(c[0], c[1]) for c in EDGE_MAP_CASES]}
+    assert signed >= {32, 8, 2, 1}, signed
+    plain = {edt_case_plan(1, c[0][1:], 1)["plain_TX"] for c in EDGE_EDT_CASES if len(c[0]) == 4}
+    assert plain >= {64, 8, 1}, plain
+    assert all(L >= 1 and I >= 1 for c in EDGE_EDT_CASES for L, I in edt_axis_passes(c[0][1:]))
+
+
+@pytest.mark.parametrize("case", EDGE_EDT_CASES, ids=[edge_case_id(c) for c in EDGE_EDT_CASES])
+def test_no_pattern_of_an_edge_case_has_a_trivial_answer(case):
+    """Every (case, pattern) has an entry whose answer is neither all zero nor all infinite -- but for the single voxel, whose
+    answer is one or the other: its two patterns give both."""
+    shape, patterns = case[0], case[1]
+    assert patterns
+    if shape == (1, 1, 1):
+        assert float(edge_edt_reference(shape, "one_corner")[1][0]) == 0.0
+        assert float(edge_edt_reference(shape, "full_entry")[1][0]) == float("inf")
+        return
+    for name in patterns:
+        m, sq, _ = edge_edt_reference(shape, name)
+        assert any(bool((e[torch.isfinite(e)] > 0).any()) for e in sq), (shape, name)
+        if name in ("far_left", "far_right") and shape[-1] > 64:
+            assert float(sq[torch.isfinite(sq)].max()) >= (shape[-1] - 1) ** 2
+    if shape == (1, 2, 32767):                                # the farthest squared distance the fields can hold, above 2^24
+        assert float(edge_edt_reference(shape, "far_left")[1].max()) == 32766.0 ** 2
+        assert float(edge_edt_reference(shape, "one_corner")[1].max()) == 32766.0 ** 2 + 1 < 2 ** 30
+
+
+@pytest.mark.parametrize("case", EDGE_MAP_CASES, ids=[edge_case_id(c) for c in EDGE_MAP_CASES])
+def test_label_edge_cases_hold_every_class_and_the_second_group_in_the_middle(case):
+    K, shape = case[0], case[1]
+    y = edge_label_case(K, shape, seed=K)
+    W = shape[-1]
+    group = edt_case_plan(K, shape[1:], 2)["group"]
+    assert bool((y == -100).any()) and bool((y == K + 3).any())
+    for k in range(K):
+        at = torch.nonzero(y == k)
+        assert 0 < at.shape[0] < y.numel(), k
+        if k >= group:                                         # one run of 9 voxels, at least a chunk away from both ends of its row
+            assert at.shape[0] == 9 and int(at[:, -1].min()) >= 64 and int(at[:, -1].max()) < W - 64
+            assert len({tuple(v[:-1].tolist()) for v in at}) == 1 and int(at[:, -1].max() - at[:, -1].min()) == 8
+    if K > group:
+        assert K - group <= 2 and group < K
+
+
+def test_surface_edge_case_holds_the_second_group_in_both_maps():
+    K, shape = EDGE_SURFACE_CASES[0][:2]
+    p, y = edge_surface_pair(K, shape, seed=K)
+    group = edt_case_plan(K, shape[1:], 1)["group"]
+    assert group < K
+    for k in range(group, K):
+        for t in (p, y):
+            x = torch.nonzero(t == k)[:, -1]
+            assert int(((x >= 64) & (x < shape[-1] - 64)).sum()) >= 9, k      # (the random blocks may hold the class elsewhere too)
+        assert not torch.equal(p == k, y == k)
+
+
+@pytest.mark.parametrize("case", EDGE_EDT_CASES, ids=[edge_case_id(c) for c in EDGE_EDT_CASES])
+def test_fp32_stays_inside_the_sampling_bound_at_the_edge_cases(case):
+    """The fp32 evaluation of |S (v - u)| from its definition against float64 at the edge shapes and patterns: inside SAMPLING_TOL
+    on its own (the worst case by its roundings is 2.1e-7 whatever the distance: every bound of the older test's docstring is
+    relative), here at distances up to 0.7 * 32766 and 1.5 * 16383."""
+    shape, patterns = case[0], case[1]
+    s = SAMPLING[len(shape) - 1]
+    worst = 0.0
+    for name in patterns:
+        m, _, want = edge_edt_reference(shape, name)
+        got = edt_brute(m, s, dtype=torch.float32)
+        fin = torch.isfinite(want) & (want > 0)
+        assert torch.equal(torch.isfinite(got), torch.isfinite(want))
+        if bool(fin.any()):
+            worst = max(worst, float(((got - want).abs()[fin] / want[fin]).max()))
+    print("fp32 sampling error at %s: %.3g" % (shape, worst))
+    assert worst <= SAMPLING_TOL
+
+
+def test_the_entries_accept_the_limit_cases_and_refuse_one_voxel_more():
+    from advchain_amd import _lib
+    lib = _lib.load()
+    maps_ws, surface_ws = lib.advchain_signed_maps_workspace, lib.advchain_surface_metrics_workspace
+    for K, shape in EDGE_MAP_LIMITS:
+        N, dims = shape[0], shape[1:]
+        assert maps_ws(N, K, len(dims), _lib.dims_array(dims)) == N * K * 2 * dims[0] * dims[1]
+        assert surface_ws(N, K, len(dims), _lib.dims_array(dims)) > 0
+    for query in (maps_ws, surface_ws):
+        assert query(1, 2, 2, _lib.dims_array((8193, 2))) < 0
+        assert query(1, 5, 2, _lib.dims_array((2, 32768))) < 0
+        assert query(1, 1, 3, _lib.dims_array((8193, 2, 2))) < 0 and query(1, 1, 3, _lib.dims_array((2, 8193, 2))) < 0
+        assert query(1, 1, 3, _lib.dims_array((8192, 2, 2))) > 0 and query(1, 1, 3, _lib.dims_array((2, 8192, 2))) > 0
+    # the transform has no query: its refusals come from the entry itself, before any launch (the pointer is never read)
+    p = ctypes.c_void_p(16)
+    for dims in ((16385, 2), (2, 32768), (16385, 2, 2), (2, 16385, 2), (2, 2, 32768)):
+        assert lib.advchain_edt(p, 1, None, 0, p, 1, len(dims), _lib.dims_array(dims), None) == -2, dims
+        assert b"too large" in lib.advchain_last_error()
+    for dims in ((8193, 2), (2, 32768)):
+        assert lib.advchain_signed_maps(p, None, p, p, 1, 2, 2, _lib.dims_array(dims), None) == -2, dims
+        assert b"too large" in lib.advchain_last_error()

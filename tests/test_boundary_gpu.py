@@ -3,7 +3,9 @@ the brute-force float64 forms of tests/edt_forms.py: every pass and tile shape o
 wave, a column longer than a 64-wide LDS tile, 3D, the longest axis outermost), masks with near and far seeds, lines and
 entries without a seed, every mask dtype; the signed maps for 1 to 70 classes with absent and filling classes, -100 and
 out-of-range labels; the loss on every load path with labels and with given maps, bf16 logits and misaligned tensors bit for
-bit, bitwise reproducibility, a captured graph and the device guard.
+bit, bitwise reproducibility, a captured graph and the device guard.  The dispatch edges of csrc/edt.hip -- rows of more than
+four chunks, a second class group, tiles narrower than 16 x, the largest shapes accepted, axes of length 1 -- are in
+tests/test_edt_edges_gpu.py.
 
 Bounds.  Unit spacing: squared distances are exact integers (torch.equal) and a distance is within 1.2e-7 relative of the
 float64 root (one fp32 ulp: the root of an exact integer is rounded once).  With a sampling: SAMPLING_TOL relative (2e-6;
