@@ -114,6 +114,8 @@ PROTOTYPES = {
     "advchain_remove_small": (_I, [_P, _P, _P, _L, _I, _P, _I, _L, _L, _L, _P]),
     "advchain_fill_holes_workspace": (_L, [_L, _I, _P]),
     "advchain_fill_holes": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _L, _L, _P]),
+    "advchain_morph_workspace": (_L, [_I, _L, _L, _I, _P]),
+    "advchain_morph": (_I, [_P, _P, _D, _I, _P, _P, _L, _L, _L, _I, _P, _P]),
     "advchain_boundary_workspace": (_L, [_L, _L, _I, _P]),
     "advchain_boundary_fwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _P]),
     "advchain_boundary_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _P]),

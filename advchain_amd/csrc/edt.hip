@@ -2,7 +2,9 @@
 //
 //   advchain_edt                 <- common.loss.distance_transform_edt
 //   advchain_signed_maps         <- common.loss.signed_distance_maps (and boundary_loss with a label target)
-//   edt_label_fields             <- csrc/seg_surface.hip (csrc/edt_fields.h): field 0 of every class through the passes, not finished
+//   edt_label_fields             <- csrc/seg_surface.hip, csrc/seg_morph.hip (csrc/edt_fields.h): field 0 of every class through the
+//                                   passes, not finished
+//   edt_mask_fields              <- csrc/seg_morph.hip: the same passes from 8-bit masks (host code only: no kernel of its own)
 //
 // A field holds, per voxel, the squared distance to the nearest SEED of its line so far, or the sentinel "no seed yet".  It
 // is separable: one pass per axis, each in place.
@@ -287,7 +289,7 @@ int edt_run(const void* src, int kind, T* g, float* out, int64_t N, int K, const
 
 // the passes without a finish: field 0 (seeds are the members) of every class, left as squared distances with the sentinel
 template <typename T>
-int edt_fields_run(const int64_t* labels, T* g, int64_t N, int K, const EdtShape& sh, const float (&s)[3], hipStream_t st) {
+int edt_fields_run(const void* src, int kind, T* g, int64_t N, int K, const EdtShape& sh, const float (&s)[3], hipStream_t st) {
   const int64_t D = sh.d[0], H = sh.d[1], W = sh.d[2], R = D * H, Q = N * K;
   if (N * R > 0x7fffffff) {
     advchain_set_error_("edt: too many rows for one launch");
@@ -296,7 +298,7 @@ int edt_fields_run(const int64_t* labels, T* g, int64_t N, int K, const EdtShape
   const int chunks = (int)((W + 63) / 64);
   const int group = kEdtBallots / chunks;
   for (int k0 = 0; k0 < K; k0 += group) {
-    hipLaunchKernelGGL(k_edt_rows<T>, dim3((unsigned)(N * R)), dim3(kBlock), 0, st, (const void*)labels, (int)SRC_LABELS, g, K, 1, 0,
+    hipLaunchKernelGGL(k_edt_rows<T>, dim3((unsigned)(N * R)), dim3(kBlock), 0, st, src, kind, g, K, 1, 0,
                        (int)W, R, k0, K - k0 < group ? K - k0 : group, chunks, s[2]);
     ADVCHAIN_LAUNCH_CHECK();
   }
@@ -316,12 +318,12 @@ int64_t edt_label_fields_words(int64_t entries, int64_t K, int ndim, const int64
   return edt_words(entries * K, 1, sh);
 }
 
-int edt_label_fields(const int64_t* labels, const float* sampling, void* fields, int64_t entries, int64_t K, int ndim,
-                     const int64_t* dims, const char* what, hipStream_t st) {
+int edt_fields_check(const float* sampling, int64_t entries, int64_t K, int ndim, const int64_t* dims, const char* what,
+                     int64_t (&d)[3], float (&s)[3]) {
   char msg[256];
   EdtShape sh;
   const int rc = edt_shape(ndim, dims, 2, &sh);
-  if (rc == ADVCHAIN_ERR_ARG || entries < 1 || K < 1 || K > 65535 || !labels || !fields) {
+  if (rc == ADVCHAIN_ERR_ARG || entries < 1 || K < 1 || K > 65535) {
     snprintf(msg, sizeof(msg), "%s: bad pointer, N, K, ndim or dims", what);
     advchain_set_error_(msg);
     return ADVCHAIN_ERR_ARG;
@@ -331,14 +333,41 @@ int edt_label_fields(const int64_t* labels, const float* sampling, void* fields,
     advchain_set_error_(msg);
     return ADVCHAIN_ERR_UNSUPPORTED;
   }
-  float s[3];
   if (!edt_spacing(sampling, sh, s)) {
     snprintf(msg, sizeof(msg), "%s: sampling must be positive and finite (and the physical diagonal below 1e14)", what);
     advchain_set_error_(msg);
     return ADVCHAIN_ERR_ARG;
   }
-  if (sampling) return edt_fields_run<float>(labels, (float*)fields, entries, (int)K, sh, s, st);
-  return edt_fields_run<int>(labels, (int*)fields, entries, (int)K, sh, s, st);
+  for (int a = 0; a < 3; ++a) d[a] = sh.d[a];
+  return ADVCHAIN_OK;
+}
+
+static int edt_fields_from(const void* src, int kind, const float* sampling, void* fields, int64_t entries, int64_t K, int ndim,
+                           const int64_t* dims, const char* what, hipStream_t st) {
+  if (!src || !fields) {
+    char msg[256];
+    snprintf(msg, sizeof(msg), "%s: bad pointer, N, K, ndim or dims", what);
+    advchain_set_error_(msg);
+    return ADVCHAIN_ERR_ARG;
+  }
+  EdtShape sh;
+  float s[3];
+  const int rc = edt_fields_check(sampling, entries, K, ndim, dims, what, sh.d, s);
+  if (rc != ADVCHAIN_OK) return rc;
+  sh.nd = ndim;
+  sh.V = sh.d[0] * sh.d[1] * sh.d[2];
+  if (sampling) return edt_fields_run<float>(src, kind, (float*)fields, entries, (int)K, sh, s, st);
+  return edt_fields_run<int>(src, kind, (int*)fields, entries, (int)K, sh, s, st);
+}
+
+int edt_label_fields(const int64_t* labels, const float* sampling, void* fields, int64_t entries, int64_t K, int ndim,
+                     const int64_t* dims, const char* what, hipStream_t st) {
+  return edt_fields_from(labels, SRC_LABELS, sampling, fields, entries, K, ndim, dims, what, st);
+}
+
+int edt_mask_fields(const unsigned char* mask, const float* sampling, void* fields, int64_t entries, int ndim, const int64_t* dims,
+                    const char* what, hipStream_t st) {
+  return edt_fields_from(mask, SRC_U8, sampling, fields, entries, 1, ndim, dims, what, st);
 }
 
 }  // namespace advchain

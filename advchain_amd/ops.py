@@ -2347,6 +2347,59 @@ def find_holes(labels, num_classes, connectivity=1, background=0, max_size=None)
     return _fill_holes("find_holes", labels, num_classes, connectivity, background, max_size, False, True)[1]
 
 
+# ---- erosion, dilation, opening and closing with a Euclidean ball (csrc/seg_morph.hip) -----------------------------------------
+
+# The tiles of the morphology kernels by number of spatial axes; None: the axis is not tiled (k_morph_axis stages whole lines).
+# Along x the row kernel works in ballots of 64 voxels and the column kernel in tiles of 32 x or a power of two below: every
+# multiple of 64 is a seam of both.
+MORPH_TILE = {2: (None, 64), 3: (None, None, 64)}
+_MORPH_OPS = {"erosion": 0, "dilation": 1, "opening": 2, "closing": 3}
+
+
+def _morph(name, labels, radius, num_classes, sampling, background):
+    labels = _dev_labels(labels.detach() if isinstance(labels, torch.Tensor) else labels, "labels")
+    N, K, sp = labels.shape[0], int(num_classes), tuple(labels.shape[1:])
+    lib = _lib.load()
+    dims = _lib.dims_array(sp)
+    n = lib.advchain_morph_workspace(_MORPH_OPS[name], N, K, len(sp), dims)
+    if n < 0:
+        raise NotImplementedError("%s: N=%d, K=%d, spatial shape %s is too large for the distance fields (an axis above 32767 -- 8192 "
+                                  "for the leading axes -- or a squared diagonal of 2^30 or more)" % (name, N, K, sp))
+    ws = torch.empty(int(n), device=labels.device, dtype=torch.int32)
+    out = torch.empty_like(labels)
+    _edt_check(lib.advchain_morph(_ptr(labels), _sampling_array(sampling, len(sp)), float(radius), _MORPH_OPS[name], _ptr(out),
+                                  _ptr(ws), N, K, int(background), len(sp), dims, _stream()), name, sp)
+    return out
+
+
+@_on_tensor_device
+def erosion(labels, radius, num_classes, sampling=None, background=0):
+    """(N,dims) int64 labels -> the same with every class voxel that has another label within `radius` set to `background`
+    (include/advchain_hip.h: advchain_morph, op 0).  No gradient."""
+    return _morph("erosion", labels, radius, num_classes, sampling, background)
+
+
+@_on_tensor_device
+def dilation(labels, radius, num_classes, sampling=None, background=0):
+    """(N,dims) int64 labels -> the same with every background voxel within `radius` of a class voxel set to the class of the
+    nearest one, the smaller class among equally near (advchain_morph, op 1).  No gradient."""
+    return _morph("dilation", labels, radius, num_classes, sampling, background)
+
+
+@_on_tensor_device
+def opening(labels, radius, num_classes, sampling=None, background=0):
+    """(N,dims) int64 labels -> the same with every class voxel outside the opening of its class by the ball set to `background`
+    (advchain_morph, op 2).  No gradient."""
+    return _morph("opening", labels, radius, num_classes, sampling, background)
+
+
+@_on_tensor_device
+def closing(labels, radius, num_classes, sampling=None, background=0):
+    """(N,dims) int64 labels -> the same with every background voxel inside the closing of exactly one class set to that class
+    (advchain_morph, op 3).  No gradient."""
+    return _morph("closing", labels, radius, num_classes, sampling, background)
+
+
 class _Boundary(torch.autograd.Function):
     """1/(N V) sum omega_k softmax(x)_k maps_k over the counted voxels and classes (include/advchain_hip.h:
     advchain_boundary_fwd).  Differentiable w.r.t. the logits; the maps are a constant.  Two launches forward, one backward."""

@@ -888,6 +888,35 @@ int advchain_fill_holes(const int64_t* labels, int64_t* out, int64_t* fill, int6
                         int64_t N, int64_t K, int ndim, const int64_t* dims, int connectivity, int64_t background,
                         int64_t max_size, void* stream);
 
+/* ---- erosion, dilation, opening and closing of label maps with a Euclidean ball, 2D and 3D (seg_morph.hip) ---------------------
+ * Not in the reference.  labels (N, dims) int64, dims = (H, W) or (D, H, W); K classes; `background` any integer.  A class voxel
+ * carries a label k in [0, K) other than `background`; S_k is the set of voxels of an entry with label k.  A label outside [0, K)
+ * (-100, K + 3) is neither class nor background: it is copied, never changes, never grows, and counts as "another label".  Labels
+ * are only compared.  Nothing crosses batch entries.  The ball is B = {o : sum_a (s_a o_a)^2 <= radius^2}, s = `sampling` (NULL:
+ * 1, and then the test is the integer one, |o|^2 <= floor(radius^2), capped at 2^30 - 1; otherwise ndim host floats, and the test
+ * is on fp32 fields against radius^2 rounded to fp32).  A position outside the image is nothing: not a member of any class
+ * (dilation gains nothing from it) and not an obstacle (erosion is not eaten from the border): scipy's binary_dilation with
+ * border_value=0 and binary_erosion with border_value=1.  `op`:
+ *   0 erosion   a class voxel v of class k keeps k iff every in-image v + o, o in B, carries k; otherwise it becomes `background`.
+ *   1 dilation  a background voxel becomes the class of the class voxel u within the ball that minimises (|s (v - u)|^2,
+ *               labels[u]) lexicographically: nearest wins, among equally near the smaller class.  Classes never overwrite.
+ *   2 opening   per class E_k = erosion of S_k, O_k = {v : d^2(v, E_k) <= radius^2}; a class voxel of class k outside O_k becomes
+ *               `background`.  Not dilation(erosion(x)), where freed voxels would be contested between classes.
+ *   3 closing   per class D_k = {v in the image : d^2(v, S_k) <= radius^2} (voxels of any label), C_k = {v : every in-image v + o
+ *               lies in D_k}; a background voxel becomes k iff it lies in C_k for exactly one class k; claimed by two, it stays.
+ * Every other voxel is copied.  out (N, dims) int64 is not the input.  A ball that holds only the origin gives a copy.
+ * Erosion and dilation run ONE field per voxel whatever K is (the squared distance to the nearest other label; the key
+ * (squared distance, class) of the nearest class voxel), every scan bounded at ceil(radius / spacing) offsets; opening and
+ * closing take their per-class fields from the passes of the transform above, never for k == background.  No atomics, no
+ * memset, no host read-back: the same bits on every run, capturable on one stream.  K in 1 .. 65535; ADVCHAIN_ERR_UNSUPPORTED
+ * for the shapes advchain_signed_maps refuses.
+ * `workspace` (16-byte aligned, no clearing needed): advchain_morph_workspace 4-byte words, host-only query, -1 for a bad op and
+ * exactly where advchain_signed_maps_workspace is -1; with V voxels per entry it is N V (erosion), 2 N V (dilation),
+ * N V (2 + K) (opening), N V (2 + K) + ceil(N K V / 4) (closing).                                                              */
+int64_t advchain_morph_workspace(int op, int64_t N, int64_t K, int ndim, const int64_t* dims); /* 4-byte words */
+int advchain_morph(const int64_t* labels, const float* sampling, double radius, int op, int64_t* out, void* workspace, int64_t N,
+                   int64_t K, int64_t background, int ndim, const int64_t* dims, void* stream);
+
 /* ---- boundary (surface) loss, 2D and 3D (seg_boundary.hip) -----------------------------------------------------------------
  * Not in the reference (Kervadec et al.).  logits (N,K,dims) fp32 (logits_bf16 = 0) or bf16 (1), maps (N,K,dims) fp32 signed
  * distance maps (a constant), p = softmax over K inside the kernel:
