@@ -108,6 +108,9 @@ PROTOTYPES = {
     "advchain_signed_maps": (_I, [_P, _P, _P, _P, _L, _L, _I, _P, _P]),
     "advchain_surface_metrics_workspace": (_L, [_L, _L, _I, _P]),
     "advchain_surface_metrics": (_I, [_P, _P, _P, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _P]),
+    "advchain_surface_dice_route": (_I, [_L, _L, _I, _P, _P, _D, _I]),
+    "advchain_surface_dice_workspace": (_L, [_L, _L, _I, _P, _P, _D, _I]),
+    "advchain_surface_dice": (_I, [_P, _P, _P, _P, _D, _I, _P, _P, _P, _P, _L, _L, _I, _P, _P]),
     "advchain_components_workspace": (_L, [_L, _I, _P]),
     "advchain_components": (_I, [_P, _P, _P, _P, _P, _L, _I, _P, _I, _L, _L, _P]),
     "advchain_keep_largest": (_I, [_P, _P, _P, _P, _L, _L, _I, _P, _I, _L, _P]),

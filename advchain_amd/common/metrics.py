@@ -1,5 +1,5 @@
 """Validation metrics of label maps on the device (not in the reference; csrc/seg_surface.hip on the distance fields of csrc/edt.hip):
-``surface_distance_metrics`` / ``hausdorff_distance`` / ``average_surface_distance``.
+``surface_distance_metrics`` / ``hausdorff_distance`` / ``average_surface_distance`` / ``surface_dice``.
 
 Definitions.  pred and target are int64 label maps (N, dims), dims = (H, W) or (D, H, W), K = num_classes.  For entry n and class
 k: A = {v : pred[n,v] == k} and B = {v : target[n,v] == k}.  A label outside [0, K), -100 included, belongs to no class (the rule
@@ -35,7 +35,7 @@ import math
 import torch
 
 from .. import ops
-from ..ops import SurfaceMetrics  # noqa: F401
+from ..ops import SurfaceDice, SurfaceMetrics  # noqa: F401
 from .loss import _check_num_classes, _check_sampling, _require_gpu
 
 
@@ -97,3 +97,39 @@ def average_surface_distance(pred, target, num_classes, sampling=None, symmetric
     _require_gpu(target, "target")
     m = ops.surface_distance_metrics(pred, target, num_classes, sampling=sampling)
     return m.assd if symmetric else m.directed[:, :, 0, 2]
+
+
+def surface_dice(pred, target, num_classes, tolerance, sampling=None):
+    """Normalised surface Dice at a tolerance (NSD) of every class of a pair of label maps: the share of border voxels that lie
+    within `tolerance` of the other map's border.  A, B, the border dS, the two directions and `sampling` are those of the module's
+    docstring.  This is the voxel-count definition of MONAI's compute_surface_dice (Medical Segmentation Decathlon, Metrics
+    Reloaded), not DeepMind's surface-area-weighted one.  Returns SurfaceDice, a namedtuple of device tensors:
+
+        surface_dice    (N,K)    fp32   (c0 + c1) / (m0 + m1), taken in float64 and rounded to fp32 once
+        within          (N,K,2)  int64  c0 = #{a in dA : d(a, dB) <= tau_k},  c1 = #{b in dB : d(b, dA) <= tau_k}
+        surface_voxels  (N,K,2)  int64  m0, m1: the integers surface_distance_metrics returns
+
+    tolerance: one finite number >= 0, or num_classes of them (list, tuple or 1-D tensor; MONAI's class_thresholds), in the units
+    of `sampling`.  Empty borders: NaN when m0 + m1 == 0; when exactly one border is empty every distance is +inf, nothing is
+    within, and the value is 0 (MONAI's convention).
+
+    The comparison follows the ball rule of common.postprocess.erosion / dilation, so the two agree.  With unit spacing it is
+    on exact integers: d^2 <= T_k with T_k = min(floor(tau_k * tau_k), 2^30 - 1), taken in float64 on the host.  tolerance=2
+    includes the squared length 4; math.sqrt(3) gives T = 2 (its square is 2.9999999999999996 in float64): pass a hair more than
+    a root that is meant to be included.  With a sampling the squared distance is the fp32 value the distance transform
+    produces, ((s_x dx)^2 + (s_y dy)^2) + (s_z dz)^2 evaluated in fp32 in that order, compared with tau_k^2 rounded to fp32 once:
+    a tolerance equal to a multiple of the spacing (0.7 at a spacing of 0.7, or 1.4) can fall on either side of the comparison.
+    Give such a tolerance a hair above the multiple (1.4001).
+
+    Every value is the same bits on every run and on both routes of the kernel (a search inside the ball for small
+    tolerances, the distance fields for large ones); integer atomics only, nothing is read back to the host, and the call can
+    be captured in a graph after the first use of a tolerance vector (its K words are copied to the device once and cached).
+    The cache keeps the 64 vectors per process that were used last: a graph captured outside a frozen plan holds no reference
+    of its own to the vector it read, so a program that replays such a graph while it goes through more than 64 other tolerance
+    vectors must keep the graph's vector in use (call once with it eagerly) or capture under a plan.
+    There is no gradient: the inputs are detached."""
+    sampling = _check_maps("surface_dice", pred, target, num_classes, sampling)
+    tolerance = ops.surface_dice_tolerances("surface_dice", tolerance, num_classes)
+    _require_gpu(pred, "pred")
+    _require_gpu(target, "target")
+    return ops.surface_dice(pred, target, num_classes, tolerance, sampling=sampling)

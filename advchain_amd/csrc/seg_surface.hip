@@ -1,6 +1,7 @@
 // Surface distance metrics of a pair of label maps, every class in one call, 2D and 3D, for gfx950:
 //
 //   advchain_surface_metrics     <- common.metrics.surface_distance_metrics (hausdorff_distance, average_surface_distance)
+//   advchain_surface_dice        <- common.metrics.surface_dice (further down: "surface Dice at a tolerance")
 //
 // For entry n and class k, A = {v: pred[n,v] == k}, B = {v: target[n,v] == k}; the border of a set is its voxels with a face
 // neighbour (4 in 2D, 6 in 3D) outside it, a position outside the image counting as outside.  A voxel has one label per map,
@@ -368,6 +369,333 @@ bool surface_plan(int64_t N, int64_t K, int ndim, const int64_t* dims, SurfacePl
   return p->total < ((int64_t)1 << 60);
 }
 
+// ---- surface Dice at a tolerance --------------------------------------------------------------------------------------------
+//   advchain_surface_dice        <- common.metrics.surface_dice
+//
+// within[n,k,0] = #{a in dA: d(a, dB)^2 <= thr_k}, within[n,k,1] = #{b in dB: d(b, dA)^2 <= thr_k}, next to m0 = |dA|, m1 = |dB|;
+// surface_dice = (c0 + c1) / (m0 + m1).  thr_k is a device word per class: with unit spacing the integer min(floor(tau_k^2),
+// 2^30 - 1), and the test is on exact integer squares; with a sampling the bits of tau_k^2 rounded to fp32 (at most 1e29), and the
+// square is the fp32 value of the transform, ((s_x dx)^2 + (s_y dy)^2) + (s_z dz)^2 without contraction: the transform takes
+// exact minima of these sums axis by axis and fp32 addition is monotone, so "some border voxel of the class within the
+// threshold" and "field word <= threshold" are the same predicate.  Both kinds of word are non-negative: their unsigned
+// integer order is their order.  Two routes with the same bits:
+//   ball     k_surface_ball, one pass over the two maps, no word per class.  A workgroup stages the classes of both maps of its
+//            tile and a halo of cap_a + 1 voxels per tiled axis in LDS, one 32-bit word per cell (pred's class in the low half,
+//            target's in the high half, 0xffff no class, 0xfffe outside the image), evaluates the border predicate of
+//            k_surface_edges for the owned cells and cap_a of the halo (the last layer only serves as their neighbours) and
+//            leaves in every word the class at a border voxel and 0xffff elsewhere.  An owned border voxel of either map then
+//            looks for the same class in the other half inside the ball: |dz| and |dy| outward from 0, x bounded by what is
+//            left of the threshold, stopping at the first hit.  m0, m1, c0, c1: LDS counters per group of 256 classes, one
+//            64-bit integer atomic per non-zero counter.  clear + ball + finish: three launches, no field, no edge map.
+//            cap_a = min(the largest offset o with (s_a o)^2 <= the largest threshold, dims_a - 1): isqrt(T_max) with unit
+//            spacing and floor(tau_max / s_a) with a sampling (decided by the fp32 test itself where the quotient is within
+//            rounding of an integer).
+//            ELIGIBLE iff K <= 65534 (the two halves of a word) and a tile of the list below -- from the widest on, the
+//            first that fits is taken -- has (tz + 2 hz) (ty + 2 hy) (tx + 2 hx) cells of 5 bytes (a word and a flag byte)
+//            within kBallLdsBytes, with h_a = cap_a + 1 and in 2D tz = 1, hz = 0:
+//              2D  (32,64) (16,64) (8,64)            3D  (8,8,32) (4,8,32) (4,4,32) (2,4,32) (2,2,32)
+//            With unit spacing that is a cap of at most 38 in 2D and 6 in 3D.  No limit on the axes beyond 2^31 - 1 tiles.
+//   fields   the edge pass and edt_label_fields as for the distances, then k_surface_within: over the chunks and keys of
+//            k_surface_digits, key <= thr[class] per (n, k, direction), LDS counters per group of classes merged with 64-bit
+//            integer atomics.  Any tolerance; the shape limits and the workspace of the distance fields.
+// Dispatch: the ball where it is eligible and no cap exceeds kBallDispatchCap2 (2D) / kBallDispatchCap3 (3D), else the fields,
+// else (a shape the fields refuse) the ball where it is eligible.
+constexpr int kBallLdsBytes = 61440;          // dynamic LDS of k_surface_ball: 64 KiB less the 4 KiB of its counters
+constexpr int kBallClasses = 256;             // classes whose four counters LDS holds at a time
+constexpr int kBallMaxK = 65534;
+// Dispatch limits from profiles/r28/surface_dice/summary.md (blobs, caps 1, 2, 3 and 5 timed against the fields).  2D: the ball
+// is 1.2-20x faster at every cap timed, 5 is the largest that was.  3D: 4.5x and 1.8x faster at caps 1 and 2, but 0.74x at cap 3
+// and 0.38x at cap 5 (4x4x128x128x64: the halo is 5x to 22x the owned tile).
+constexpr int kBallDispatchCap2 = 5;
+constexpr int kBallDispatchCap3 = 2;
+constexpr u32 kHalfNone = 0xffffu, kHalfOutside = 0xfffeu;
+enum { DICE_ROUTE_ANY = 0, DICE_ROUTE_BALL = 1, DICE_ROUTE_FIELDS = 2 };
+
+struct BallGeom {
+  int nd, tz, ty, tx;          // owned tile (tz = 1 in 2D)
+  int c[3], h[3];              // cap and halo per axis (z, y, x); 0 along z in 2D
+  int lz, ly, lx;              // staged cells per axis
+  int tiles_z, tiles_y, tiles_x;
+  float s[3];
+};
+
+template <typename T> struct Bsq;
+template <> struct Bsq<int> {
+  static __device__ __forceinline__ int of(int d, float) { return d * d; }
+  static __device__ __forceinline__ int word(u32 w) { return (int)w; }
+};
+template <> struct Bsq<float> {
+  static __device__ __forceinline__ float of(int d, float s) { const float sd = s * (float)d; return sd * sd; }
+  static __device__ __forceinline__ float word(u32 w) { return __uint_as_float(w); }
+};
+
+__global__ void __launch_bounds__(kBlock)
+k_surface_dice_clear(int64_t* __restrict__ surface_voxels, int64_t* __restrict__ within, int64_t* __restrict__ overlap, int64_t NK) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < 2 * NK) surface_voxels[i] = within[i] = 0;
+  if (overlap && i < 3 * NK) overlap[i] = 0;
+}
+
+// a border voxel of class `cls` of the other map (its half of a word at `shift`) within `thr` of cell `at`
+template <typename T>
+__device__ __forceinline__ bool ball_find(const u32* __restrict__ w, int at, u32 cls, int shift, T thr, const BallGeom& g) {
+  const int sxy = g.lx * g.ly;
+  for (int az = 0; az <= g.c[0]; ++az) {
+    const T fz = Bsq<T>::of(az, g.s[0]);
+    if (!(fz <= thr)) break;
+    for (int sz = 0; sz < (az ? 2 : 1); ++sz) {
+      const int pz = at + (sz ? -az : az) * sxy;
+      for (int ay = 0; ay <= g.c[1]; ++ay) {
+        const T fy = Bsq<T>::of(ay, g.s[1]);
+        if (!(fy + fz <= thr)) break;
+        for (int sy = 0; sy < (ay ? 2 : 1); ++sy) {
+          const int py = pz + (sy ? -ay : ay) * g.lx;
+          for (int ax = 0; ax <= g.c[2]; ++ax) {
+            const T fx = Bsq<T>::of(ax, g.s[2]);
+            if (!((fx + fy) + fz <= thr)) break;             // (the order of the transform's additions: x, then y, then z)
+            if (((w[py + ax] >> shift) & 0xffffu) == cls) return true;
+            if (((w[py - ax] >> shift) & 0xffffu) == cls) return true;
+          }
+        }
+      }
+    }
+  }
+  return false;
+}
+
+// blockIdx.x = ((n tiles_z + z tile) tiles_y + y tile) tiles_x + x tile
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+k_surface_ball(const int64_t* __restrict__ pred, const int64_t* __restrict__ target, const u32* __restrict__ thr,
+               int64_t* surface_voxels, int64_t* within, int K, int D, int H, int W, BallGeom g) {
+  extern __shared__ __align__(16) unsigned char ball_lds[];
+  __shared__ u32 counts[kBallClasses * 4];
+  const int LX = g.lx, LY = g.ly, cells = g.lz * LY * LX;
+  u32* w = reinterpret_cast<u32*>(ball_lds);
+  unsigned char* flag = ball_lds + (size_t)cells * 4;
+  int64_t b = blockIdx.x;
+  const int bx = (int)(b % g.tiles_x); b /= g.tiles_x;
+  const int by = (int)(b % g.tiles_y); b /= g.tiles_y;
+  const int bz = (int)(b % g.tiles_z);
+  const int64_t n = b / g.tiles_z, V = (int64_t)D * H * W;
+  const int z0 = bz * g.tz, y0 = by * g.ty, x0 = bx * g.tx;
+
+  for (int i = threadIdx.x; i < cells; i += kBlock) {
+    const int lx = i % LX, ly = (i / LX) % LY, lz = i / (LX * LY);
+    const int64_t z = (int64_t)z0 + lz - g.h[0], y = (int64_t)y0 + ly - g.h[1], x = (int64_t)x0 + lx - g.h[2];
+    u32 a = kHalfOutside, c = kHalfOutside;
+    if (z >= 0 && z < D && y >= 0 && y < H && x >= 0 && x < W) {
+      const int64_t at = n * V + (z * H + y) * W + x;
+      const int ka = class_of(pred[at], K), kc = class_of(target[at], K);
+      a = ka < 0 ? kHalfNone : (u32)ka;
+      c = kc < 0 ? kHalfNone : (u32)kc;
+    }
+    w[i] = a | (c << 16);
+  }
+  __syncthreads();
+
+  // the border predicate for every cell but the outermost layer of the tiled axes
+  const int IX = LX - 2, IY = LY - 2, IZ = g.nd == 3 ? g.lz - 2 : 1, oz = g.nd == 3 ? 1 : 0, inner = IZ * IY * IX;
+  for (int i = threadIdx.x; i < inner; i += kBlock) {
+    const int at = ((i / (IX * IY) + oz) * LY + (i / IX) % IY + 1) * LX + i % IX + 1;
+    const u32 v = w[at], a = v & 0xffffu, c = v >> 16;
+    const u32 l = w[at - 1], r = w[at + 1], u = w[at - LX], d = w[at + LX];
+    bool ea = (l & 0xffffu) != a || (r & 0xffffu) != a || (u & 0xffffu) != a || (d & 0xffffu) != a;
+    bool ec = (l >> 16) != c || (r >> 16) != c || (u >> 16) != c || (d >> 16) != c;
+    if (g.nd == 3) {
+      const u32 f = w[at - LX * LY], k = w[at + LX * LY];
+      ea = ea || (f & 0xffffu) != a || (k & 0xffffu) != a;
+      ec = ec || (f >> 16) != c || (k >> 16) != c;
+    }
+    flag[at] = (unsigned char)((ea && a < kHalfOutside ? 1 : 0) | (ec && c < kHalfOutside ? 2 : 0));
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < inner; i += kBlock) {
+    const int at = ((i / (IX * IY) + oz) * LY + (i / IX) % IY + 1) * LX + i % IX + 1;
+    const u32 v = w[at], f = flag[at];
+    w[at] = ((f & 1u) ? (v & 0xffffu) : kHalfNone) | (((f & 2u) ? (v >> 16) : kHalfNone) << 16);
+  }
+
+  const int own = g.tz * g.ty * g.tx;
+  for (int g0 = 0; g0 < K; g0 += kBallClasses) {
+    for (int i = threadIdx.x; i < kBallClasses * 4; i += kBlock) counts[i] = 0u;
+    __syncthreads();                                     // (the first time: also the barrier behind the edge words)
+    for (int i = threadIdx.x; i < own; i += kBlock) {
+      const int tx = i % g.tx, ty = (i / g.tx) % g.ty, tz = i / (g.tx * g.ty);
+      if (z0 + tz >= D || y0 + ty >= H || x0 + tx >= W) continue;
+      const int at = ((tz + g.h[0]) * LY + ty + g.h[1]) * LX + tx + g.h[2];
+      const u32 v = w[at], a = v & 0xffffu, c = v >> 16;
+      if (a != kHalfNone && (int)a >= g0 && (int)a < g0 + kBallClasses) {
+        u32* q = counts + ((int)a - g0) * 4;
+        atomicAdd(q + 0, 1u);
+        if (ball_find<T>(w, at, a, 16, Bsq<T>::word(thr[a]), g)) atomicAdd(q + 2, 1u);
+      }
+      if (c != kHalfNone && (int)c >= g0 && (int)c < g0 + kBallClasses) {
+        u32* q = counts + ((int)c - g0) * 4;
+        atomicAdd(q + 1, 1u);
+        if (ball_find<T>(w, at, c, 0, Bsq<T>::word(thr[c]), g)) atomicAdd(q + 3, 1u);
+      }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < kBallClasses * 4; i += kBlock) {
+      const int kk = g0 + i / 4, f = i % 4;
+      const u32 v = counts[i];
+      if (kk < K && v) {
+        int64_t* o = (f < 2 ? surface_voxels : within) + (n * K + kk) * 2 + (f & 1);
+        atomicAdd(reinterpret_cast<u64*>(o), (u64)v);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// the field route's count: blockIdx = (chunk, n, direction) as k_surface_digits
+__global__ void __launch_bounds__(kBlock)
+k_surface_within(const int64_t* __restrict__ edges, const u32* __restrict__ fields, const u32* __restrict__ thr, int64_t* within,
+                 int64_t N, int K, int64_t V, int64_t per) {
+  __shared__ u32 counts[kCountClasses];
+  const Chunk ch = chunk_of(edges, fields, N, K, V, per);
+  const int64_t n = blockIdx.y, d = blockIdx.z;
+  for (int g0 = 0; g0 < K; g0 += kCountClasses) {
+    for (int i = threadIdx.x; i < kCountClasses; i += kBlock) counts[i] = 0u;
+    __syncthreads();
+    for (int64_t v = ch.begin + threadIdx.x; v < ch.end; v += kBlock) {
+      const int64_t e = ch.edge[v];
+      if (e < g0 || e >= g0 + kCountClasses) continue;
+      if (ch.field[e * V + v] <= thr[e]) atomicAdd(&counts[(int)e - g0], 1u);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < kCountClasses; i += kBlock) {
+      const u32 c = counts[i];
+      if (g0 + i < K && c) atomicAdd(reinterpret_cast<u64*>(within + (n * K + g0 + i) * 2 + d), (u64)c);
+    }
+    __syncthreads();
+  }
+}
+
+__global__ void __launch_bounds__(kBlock)
+k_surface_dice_finish(const int64_t* __restrict__ surface_voxels, const int64_t* __restrict__ within, float* __restrict__ out,
+                      int64_t NK) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= NK) return;
+  const int64_t m = surface_voxels[2 * i] + surface_voxels[2 * i + 1], c = within[2 * i] + within[2 * i + 1];
+  out[i] = m == 0 ? (float)NAN : (float)((double)c / (double)m);
+}
+
+const int kBallTiles2[][3] = {{1, 32, 64}, {1, 16, 64}, {1, 8, 64}};
+const int kBallTiles3[][3] = {{8, 8, 32}, {4, 8, 32}, {4, 4, 32}, {2, 4, 32}, {2, 2, 32}};
+
+float host_sq(int d, float s) {                  // Bsq<float>::of on the host (this file is compiled without contraction)
+  const float sd = s * (float)d;
+  return sd * sd;
+}
+
+// The arguments every route needs: 0, or ADVCHAIN_ERR_ARG with the error set.  d = (D, H, W), s the spacing of those axes.
+int dice_args(int64_t N, int64_t K, int ndim, const int64_t* dims, const float* sampling, double tolerance_max, int route,
+              int64_t (&d)[3], float (&s)[3]) {
+  ADVCHAIN_CHECK_ARG(K >= 1 && K <= 65535, "surface_dice: K must be in 1..65535");
+  ADVCHAIN_CHECK_ARG(N >= 1, "surface_dice: bad N");
+  ADVCHAIN_CHECK_ARG(dims && (ndim == 2 || ndim == 3), "surface_dice: bad ndim or dims");
+  for (int a = 0; a < ndim; ++a) ADVCHAIN_CHECK_ARG(dims[a] >= 1, "surface_dice: bad ndim or dims");
+  ADVCHAIN_CHECK_ARG(tolerance_max >= 0.0 && tolerance_max <= 1.79769313486231570e308,
+                     "surface_dice: the tolerance must be finite and not negative");
+  ADVCHAIN_CHECK_ARG(route >= DICE_ROUTE_ANY && route <= DICE_ROUTE_FIELDS, "surface_dice: route is 0 (dispatch), 1 (ball) or 2 (fields)");
+  d[0] = ndim == 3 ? dims[0] : 1;
+  d[1] = dims[ndim - 2];
+  d[2] = dims[ndim - 1];
+  s[0] = s[1] = s[2] = 1.f;
+  for (int a = 0; sampling && a < ndim; ++a) {
+    const float v = sampling[a];
+    ADVCHAIN_CHECK_ARG(v > 0.f && v <= 3.40282347e38f && (double)v * v >= 1.0e-30,
+                       "surface_dice: sampling must be positive and finite (and the physical diagonal below 1e14)");
+    s[3 - ndim + a] = v;
+  }
+  return ADVCHAIN_OK;
+}
+
+// the ball route's tile for these caps, or false where it is not eligible
+bool ball_geometry(int64_t N, int64_t K, int ndim, const int64_t (&d)[3], const float (&s)[3], bool unit, double tolerance_max,
+                   BallGeom* g) {
+  if (K > kBallMaxK) return false;
+  const double t2 = tolerance_max * tolerance_max;
+  const int64_t T = t2 >= (double)(kEdtFieldInf - 1) ? kEdtFieldInf - 1 : (int64_t)floor(t2);
+  const float tf = t2 >= 1.0e29 ? 1.0e29f : (float)t2;
+  g->nd = ndim;
+  for (int a = 0; a < 3; ++a) {
+    g->s[a] = s[a];
+    int64_t c = 0;
+    if (a >= 3 - ndim) {
+      if (unit) {
+        c = (int64_t)sqrt((double)T);
+        while (c * c > T) --c;
+        while ((c + 1) * (c + 1) <= T) ++c;
+      } else {
+        const double q = floor(tolerance_max / (double)s[a]);
+        c = q >= 65536.0 ? 65536 : (int64_t)q;
+        while (c < 65536 && host_sq((int)c + 1, s[a]) <= tf) ++c;
+        while (c > 0 && !(host_sq((int)c, s[a]) <= tf)) --c;
+      }
+      if (c > d[a] - 1) c = d[a] - 1;                   // (an offset of the whole axis leaves the image)
+      if (c > 4096) return false;
+    }
+    g->c[a] = (int)c;
+    g->h[a] = a >= 3 - ndim ? (int)c + 1 : 0;
+  }
+  const int (*tiles)[3] = ndim == 3 ? kBallTiles3 : kBallTiles2;
+  const int count = ndim == 3 ? 5 : 3;
+  for (int t = 0; t < count; ++t) {
+    const int64_t lz = tiles[t][0] + 2 * g->h[0], ly = tiles[t][1] + 2 * g->h[1], lx = tiles[t][2] + 2 * g->h[2];
+    const int64_t cells = lz * ly * lx;
+    if (cells * 4 + ((cells + 3) & ~(int64_t)3) > kBallLdsBytes) continue;
+    g->tz = tiles[t][0];
+    g->ty = tiles[t][1];
+    g->tx = tiles[t][2];
+    g->lz = (int)lz;
+    g->ly = (int)ly;
+    g->lx = (int)lx;
+    const int64_t nz = (d[0] + g->tz - 1) / g->tz, ny = (d[1] + g->ty - 1) / g->ty, nx = (d[2] + g->tx - 1) / g->tx;
+    if (d[0] > 0x7fffffff || d[1] > 0x7fffffff || d[2] > 0x7fffffff || nz * ny > 0x7fffffff || nz * ny * nx > 0x7fffffff ||
+        N > 0x7fffffff / (nz * ny * nx) || N > ((int64_t)1 << 36) / K)
+      return false;
+    if ((double)d[0] * (double)d[1] * (double)d[2] * (double)N >= 9.0e18) return false;
+    g->tiles_z = (int)nz;
+    g->tiles_y = (int)ny;
+    g->tiles_x = (int)nx;
+    return true;
+  }
+  return false;
+}
+
+bool fields_plan(int64_t N, int64_t K, int ndim, const int64_t* dims, const float* sampling, SurfacePlan* p) {
+  if (N > 65535 || N > ((int64_t)1 << 36) / K || !surface_plan(N, K, ndim, dims, p)) return false;
+  const int64_t tz = ndim == 3 ? 4 : 1, ty = ndim == 3 ? 8 : 32, D = ndim == 3 ? dims[0] : 1;
+  const int64_t tiles = ((D + tz - 1) / tz) * ((dims[ndim - 2] + ty - 1) / ty) * ((dims[ndim - 1] + kEdgeTX - 1) / kEdgeTX);
+  if (N * tiles > 0x7fffffff) return false;
+  int64_t d[3];
+  float s[3];
+  return edt_fields_check(sampling, 2 * N, K, ndim, dims, "surface_dice", d, s) == ADVCHAIN_OK;
+}
+
+// DICE_ROUTE_BALL or DICE_ROUTE_FIELDS, or ADVCHAIN_ERR_UNSUPPORTED with the error set
+int dice_route(int64_t N, int64_t K, int ndim, const int64_t* dims, const float* sampling, double tolerance_max, int route,
+               const int64_t (&d)[3], const float (&s)[3], BallGeom* g, SurfacePlan* p) {
+  const bool ball = ball_geometry(N, K, ndim, d, s, sampling == nullptr, tolerance_max, g);
+  const bool fields = fields_plan(N, K, ndim, dims, sampling, p);
+  if (route == DICE_ROUTE_BALL) {
+    if (ball) return DICE_ROUTE_BALL;
+    advchain_set_error_("surface_dice: the ball route is not eligible (the tile with a halo of cap + 1 voxels does not fit in LDS, "
+                        "K above 65534, or too many tiles)");
+    return ADVCHAIN_ERR_UNSUPPORTED;
+  }
+  if (route == DICE_ROUTE_ANY && ball) {
+    const int top = g->c[0] > g->c[1] ? (g->c[0] > g->c[2] ? g->c[0] : g->c[2]) : (g->c[1] > g->c[2] ? g->c[1] : g->c[2]);
+    if (top <= (ndim == 3 ? kBallDispatchCap3 : kBallDispatchCap2) || !fields) return DICE_ROUTE_BALL;
+  }
+  if (fields) return DICE_ROUTE_FIELDS;
+  advchain_set_error_("surface_dice: shape too large for the distance fields (an axis or the squared diagonal)");
+  return ADVCHAIN_ERR_UNSUPPORTED;
+}
+
 }  // namespace
 }  // namespace advchain
 
@@ -454,6 +782,87 @@ int advchain_surface_metrics(const int64_t* pred, const int64_t* target, const f
   hipLaunchKernelGGL(k_surface_finish, dim3((unsigned)(N * K)), dim3(64), 0, st, sg,
                      (const int64_t*)surface_voxels, (const int64_t*)overlap, q, unit, hausdorff, hausdorff_pct, assd, directed,
                      max_squared, dice, N, (int)K, (int)p.chunks);
+  ADVCHAIN_LAUNCH_CHECK();
+  return ADVCHAIN_OK;
+}
+
+int advchain_surface_dice_route(int64_t N, int64_t K, int ndim, const int64_t* dims, const float* sampling, double tolerance_max,
+                                int route) {
+  int64_t d[3];
+  float s[3];
+  const int rc = dice_args(N, K, ndim, dims, sampling, tolerance_max, route, d, s);
+  if (rc != ADVCHAIN_OK) return rc;
+  BallGeom g;
+  SurfacePlan p;
+  return dice_route(N, K, ndim, dims, sampling, tolerance_max, route, d, s, &g, &p);
+}
+
+int64_t advchain_surface_dice_workspace(int64_t N, int64_t K, int ndim, const int64_t* dims, const float* sampling,
+                                        double tolerance_max, int route) {
+  int64_t d[3];
+  float s[3];
+  if (dice_args(N, K, ndim, dims, sampling, tolerance_max, route, d, s) != ADVCHAIN_OK) return -1;
+  BallGeom g;
+  SurfacePlan p;
+  const int r = dice_route(N, K, ndim, dims, sampling, tolerance_max, route, d, s, &g, &p);
+  if (r < 0) return -1;
+  return r == DICE_ROUTE_BALL ? 0 : p.w_fields + p.w_edges + 6 * N * K;
+}
+
+int advchain_surface_dice(const int64_t* pred, const int64_t* target, const float* sampling, const void* thresholds,
+                          double tolerance_max, int route, float* surface_dice, int64_t* within, int64_t* surface_voxels,
+                          void* workspace, int64_t N, int64_t K, int ndim, const int64_t* dims, void* stream) {
+  ADVCHAIN_CHECK_ARG(pred && target && thresholds && surface_dice && within && surface_voxels, "surface_dice: null pointer");
+  int64_t d[3];
+  float s[3];
+  int rc = dice_args(N, K, ndim, dims, sampling, tolerance_max, route, d, s);
+  if (rc != ADVCHAIN_OK) return rc;
+  BallGeom g;
+  SurfacePlan p;
+  const int r = dice_route(N, K, ndim, dims, sampling, tolerance_max, route, d, s, &g, &p);
+  if (r < 0) return r;
+  hipStream_t st = (hipStream_t)stream;
+  const u32* thr = (const u32*)thresholds;
+  const int64_t NK = N * K;
+  const unsigned flat = (unsigned)((3 * NK + kBlock - 1) / kBlock);
+  const int D = (int)d[0], H = (int)d[1], W = (int)d[2];
+
+  if (r == DICE_ROUTE_BALL) {
+    hipLaunchKernelGGL(k_surface_dice_clear, dim3(flat), dim3(kBlock), 0, st, surface_voxels, within, (int64_t*)nullptr, NK);
+    ADVCHAIN_LAUNCH_CHECK();
+    const int64_t cells = (int64_t)g.lz * g.ly * g.lx;
+    const size_t lds = (size_t)(cells * 4 + ((cells + 3) & ~(int64_t)3));
+    const unsigned blocks = (unsigned)(N * g.tiles_z * g.tiles_y * g.tiles_x);
+    if (sampling)
+      hipLaunchKernelGGL(k_surface_ball<float>, dim3(blocks), dim3(kBlock), lds, st, pred, target, thr, surface_voxels, within,
+                         (int)K, D, H, W, g);
+    else
+      hipLaunchKernelGGL(k_surface_ball<int>, dim3(blocks), dim3(kBlock), lds, st, pred, target, thr, surface_voxels, within,
+                         (int)K, D, H, W, g);
+    ADVCHAIN_LAUNCH_CHECK();
+  } else {
+    ADVCHAIN_CHECK_ARG(workspace && ((uintptr_t)workspace & 15) == 0, "surface_dice: workspace must be 16-byte aligned and not null");
+    u32* w = (u32*)workspace;
+    u32* fields = w;                              w += p.w_fields;
+    int64_t* edges = (int64_t*)w;                 w += p.w_edges;
+    int64_t* overlap = (int64_t*)w;
+    hipLaunchKernelGGL(k_surface_dice_clear, dim3(flat), dim3(kBlock), 0, st, surface_voxels, within, overlap, NK);
+    ADVCHAIN_LAUNCH_CHECK();
+    const int hz = ndim == 3 ? 1 : 0, TZ = hz ? 4 : 1, TY = hz ? 8 : 32;
+    const int64_t tiles_z = (D + TZ - 1) / TZ, tiles_y = (H + TY - 1) / TY, tiles_x = (W + kEdgeTX - 1) / kEdgeTX;
+    const size_t lds = (size_t)(TZ + 2 * hz) * (TY + 2) * (kEdgeTX + 2) * 2 * sizeof(int);
+    hipLaunchKernelGGL(k_surface_edges, dim3((unsigned)(N * tiles_z * tiles_y * tiles_x)), dim3(kBlock), lds, st, pred, target, edges,
+                       edges + N * p.V, surface_voxels, overlap, (int)K, D, H, W, hz, TZ, TY, (int)tiles_z, (int)tiles_y,
+                       (int)tiles_x);
+    ADVCHAIN_LAUNCH_CHECK();
+    rc = edt_label_fields(edges, sampling, fields, 2 * N, K, ndim, dims, "surface_dice", st);
+    if (rc != ADVCHAIN_OK) return rc;
+    hipLaunchKernelGGL(k_surface_within, dim3((unsigned)p.chunks, (unsigned)N, 2), dim3(kBlock), 0, st, (const int64_t*)edges,
+                       (const u32*)fields, thr, within, N, (int)K, p.V, p.per);
+    ADVCHAIN_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_surface_dice_finish, dim3((unsigned)((NK + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                     (const int64_t*)surface_voxels, (const int64_t*)within, surface_dice, NK);
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
 }

@@ -7,6 +7,9 @@ memory (``torch.empty``), the current stream and the autograd tape only.
 import collections
 import ctypes
 import functools
+import math
+import numbers
+import struct
 
 import numpy as np
 import torch
@@ -2240,6 +2243,136 @@ def surface_distance_metrics(pred, target, num_classes, sampling=None, percentil
                                             _ptr(overlap), _ptr(dice), _ptr(ws), N, K, len(sp), dims, _stream()),
                "surface_metrics", sp)
     return SurfaceMetrics(f32[0], f32[1], f32[2], f32[3], voxels, max_squared, overlap, dice)
+
+
+# ---- surface Dice at a tolerance (csrc/seg_surface.hip: k_surface_ball, k_surface_within) ---------------------------------------
+
+SurfaceDice = collections.namedtuple("SurfaceDice", ["surface_dice", "within", "surface_voxels"])
+# The widest owned tile of the ball kernel by number of spatial axes; a tile that does not fit in LDS with its halo is halved
+# along the leading axes (kBallTiles2 / kBallTiles3 of the source): every seam of this tile is a seam of the narrower ones, which
+# add seams of their own at the multiples of their sizes (tests/test_surface_dice_gpu.py runs each of them).
+SURFACE_DICE_TILE = {2: (32, 64), 3: (8, 8, 32)}
+_DICE_ROUTES = {None: 0, "ball": 1, "fields": 2}
+_DICE_THRESHOLDS = {}
+
+
+def surface_dice_tolerances(name, tolerance, num_classes):
+    """`tolerance` -- one finite real number >= 0 (a Python or numpy scalar, not a bool), or num_classes of them as a list, a
+    tuple, a 1-D numpy array or a 1-D tensor -- as a tuple of num_classes floats, or ValueError.  (A tensor is read on the host:
+    pass numbers where the call must not synchronise.)"""
+    K = int(num_classes)
+    rule = "tolerance must be one finite real number >= 0 or a list, tuple or 1-D array / tensor of %d of them" % K
+    if isinstance(tolerance, (torch.Tensor, np.ndarray)):
+        boolean = tolerance.dtype == (torch.bool if isinstance(tolerance, torch.Tensor) else np.dtype(bool))
+        if tolerance.ndim != 1 or boolean:
+            raise ValueError("%s: %s, got a %s array of shape %s" % (name, rule, tolerance.dtype, tuple(tolerance.shape)))
+        tolerance = tolerance.detach().cpu().tolist() if isinstance(tolerance, torch.Tensor) else tolerance.tolist()
+    scalar = not isinstance(tolerance, (list, tuple))
+    vals = [tolerance] if scalar else list(tolerance)
+    if not scalar and len(vals) != K:
+        raise ValueError("%s: tolerance has the wrong length: %d numbers for %d classes" % (name, len(vals), K))
+    for v in vals:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v < 0:
+            raise ValueError("%s: %s, got %r" % (name, rule, tolerance))
+    return tuple(float(v) for v in vals) * (K if scalar else 1)
+
+
+def surface_dice_threshold_words(tolerances, unit):
+    """The 32-bit word per class that the kernels compare squared distances with.  Unit spacing: the integer
+    min(floor(tau * tau), 2^30 - 1), taken in float64.  With a sampling: the bits of tau * tau rounded to fp32 once (at most
+    1e29)."""
+    words = []
+    for t in tolerances:
+        t2 = float(t) * float(t)
+        if unit:
+            words.append(2 ** 30 - 1 if t2 >= 2 ** 30 - 1 else int(math.floor(t2)))
+        else:
+            words.append(struct.unpack("<I", struct.pack("<f", min(t2, 1.0e29)))[0])
+    return tuple(words)
+
+
+def surface_dice_thresholds_device(words, device):
+    """The K threshold words as K int32 on the device, cached per (device, words) the way class weights are: one host-device
+    copy at the first use, none after it.  Read-only.  The cache holds the 64 vectors used last and drops the oldest one for a
+    new one; a frozen plan keeps the tensor its capture read alive, a bare torch.cuda.graph capture does not -- see
+    common.metrics.surface_dice."""
+    key = (str(device), words)
+    t = _DICE_THRESHOLDS.pop(key, None)
+    if t is not None:
+        _DICE_THRESHOLDS[key] = t                      # (most recently used last)
+    else:
+        if len(_DICE_THRESHOLDS) >= 64:
+            _DICE_THRESHOLDS.pop(next(iter(_DICE_THRESHOLDS)))
+        # (words above 2^31 - 1 do not occur: fp32 bits of a non-negative number and integers below 2^30)
+        t = _DICE_THRESHOLDS[key] = torch.tensor(words, dtype=torch.int32, device=device)
+    plan = _PLAN
+    if plan is not None and plan.is_frozen:
+        plan.persistent.setdefault(("surface_dice_thr",) + key, t)
+    return t
+
+
+def _surface_dice_refused(N, K, sp, route):
+    msg = _lib.load().advchain_last_error().decode()
+    if route == "ball":
+        return NotImplementedError("surface_dice: N=%d, K=%d, spatial shape %s: %s" % (N, K, tuple(sp), msg))
+    return NotImplementedError("surface_dice: N=%d, K=%d, spatial shape %s is too large for the distance fields (an axis above "
+                               "32767 -- 8192 for the leading axes -- or a squared diagonal of 2^30 or more)" % (N, K, tuple(sp)))
+
+
+def surface_dice_route(N, K, spatial_shape, tolerance, sampling=None, route=None):
+    """"ball" or "fields": the route surface_dice takes for these sizes (a host-only query of the library, no GPU), or
+    NotImplementedError where no route can take them."""
+    if route not in _DICE_ROUTES:
+        raise ValueError("surface_dice: route must be None, 'ball' or 'fields', got %r" % (route,))
+    sp = tuple(int(s) for s in spatial_shape)
+    tol = surface_dice_tolerances("surface_dice", tolerance, K)
+    lib = _lib.load()
+    rc = lib.advchain_surface_dice_route(int(N), int(K), len(sp), _lib.dims_array(sp), _sampling_array(sampling, len(sp)), max(tol),
+                                         _DICE_ROUTES[route])
+    if rc == -2:
+        raise _surface_dice_refused(N, K, sp, route)
+    if rc not in (1, 2):
+        _lib.check(rc, "surface_dice")
+    return "ball" if rc == 1 else "fields"
+
+
+@_on_tensor_device
+def surface_dice(pred, target, num_classes, tolerance, sampling=None, route=None):
+    """(N,dims) int64 label maps -> SurfaceDice(surface_dice (N,K) fp32, within (N,K,2) int64, surface_voxels (N,K,2) int64): the
+    normalised surface Dice at a tolerance of every class (include/advchain_hip.h: advchain_surface_dice).  `route` (tests and
+    tools only): None dispatches, "ball" or "fields" forces a route; a forced ball that is not eligible raises
+    NotImplementedError.  No gradient."""
+    pred = _dev_labels(pred.detach() if isinstance(pred, torch.Tensor) else pred, "pred")
+    target = _dev_labels(target.detach() if isinstance(target, torch.Tensor) else target, "target")
+    _same_device(pred, target)
+    if pred.shape != target.shape:
+        raise ValueError("surface_dice: pred %s and target %s differ in shape" % (tuple(pred.shape), tuple(target.shape)))
+    if route not in _DICE_ROUTES:
+        raise ValueError("surface_dice: route must be None, 'ball' or 'fields', got %r" % (route,))
+    N, K = pred.shape[0], int(num_classes)
+    sp = tuple(pred.shape[1:])
+    tol = surface_dice_tolerances("surface_dice", tolerance, K)
+    lib = _lib.load()
+    dims = _lib.dims_array(sp)
+    samp = _sampling_array(sampling, len(sp))
+    n = lib.advchain_surface_dice_workspace(N, K, len(sp), dims, samp, max(tol), _DICE_ROUTES[route])
+    if n < 0:
+        rc = lib.advchain_surface_dice_route(N, K, len(sp), dims, samp, max(tol), _DICE_ROUTES[route])
+        if rc == -2:
+            raise _surface_dice_refused(N, K, sp, route)
+        _lib.check(rc, "surface_dice")
+    dev = pred.device
+    thr = surface_dice_thresholds_device(surface_dice_threshold_words(tol, sampling is None), dev)
+    ws = torch.empty(int(n), device=dev, dtype=torch.float32) if n > 0 else None
+    out = torch.empty((N, K), device=dev, dtype=torch.float32)
+    within = torch.empty((N, K, 2), device=dev, dtype=torch.int64)
+    voxels = torch.empty((N, K, 2), device=dev, dtype=torch.int64)
+    rc = lib.advchain_surface_dice(_ptr(pred), _ptr(target), samp, _ptr(thr), max(tol), _DICE_ROUTES[route], _ptr(out),
+                                   _ptr(within), _ptr(voxels), _ptr(ws), N, K, len(sp), dims, _stream())
+    if rc == -2:
+        raise _surface_dice_refused(N, K, sp, route)
+    _lib.check(rc, "surface_dice")
+    return SurfaceDice(out, within, voxels)
 
 
 # ---- connected components and the filters on them (csrc/seg_components.hip) ------------------------------------------------------

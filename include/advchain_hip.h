@@ -840,6 +840,40 @@ int advchain_surface_metrics(const int64_t* pred, const int64_t* target, const f
                              int64_t* overlap, float* dice, void* workspace, int64_t N, int64_t K, int ndim,
                              const int64_t* dims, void* stream);
 
+/* ---- surface Dice at a tolerance (NSD) of a pair of label maps, 2D and 3D (seg_surface.hip) -----------------------------------
+ * Not in the reference; MONAI's compute_surface_dice (voxel counts, not surface areas).  pred, target, A, B, the border dS, the
+ * directions and `sampling` as for advchain_surface_metrics above.  With a tolerance tau_k per class:
+ *   within (N,K,2) int64          c0 = #{a in dA: d(a, dB) <= tau_k}, c1 = #{b in dB: d(b, dA) <= tau_k}
+ *   surface_voxels (N,K,2) int64  m0 = |dA|, m1 = |dB| (the integers of advchain_surface_metrics)
+ *   surface_dice (N,K) fp32       (c0 + c1) / (m0 + m1) in fp64, rounded once; NaN when m0 + m1 == 0; 0 when exactly one border is
+ *                                 empty (every distance is +inf: nothing is within)
+ * `thresholds`: K 32-bit words in DEVICE memory, the squared tolerances as the comparison takes them (the ball rule of
+ * advchain_morph).  sampling NULL: int32 T_k = min(floor(tau_k^2), 2^30 - 1) and the test d^2 <= T_k is on exact integers
+ * (tau = 2 includes the squared length 4; sqrt(3) in double gives T = 2).  With a sampling: the bits of tau_k^2 rounded to fp32
+ * once (at most 1e29), compared with the fp32 squared distance of the transform, ((s_x dx)^2 + (s_y dy)^2) + (s_z dz)^2 without
+ * contraction: a tolerance equal to a multiple of the spacing can fall on either side.  `tolerance_max` (host): the largest
+ * tau_k; it bounds the search and chooses the route.  Two routes, equal bits:
+ *   1 "ball"    one kernel stages a tile of both maps with a halo of cap_a + 1 voxels in LDS, cap_a = min(floor(tau_max / s_a),
+ *               dims_a - 1), and every border voxel looks for a border voxel of its class of the other map inside the ball; cost
+ *               independent of K, no workspace.  Eligible iff K <= 65534 and a tile of (32,64) (16,64) (8,64) in 2D, (8,8,32)
+ *               (4,8,32) (4,4,32) (2,4,32) (2,2,32) in 3D with that halo, at 5 bytes a cell, fits 60 KiB of LDS.
+ *   2 "fields"  the edge pass and distance fields of advchain_surface_metrics, then one count pass key <= threshold; any
+ *               tolerance, the shape limits of advchain_surface_metrics.
+ * `route`: 0 dispatch (the ball where it is eligible and no cap exceeds 5 in 2D, 2 in 3D -- where it was measured to be the
+ * faster one -- else the fields, else the ball), 1 or 2 forces one.
+ * advchain_surface_dice_route: the route a call takes (1 or 2), host-only; ADVCHAIN_ERR_UNSUPPORTED where none can (a forced
+ * ball that is not eligible; a shape the fields refuse).  advchain_surface_dice_workspace: 4-byte words of `workspace` for that
+ * route (16-byte aligned, no clearing needed; 0 for the ball: `workspace` may be NULL), -1 where the call would be refused:
+ *   fields: 2 N K V + 4 N V + 6 N K.
+ * Integer atomics only, no memset, no host read-back: bitwise reproducible, capturable on one stream.                          */
+int advchain_surface_dice_route(int64_t N, int64_t K, int ndim, const int64_t* dims, const float* sampling, double tolerance_max,
+                                int route);
+int64_t advchain_surface_dice_workspace(int64_t N, int64_t K, int ndim, const int64_t* dims, const float* sampling,
+                                        double tolerance_max, int route); /* 4-byte words */
+int advchain_surface_dice(const int64_t* pred, const int64_t* target, const float* sampling, const void* thresholds,
+                          double tolerance_max, int route, float* surface_dice, int64_t* within, int64_t* surface_voxels,
+                          void* workspace, int64_t N, int64_t K, int ndim, const int64_t* dims, void* stream);
+
 /* ---- connected components of label maps and the filters on them, 2D and 3D (seg_components.hip) -----------------------------
  * Not in the reference.  labels (N, dims) int64, dims = (H, W) or (D, H, W).  Two voxels of an entry are adjacent when their
  * offsets differ by at most 1 on every axis and on at most `connectivity` axes (1 .. ndim: scipy's generate_binary_structure);
