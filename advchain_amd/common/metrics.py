@@ -1,5 +1,6 @@
 """Validation metrics of label maps on the device (not in the reference; csrc/seg_surface.hip on the distance fields of csrc/edt.hip):
-``surface_distance_metrics`` / ``hausdorff_distance`` / ``average_surface_distance`` / ``surface_dice``.
+``surface_distance_metrics`` / ``hausdorff_distance`` / ``average_surface_distance`` / ``surface_dice``, and (csrc/seg_components.hip)
+the instance-wise ``instance_metrics``; its definitions follow those of the voxel-wise metrics below.
 
 Definitions.  pred and target are int64 label maps (N, dims), dims = (H, W) or (D, H, W), K = num_classes.  For entry n and class
 k: A = {v : pred[n,v] == k} and B = {v : target[n,v] == k}.  A label outside [0, K), -100 included, belongs to no class (the rule
@@ -29,14 +30,48 @@ are empty.
 
 With unit spacing the squared distances are exact int32, roots, interpolation and means are taken in float64 and rounded to fp32
 once; every value is the same bits on every run, nothing is read back to the host, and the call can be captured in a graph.  There
-is no gradient: the inputs are detached."""
+is no gradient: the inputs are detached.
+
+Instance-wise detection (``instance_metrics``).  The metrics above score a class as one set of voxels; lesion, nodule, metastasis
+and cell tasks count objects instead (Metrics Reloaded, BraTS-METS, panoptic segmentation): how many were found, missed or
+invented, and how well the found ones were segmented.
+
+Components.  ``connectivity``, ``background``, foreground and component are exactly those of
+common.postprocess.connected_components(..., num_classes=K): a label outside [0, K), -100 included, or equal to ``background`` is
+in no component.  The class of a component is the label of its voxels.
+
+Per entry and class.  For entry n and class k, P is the set of components of class k in pred[n], T the same in target[n],
+nP = |P| and nT = |T|.  For a in P and b in T: I = |a n b| and U = |a| + |b| - I.  The pair overlaps when I >= 1.  Components of
+different classes never form a pair.
+
+Match rule.  A pair matches when IoU > iou_threshold, evaluated as (double)I > iou_threshold * (double)U: one fp64 product, one
+comparison.  iou_threshold is a finite number with 0.5 <= iou_threshold < 1 (Kirillov et al., Panoptic Segmentation; Metrics
+Reloaded's "Mask IoU > 0.5").  With the strict inequality and a threshold of at least 0.5 a component matches at most one
+partner: I > U / 2 >= |a| / 2, and the components of target are disjoint.  So the matches are a matching, no assignment problem
+arises, and TP is well defined.  IoU == 0.5 exactly does not match at the default.  Thresholds below 0.5 need an assignment step
+and are refused with a ValueError.
+
+Quantities.  TP is the number of matches, FP = nP - TP and FN = nT - TP.  iou_fixed is the sum over the matches of
+floor(2^32 I / U), taken as the integer division (I << 32) / U in unsigned 64-bit: an exact integer that does not depend on any
+order, below 2^63 (I < 2^31, fewer than 2^31 components).
+
+Quotients.  Every quotient is taken in float64 from these integers and rounded to fp32 once.  With S = (double)iou_fixed * 2^-32:
+
+    precision  TP / nP             NaN when nP == 0
+    recall     TP / nT             NaN when nT == 0
+    f1         2 TP / (nP + nT)    NaN when nP + nT == 0     (the recognition quality RQ)
+    sq         S / TP              NaN when TP == 0          (the segmentation quality: the mean IoU of the matches)
+    pq         2 S / (nP + nT)     NaN when nP + nT == 0     (the panoptic quality, sq * f1)
+
+The class equal to ``background`` has no components, so its row is all zeros and NaN."""
 import math
 
 import torch
 
 from .. import ops
-from ..ops import SurfaceDice, SurfaceMetrics  # noqa: F401
+from ..ops import InstanceMetrics, SurfaceDice, SurfaceMetrics  # noqa: F401
 from .loss import _check_num_classes, _check_sampling, _require_gpu
+from .postprocess import _check_labels
 
 
 def _check_maps(name, pred, target, num_classes, sampling):
@@ -133,3 +168,36 @@ def surface_dice(pred, target, num_classes, tolerance, sampling=None):
     _require_gpu(pred, "pred")
     _require_gpu(target, "target")
     return ops.surface_dice(pred, target, num_classes, tolerance, sampling=sampling)
+
+
+def instance_metrics(pred, target, num_classes, iou_threshold=0.5, connectivity=1, background=0, return_maps=False):
+    """Instance-wise detection metrics of every class of a pair of label maps: the connected components of both maps are matched
+    per class at IoU > ``iou_threshold`` (definitions: the module's docstring).  Returns InstanceMetrics, a namedtuple of device
+    tensors:
+
+        components     (N,K,2)   int64   nP, nT
+        matched        (N,K)     int64   TP; FP = nP - TP, FN = nT - TP
+        overlapping    (N,K,2)   int64   components of P that overlap at least one component of T, and of T that overlap at least
+                                         one of P (the "any overlap" detection count of lesion-wise reports)
+        iou_fixed      (N,K)     int64   the sum over the matches of floor(2^32 I / U)
+        precision, recall, f1, sq, pq    (N,K) fp32 each
+        pred_status, target_status       (N,dims) uint8 with return_maps=True, else None: 0 for a voxel in no component, 1 when
+                                         its component is matched, 2 when it is unmatched but overlaps a component of its class
+                                         in the other map, 3 when it overlaps none
+
+    iou_threshold: a finite number in [0.5, 1); num_classes at most 65535.  This is neither BraTS's lesion-wise Dice (which
+    dilates and merges lesions first) nor a Hungarian assignment (which thresholds below 0.5 would need).
+
+    The components are those of common.postprocess.connected_components; the overlaps of all pairs are counted on the device
+    in a hash table per entry that cannot overflow.  Every value is the same bits on every run; integer atomics only, nothing
+    is read back to the host, and the call can be captured in a graph.  There is no gradient: the inputs are detached."""
+    _check_maps("instance_metrics", pred, target, num_classes, None)
+    _check_labels("instance_metrics", pred, connectivity, background)
+    if isinstance(iou_threshold, bool) or not isinstance(iou_threshold, (int, float)) or not math.isfinite(iou_threshold) \
+            or iou_threshold < 0.5 or iou_threshold >= 1:
+        raise ValueError("instance_metrics: iou_threshold must be a finite number in [0.5, 1) (a lower one needs an assignment "
+                         "step), got %r" % (iou_threshold,))
+    _require_gpu(pred, "pred")
+    _require_gpu(target, "target")
+    return ops.instance_metrics(pred, target, num_classes, iou_threshold=float(iou_threshold), connectivity=connectivity,
+                                background=background, return_maps=bool(return_maps))

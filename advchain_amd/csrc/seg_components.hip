@@ -4,6 +4,7 @@
 //   advchain_keep_largest    <- common.postprocess.keep_largest_component
 //   advchain_remove_small    <- common.postprocess.remove_small_components
 //   advchain_fill_holes      <- common.postprocess.fill_holes, find_holes
+//   advchain_instance_match  <- common.metrics.instance_metrics (see "instance matching" below)
 //
 // Two voxels of an entry are adjacent when their offsets differ by at most 1 on every axis and on at most `connectivity` axes
 // (scipy's generate_binary_structure); adjacent voxels are connected when they carry the same label and that label is
@@ -560,6 +561,226 @@ k_hole_fill(const int64_t* __restrict__ labels, const int* __restrict__ parent, 
   }
 }
 
+// ---- instance matching --------------------------------------------------------------------------------------------------------
+// advchain_instance_match: k_cc_tile, k_cc_seam and k_cc_flatten<true> label pred and target, each into its own half of the
+// workspace: every voxel then holds the root of its component and every root its voxel count.  On top of them:
+//   k_inst_clear    the pair table (keys empty, counts 0) and the integer outputs (0).
+//   k_inst_pair     every voxel with a root in both maps and the same label in both adds 1 to the key (root in pred << 32) | root
+//                   in target of its entry's table; the roots of a map are counted per class and get a zero state word.
+//   k_inst_match    every used slot: I, |a|, |b| and the class give the overlap marks, the match rule and iou_fixed.
+//   k_inst_finish   the five quotients per (entry, class).
+//   k_inst_status   the status maps, from the state word of the root.
+// The table of an entry is open addressing with linear probing over `slots` = max(2 V, 64) slots: an entry has at most V
+// distinct pairs (a voxel adds to one key), so at least half of the slots stay empty, a probe always ends, and nothing
+// overflows.  A key is claimed by a 64-bit compare-and-swap on the empty word; a thread whose swap fails re-reads what the slot
+// holds now and adds there or moves on: nobody waits.  Which slot a key lands in depends on the order of arrival; the count of a
+// key, and everything k_inst_match derives from the set of (key, count), do not.
+constexpr u64 kEmptyKey = ~0ull;                 // (a root is below 2^31: no key has all bits set)
+constexpr int kOverlapBit = 1, kMatchBit = 2;    // the state word of a root
+
+__device__ __forceinline__ u64 inst_hash(u64 key) {
+  key ^= key >> 33;                              // (the finaliser of MurmurHash3: neighbouring roots spread over the table)
+  key *= 0xff51afd7ed558ccdull;
+  key ^= key >> 33;
+  key *= 0xc4ceb9fe1a85ec53ull;
+  key ^= key >> 33;
+  return key;
+}
+__device__ __forceinline__ u32 inst_slot(u64 hash, u32 slots) {
+  return (u32)(((hash >> 32) * (u64)slots) >> 32);                                        // < slots
+}
+
+__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// dst[k * stride] += the number of lanes with `is` set and class k, one atomic per class among the lanes of the wave (every
+// lane of the wave calls it)
+__device__ __forceinline__ void wave_count_by_class(bool is, int k, u64* dst, int stride, int lane) {
+  u64 todo = __ballot(is);
+  while (todo) {                                                                          // one turn per class: todo loses bits
+    const int k1 = __shfl(k, __builtin_ctzll(todo), 64);
+    const u64 same = __ballot(is && k == k1);
+    if (lane == 0) atomicAdd(dst + (int64_t)k1 * stride, (u64)__popcll(same));
+    todo &= ~same;
+  }
+}
+
+__global__ void __launch_bounds__(kBlock)
+k_inst_clear(u64* __restrict__ keys, u32* __restrict__ counts, int64_t table, u64* __restrict__ components,
+             u64* __restrict__ matched, u64* __restrict__ overlapping, u64* __restrict__ iou_fixed, int64_t NK) {
+  const int64_t threads = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < table; i += threads) {
+    keys[i] = kEmptyKey;
+    counts[i] = 0u;
+  }
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < NK; i += threads) {
+    components[2 * i] = components[2 * i + 1] = 0ull;
+    overlapping[2 * i] = overlapping[2 * i + 1] = 0ull;
+    matched[i] = 0ull;
+    iou_fixed[i] = 0ull;
+  }
+}
+
+// key += length in the table of an entry.  Ends: the table always has an empty slot.  A swap that fails has the slot's new key
+// in hand: ours (another thread claimed it for the same pair) or another's, and then the probe moves on.
+__device__ __forceinline__ void inst_add(u64* table, u32* count, u32 slots, u64 key, u32 length) {
+  u32 at = inst_slot(inst_hash(key), slots);
+  for (;;) {
+    u64 held = __hip_atomic_load(table + at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (held == kEmptyKey) held = atomicCAS(table + at, kEmptyKey, key);                  // (the old value: empty, ours or another's)
+    if (held == kEmptyKey || held == key) {
+      atomicAdd(count + at, length);
+      return;
+    }
+    at = at + 1u == slots ? 0u : at + 1u;
+  }
+}
+
+// The same in a table of kStageSlots slots in LDS, at most kStageProbes probes: false when they all hold other keys.
+constexpr int kStageSlots = 128, kStageProbes = 8;
+__device__ __forceinline__ bool inst_stage(u64* table, u32* count, u64 key, u32 length) {
+  u32 at = (u32)inst_hash(key) & (kStageSlots - 1);
+  for (int probe = 0; probe < kStageProbes; ++probe) {
+    u64 held = __hip_atomic_load(table + at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (held == kEmptyKey) held = atomicCAS(table + at, kEmptyKey, key);
+    if (held == kEmptyKey || held == key) {
+      atomicAdd(count + at, length);
+      return true;
+    }
+    at = (at + 1u) & (kStageSlots - 1);
+  }
+  return false;
+}
+
+// Chunked as k_cc_flatten.  A wave holds 64 consecutive voxels: the lanes in a row that carry the same key are a run (found by
+// one ballot, as the runs of equal labels in k_cc_tile), and the first lane of a run adds its length -- to a small table of the
+// workgroup in LDS first, whose used slots go to the entry's table at the end: the 2048 voxels of a chunk seldom hold more than
+// a few pairs, and the voxels that two large components share would otherwise queue an add per run on one word in global
+// memory (4 x 128 x 128 x 64 blobs: 192 us for this pass without the stage, 25 us with it).  A run that finds the stage full
+// goes to the entry's table itself: the stage changes how many adds a count is made of, never the count.
+__global__ void __launch_bounds__(kBlock)
+k_inst_pair(const int64_t* __restrict__ pred, const int64_t* __restrict__ target, const int* __restrict__ parent_p,
+            const int* __restrict__ parent_t, int* __restrict__ state_p, int* __restrict__ state_t, u64* keys, u32* counts,
+            u64* components, int64_t K, int64_t V, int64_t chunks, u32 slots) {
+  __shared__ u64 stage_key[kStageSlots];
+  __shared__ u32 stage_count[kStageSlots];
+  const Chunked c = chunk_of(chunks);
+  const int64_t e = c.n * V;
+  u64* table = keys + c.n * (int64_t)slots;
+  u32* count = counts + c.n * (int64_t)slots;
+  const int lane = threadIdx.x & 63;
+  if (threadIdx.x < kStageSlots) {
+    stage_key[threadIdx.x] = kEmptyKey;
+    stage_count[threadIdx.x] = 0u;
+  }
+  __syncthreads();
+  for (int j = 0; j < kPerThread; ++j) {
+    if (c.base + j * kBlock >= V) break;                                                  // (uniform)
+    const int64_t v = c.base + j * kBlock + threadIdx.x;
+    const int rp = v < V ? parent_p[e + v] : -1, rt = v < V ? parent_t[e + v] : -1;
+    const bool root_p = rp >= 0 && rp == (int)v, root_t = rt >= 0 && rt == (int)v;
+    // (a voxel with a root carries a class index: in [0, K))
+    const int kp = rp >= 0 ? (int)pred[e + v] : -1, kt = rt >= 0 ? (int)target[e + v] : -2;
+    if (root_p) state_p[e + v] = 0;
+    if (root_t) state_t[e + v] = 0;
+    wave_count_by_class(root_p, kp, components + 2 * c.n * K, 2, lane);
+    wave_count_by_class(root_t, kt, components + 2 * c.n * K + 1, 2, lane);
+    const u64 key = kp == kt ? ((u64)(u32)rp << 32) | (u64)(u32)rt : kEmptyKey;
+    const u64 left = __shfl_up(key, 1, 64);                                               // (every lane takes part)
+    const u64 heads = __ballot(lane == 0 || left != key);
+    if (key != kEmptyKey && ((heads >> lane) & 1ull)) {
+      const u64 behind = lane == 63 ? 0ull : heads >> (lane + 1);
+      const u32 length = behind ? (u32)__builtin_ctzll(behind) + 1u : (u32)(64 - lane);
+      if (!inst_stage(stage_key, stage_count, key, length)) inst_add(table, count, slots, key, length);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < kStageSlots && stage_key[threadIdx.x] != kEmptyKey)
+    inst_add(table, count, slots, stage_key[threadIdx.x], stage_count[threadIdx.x]);
+}
+
+// One slot per thread and turn.  The first marker of a root (the old value of the atomic OR says so) counts it as overlapping; a
+// root is matched at most once (iou_threshold >= 0.5), so the match counts need no such test.  The adds of a wave are summed per
+// class first.
+__global__ void __launch_bounds__(kBlock)
+k_inst_match(const int64_t* __restrict__ pred, const int* __restrict__ sizes_p, const int* __restrict__ sizes_t, int* state_p,
+             int* state_t, const u64* __restrict__ keys, const u32* __restrict__ counts, u64* matched, u64* overlapping,
+             u64* iou_fixed, double threshold, int64_t K, int64_t V, u32 slots, int64_t table) {
+  const int lane = threadIdx.x & 63;
+  const int64_t threads = (int64_t)gridDim.x * kBlock;
+  for (int64_t i0 = (int64_t)blockIdx.x * kBlock; i0 < table; i0 += threads) {           // (uniform: ballots inside)
+    const int64_t i = i0 + threadIdx.x;
+    const u64 key = i < table ? keys[i] : kEmptyKey;
+    const bool used = key != kEmptyKey;
+    int64_t nk = -1;
+    bool first_p = false, first_t = false, match = false;
+    u64 fixed = 0ull;
+    if (used) {
+      const int64_t n = i / slots, e = n * V;
+      const int64_t rp = (int64_t)(key >> 32), rt = (int64_t)(key & 0xffffffffull);
+      const u64 I = counts[i];
+      const u64 U = (u64)(u32)sizes_p[e + rp] + (u64)(u32)sizes_t[e + rt] - I;
+      nk = n * K + pred[e + rp];                                                          // (the label at a root is a class index)
+      match = (double)I > threshold * (double)U;
+      const int mark = match ? kOverlapBit | kMatchBit : kOverlapBit;
+      first_p = !(atomicOr(state_p + e + rp, mark) & kOverlapBit);
+      first_t = !(atomicOr(state_t + e + rt, mark) & kOverlapBit);
+      if (match) fixed = (I << 32) / U;
+    }
+    u64 todo = __ballot(used);
+    while (todo) {                                                                        // one turn per (entry, class)
+      const int64_t nk1 = __shfl(nk, __builtin_ctzll(todo), 64);
+      const bool same = used && nk == nk1;
+      const u64 np = __ballot(same && first_p), nt = __ballot(same && first_t), nm = __ballot(same && match);
+      const u64 sum = nm ? wave_sum_u64(same ? fixed : 0ull) : 0ull;                      // (nm is uniform)
+      if (lane == 0) {
+        if (np) atomicAdd(overlapping + 2 * nk1, (u64)__popcll(np));
+        if (nt) atomicAdd(overlapping + 2 * nk1 + 1, (u64)__popcll(nt));
+        if (nm) {
+          atomicAdd(matched + nk1, (u64)__popcll(nm));
+          atomicAdd(iou_fixed + nk1, sum);
+        }
+      }
+      todo &= ~__ballot(same);
+    }
+  }
+}
+
+// Every quotient in fp64 from the integers, rounded to fp32 once; 2 x and x 2^-32 are exact, so each is one division.
+__global__ void __launch_bounds__(kBlock)
+k_inst_finish(const int64_t* __restrict__ components, const int64_t* __restrict__ matched, const int64_t* __restrict__ iou_fixed,
+              float* __restrict__ precision, float* __restrict__ recall, float* __restrict__ f1, float* __restrict__ sq,
+              float* __restrict__ pq, int64_t NK) {
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const int64_t threads = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < NK; i += threads) {
+    const double np = (double)components[2 * i], nt = (double)components[2 * i + 1], tp = (double)matched[i];
+    const double S = (double)iou_fixed[i] * (1.0 / 4294967296.0);
+    precision[i] = (float)(np == 0.0 ? nan : tp / np);
+    recall[i] = (float)(nt == 0.0 ? nan : tp / nt);
+    f1[i] = (float)(np + nt == 0.0 ? nan : (2.0 * tp) / (np + nt));
+    sq[i] = (float)(tp == 0.0 ? nan : S / tp);
+    pq[i] = (float)(np + nt == 0.0 ? nan : (2.0 * S) / (np + nt));
+  }
+}
+
+// 0: in no component; 1: its component is matched; 2: unmatched, overlaps a component of its class; 3: overlaps none
+__global__ void __launch_bounds__(kBlock)
+k_inst_status(const int* __restrict__ parent, const int* __restrict__ state, uint8_t* __restrict__ out, int64_t V, int64_t chunks) {
+  const Chunked c = chunk_of(chunks);
+  const int64_t e = c.n * V;
+  for (int j = 0; j < kPerThread; ++j) {
+    const int64_t v = c.base + j * kBlock + threadIdx.x;
+    if (v >= V) break;
+    const int p = parent[e + v];
+    const int s = p < 0 ? 0 : state[e + p];
+    out[e + v] = (uint8_t)(p < 0 ? 0 : (s & kMatchBit) ? 1 : (s & kOverlapBit) ? 2 : 3);
+  }
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------------
 struct Plan {
   Shape s;
@@ -615,6 +836,15 @@ int components_label(const int64_t* labels, void* workspace, u64* winners, int64
   hipLaunchKernelGGL(k_cc_flatten<SIZES>, dim3(chunked), dim3(kBlock), 0, st, w->parent, w->sizes, w->counts, p.V, p.chunks);
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
+}
+
+// advchain_instance_match: the slots of an entry's pair table, and the words of the whole workspace (-1: refused): keys, counts,
+// the state words of both maps, the two labelling workspaces
+int64_t instance_plan(int64_t N, const Plan& p, int64_t* slots) {
+  *slots = 2 * p.V < 64 ? 64 : 2 * p.V;
+  if (N > 0x7fffffffLL / (3 * *slots)) return -1;
+  const int64_t total = 3 * N * *slots + 2 * N * p.V + 2 * p.total;
+  return total <= 0x7fffffffLL ? total : -1;
 }
 
 }  // namespace
@@ -733,6 +963,72 @@ int advchain_fill_holes(const int64_t* labels, int64_t* out, int64_t* fill, int6
                      (const int*)w.state, out, fill, (u64*)count, (u64*)voxels, K, max_size < 0 ? (int64_t)-1 : max_size, p.V,
                      p.chunks);
   ADVCHAIN_LAUNCH_CHECK();
+  return ADVCHAIN_OK;
+}
+
+int64_t advchain_instance_match_workspace(int64_t N, int ndim, const int64_t* dims) {
+  Plan p;
+  int64_t slots;
+  return components_plan(N, ndim, dims, &p) ? instance_plan(N, p, &slots) : -1;
+}
+
+int advchain_instance_match(const int64_t* pred, const int64_t* target, int64_t* components, int64_t* matched, int64_t* overlapping,
+                            int64_t* iou_fixed, float* precision, float* recall, float* f1, float* sq, float* pq,
+                            uint8_t* pred_status, uint8_t* target_status, void* workspace, int64_t N, int64_t K, int ndim,
+                            const int64_t* dims, int connectivity, int64_t background, double iou_threshold, void* stream) {
+  ADVCHAIN_CHECK_ARG(pred && target && components && matched && overlapping && iou_fixed && workspace,
+                     "instance_match: null pointer");
+  ADVCHAIN_CHECK_ARG(precision && recall && f1 && sq && pq, "instance_match: null pointer");
+  ADVCHAIN_CHECK_ARG((((uintptr_t)components | (uintptr_t)matched | (uintptr_t)overlapping | (uintptr_t)iou_fixed |
+                       (uintptr_t)workspace) & 7) == 0, "instance_match: the int64 outputs and the workspace must be 8-byte aligned");
+  ADVCHAIN_CHECK_ARG(K >= 1 && K <= 65535, "instance_match: K must be in 1..65535");
+  ADVCHAIN_CHECK_ARG(iou_threshold >= 0.5 && iou_threshold < 1.0, "instance_match: iou_threshold must be in [0.5, 1)");
+  COMPONENTS_CHECK_SHAPE("instance_match");
+  ADVCHAIN_CHECK_ARG(N <= ((int64_t)1 << 39) / K, "instance_match: bad N");
+  int64_t slots;
+  if (instance_plan(N, p, &slots) < 0) {
+    advchain_set_error_("instance_match: a workspace of more than 2^31 - 1 words");
+    return ADVCHAIN_ERR_UNSUPPORTED;
+  }
+  const int64_t table = N * slots, NK = N * K;
+  u64* keys = (u64*)workspace;
+  u32* counts = (u32*)(keys + table);
+  int* state_p = (int*)(counts + table);
+  int* state_t = state_p + N * p.V;
+  int* half_p = state_t + N * p.V;
+  int* half_t = half_p + p.total;
+  const unsigned chunked = (unsigned)(N * p.chunks);
+  const unsigned sweep = (unsigned)((table + kBlock - 1) / kBlock < 8192 ? (table + kBlock - 1) / kBlock : 8192);
+  hipLaunchKernelGGL(k_inst_clear, dim3(sweep), dim3(kBlock), 0, st, keys, counts, table, (u64*)components, (u64*)matched,
+                     (u64*)overlapping, (u64*)iou_fixed, NK);
+  ADVCHAIN_LAUNCH_CHECK();
+  Work wp, wt;
+  int rc = components_label<true>(pred, half_p, nullptr, 0, N, p, background, K, &wp, st);
+  if (rc != ADVCHAIN_OK) return rc;
+  rc = components_label<true>(target, half_t, nullptr, 0, N, p, background, K, &wt, st);
+  if (rc != ADVCHAIN_OK) return rc;
+  hipLaunchKernelGGL(k_inst_pair, dim3(chunked), dim3(kBlock), 0, st, pred, target, (const int*)wp.parent, (const int*)wt.parent,
+                     state_p, state_t, keys, counts, (u64*)components, K, p.V, p.chunks, (u32)slots);
+  ADVCHAIN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_inst_match, dim3(sweep), dim3(kBlock), 0, st, pred, (const int*)wp.sizes, (const int*)wt.sizes, state_p,
+                     state_t, (const u64*)keys, (const u32*)counts, (u64*)matched, (u64*)overlapping, (u64*)iou_fixed,
+                     iou_threshold, K, p.V, (u32)slots, table);
+  ADVCHAIN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_inst_finish, dim3((unsigned)((NK + kBlock - 1) / kBlock < 8192 ? (NK + kBlock - 1) / kBlock : 8192)),
+                     dim3(kBlock), 0, st,
+                     (const int64_t*)components, (const int64_t*)matched, (const int64_t*)iou_fixed, precision, recall, f1, sq, pq,
+                     NK);
+  ADVCHAIN_LAUNCH_CHECK();
+  if (pred_status) {
+    hipLaunchKernelGGL(k_inst_status, dim3(chunked), dim3(kBlock), 0, st, (const int*)wp.parent, (const int*)state_p, pred_status,
+                       p.V, p.chunks);
+    ADVCHAIN_LAUNCH_CHECK();
+  }
+  if (target_status) {
+    hipLaunchKernelGGL(k_inst_status, dim3(chunked), dim3(kBlock), 0, st, (const int*)wt.parent, (const int*)state_t,
+                       target_status, p.V, p.chunks);
+    ADVCHAIN_LAUNCH_CHECK();
+  }
   return ADVCHAIN_OK;
 }
 

@@ -2480,6 +2480,40 @@ def find_holes(labels, num_classes, connectivity=1, background=0, max_size=None)
     return _fill_holes("find_holes", labels, num_classes, connectivity, background, max_size, False, True)[1]
 
 
+InstanceMetrics = collections.namedtuple("InstanceMetrics", ["components", "matched", "overlapping", "iou_fixed", "precision",
+                                                             "recall", "f1", "sq", "pq", "pred_status", "target_status"])
+
+
+@_on_tensor_device
+def instance_metrics(pred, target, num_classes, iou_threshold=0.5, connectivity=1, background=0, return_maps=False):
+    """(N,dims) int64 label maps -> InstanceMetrics: the components of both maps matched per class at IoU > iou_threshold, their
+    counts and the detection quotients (include/advchain_hip.h: advchain_instance_match).  No gradient."""
+    pred = _dev_labels(pred.detach() if isinstance(pred, torch.Tensor) else pred, "pred")
+    target = _dev_labels(target.detach() if isinstance(target, torch.Tensor) else target, "target")
+    _same_device(pred, target)
+    if pred.shape != target.shape:
+        raise ValueError("instance_metrics: pred %s and target %s differ in shape" % (tuple(pred.shape), tuple(target.shape)))
+    N, K, sp, dev = pred.shape[0], int(num_classes), tuple(pred.shape[1:]), pred.device
+    lib = _lib.load()
+    dims = _lib.dims_array(sp)
+    n = lib.advchain_instance_match_workspace(N, len(sp), dims)
+    if n < 0:
+        raise NotImplementedError("instance_metrics: N=%d, spatial shape %s is too large (more than 2^31 - 1 voxels in an entry, or "
+                                  "a workspace of more than 2^31 - 1 words)" % (N, sp))
+    ws = torch.empty(int(n), device=dev, dtype=torch.int32)
+    components = torch.empty((N, K, 2), device=dev, dtype=torch.int64)
+    overlapping = torch.empty((N, K, 2), device=dev, dtype=torch.int64)
+    matched = torch.empty((N, K), device=dev, dtype=torch.int64)
+    iou_fixed = torch.empty((N, K), device=dev, dtype=torch.int64)
+    quotients = [torch.empty((N, K), device=dev, dtype=torch.float32) for _ in range(5)]
+    status = [torch.empty(pred.shape, device=dev, dtype=torch.uint8) if return_maps else None for _ in range(2)]
+    outputs = [components, matched, overlapping, iou_fixed] + quotients + status
+    _components_check(lib.advchain_instance_match(_ptr(pred), _ptr(target), *[_ptr(t) for t in outputs], _ptr(ws), N, K, len(sp),
+                                                  dims, int(connectivity), int(background), float(iou_threshold), _stream()),
+                      "instance_match")
+    return InstanceMetrics(*outputs)
+
+
 # ---- erosion, dilation, opening and closing with a Euclidean ball (csrc/seg_morph.hip) -----------------------------------------
 
 # The tiles of the morphology kernels by number of spatial axes; None: the axis is not tiled (k_morph_axis stages whole lines).

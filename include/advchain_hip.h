@@ -921,6 +921,35 @@ int64_t advchain_fill_holes_workspace(int64_t N, int ndim, const int64_t* dims);
 int advchain_fill_holes(const int64_t* labels, int64_t* out, int64_t* fill, int64_t* count, int64_t* voxels, void* workspace,
                         int64_t N, int64_t K, int ndim, const int64_t* dims, int connectivity, int64_t background,
                         int64_t max_size, void* stream);
+/* advchain_instance_match: instance-wise detection metrics of a pair of label maps (F1 / recognition quality, segmentation and
+ *           panoptic quality).  pred and target (N, dims) int64 are labelled by the passes above with num_classes = K, each into
+ *           its own part of the workspace.  Per entry n and class k: P and T are the components of class k of pred[n] and
+ *           target[n], nP = |P|, nT = |T|; for a in P and b in T, I = |a n b| and U = |a| + |b| - I; the pair overlaps when
+ *           I >= 1 and matches when (double)I > iou_threshold * (double)U (one fp64 product, one comparison).  iou_threshold in
+ *           [0.5, 1): with the strict inequality a component matches at most one partner, so the matches are a matching and no
+ *           assignment step exists.  Outputs, none needs clearing:
+ *             components (N,K,2) int64   nP, nT
+ *             matched (N,K) int64        TP, the number of matches (FP = nP - TP, FN = nT - TP)
+ *             overlapping (N,K,2) int64  components of P that overlap at least one of T, and of T that overlap at least one of P
+ *             iou_fixed (N,K) int64      the sum over the matches of (I << 32) / U in unsigned 64-bit integers: exact, below 2^63
+ *             precision, recall, f1, sq, pq (N,K) fp32   TP / nP, TP / nT, 2 TP / (nP + nT), S / TP, 2 S / (nP + nT) with
+ *                                        S = (double)iou_fixed 2^-32, each one fp64 division rounded to fp32 once; NaN when the
+ *                                        denominator is 0.  The row of k == background is zeros and NaN.
+ *             pred_status, target_status (N, dims) uint8 or NULL ("not wanted"): 0 in no component, 1 its component is matched,
+ *                                        2 unmatched but overlapping a component of its class of the other map, 3 overlapping none
+ *           The overlaps are counted in an open-addressing table per entry (64-bit keys (root in pred << 32) | root in target
+ *           claimed by compare-and-swap, linear probing, integer adds; a wave adds once per run of equal keys) of max(2 V, 64)
+ *           slots: an entry has at most V distinct pairs, so an empty slot always exists and nothing overflows.  K in 1 .. 65535.
+ *           Integer atomics only, no memset, no host read-back: the same bits on every run, capturable on one stream.
+ * `workspace` (8-byte aligned, no clearing needed): advchain_instance_match_workspace 4-byte words, host-only query, -1 where
+ *           advchain_components_workspace is or for more than 2^31 - 1 words; with V voxels per entry and S = max(2 V, 64) it is
+ *           N (3 S + 6 V + 2 ceil(V / 2048)): the table, a state word per voxel and map, two labelling workspaces.           */
+int64_t advchain_instance_match_workspace(int64_t N, int ndim, const int64_t* dims); /* 4-byte words */
+int advchain_instance_match(const int64_t* pred, const int64_t* target, int64_t* components, int64_t* matched,
+                            int64_t* overlapping, int64_t* iou_fixed, float* precision, float* recall, float* f1, float* sq,
+                            float* pq, uint8_t* pred_status, uint8_t* target_status, void* workspace, int64_t N, int64_t K,
+                            int ndim, const int64_t* dims, int connectivity, int64_t background, double iou_threshold,
+                            void* stream);
 
 /* ---- erosion, dilation, opening and closing of label maps with a Euclidean ball, 2D and 3D (seg_morph.hip) ---------------------
  * Not in the reference.  labels (N, dims) int64, dims = (H, W) or (D, H, W); K classes; `background` any integer.  A class voxel
