@@ -63,13 +63,46 @@ Quotients.  Every quotient is taken in float64 from these integers and rounded t
     sq         S / TP              NaN when TP == 0          (the segmentation quality: the mean IoU of the matches)
     pq         2 S / (nP + nT)     NaN when nP + nT == 0     (the panoptic quality, sq * f1)
 
-The class equal to ``background`` has no components, so its row is all zeros and NaN."""
+The class equal to ``background`` has no components, so its row is all zeros and NaN.
+
+Topology (``betti_numbers``, ``betti_error``).  None of the above sees whether a prediction has the right shape: a myocardium
+ring that is broken, a vessel with a spurious handle, a false cavity in a hollow organ.  The Betti error of the clDice and
+topology-preserving-loss literature does: |b_i(pred) - b_i(target)| per class for the Betti numbers b0 (components), b1 (loops;
+holes in 2D) and b2 (cavities).
+
+Sets.  labels is one int64 label map (N, dims).  For entry n and class k, A = {v : labels[n,v] == k}, for every k in [0, K),
+class 0 included: there is no ``background`` argument.  A label outside [0, K), -100 included, is in no class and in the
+complement of every class; labels are only compared after the range check.  Positions outside the image are in no class.
+
+Adjacency pair.  ``connectivity`` = c is the adjacency of A, in the sense of common.postprocess.connected_components; the
+complement of A gets the dual adjacency.  2D: c = 1 means 4-adjacency for A and 8 for the complement, c = 2 means 8 and 4.  3D:
+c = 1 means 6 and 26, c = 3 means 26 and 6; c = 2 (18-adjacency) has no such dual in 3D and is refused with a ValueError.  The
+default is 1, as everywhere in the package; thin structures (vessels, one voxel wide and running diagonally) want c = ndim.
+
+Euler characteristic chi.  Let p run over the lattice corners [0..D] x [0..H] x [0..W] ([0..H] x [0..W] in 2D).  The window of p is
+the voxels p - {0,1}^ndim; the one with coordinate p_a is "high on axis a", the one with p_a - 1 "low".  With [.] = 1 if true:
+
+    c = ndim (voxels are closed cubes)    chi = sum_p sum_{S subset of the axes} (-1)^|S| [some voxel of the window that is high on
+                                          every axis of S is in A]: S empty is the vertex at p, |S| = 1 an edge leaving p, |S| = 2
+                                          a face, S all axes the voxel p itself
+    c = 1 (the dual complex)              chi = sum_p sum_S (-1)^|S| [every voxel p - sum_{a in T} e_a, T subset of S, is in A]:
+                                          voxels - face pairs + 2 x 2 squares - 2 x 2 x 2 blocks
+
+Betti numbers.  b0 is the number of components of A under c.  cav is the number of components of the complement of A, under the
+dual adjacency, that contain no voxel with a coordinate 0 or size - 1 on any axis.  2D: b1 = b0 - chi and b2 = 0.  3D: b2 = cav
+and b1 = b0 + b2 - chi.  This is Euler-Poincare for the adjacency pairs above (Kong and Rosenfeld).  An empty class has
+(0, 0, 0) and chi = 0.  betti_error[n,k,i] = |b_i(pred) - b_i(target)|; there are no NaNs, everything is an integer.
+
+Cost.  One labelling of all classes and one streaming pass over the windows per map; in 3D one more labelling per class for the
+cavities, 1 + K labellings per map in all (2D needs none: b1 follows from chi).  The workspace is that of one labelling whatever K
+is.  Every value is the same bits on every run; integer atomics only, nothing is read back to the host, and the call can be
+captured in a graph.  There is no gradient: the inputs are detached."""
 import math
 
 import torch
 
 from .. import ops
-from ..ops import InstanceMetrics, SurfaceDice, SurfaceMetrics  # noqa: F401
+from ..ops import Betti, BettiError, InstanceMetrics, SurfaceDice, SurfaceMetrics  # noqa: F401
 from .loss import _check_num_classes, _check_sampling, _require_gpu
 from .postprocess import _check_labels
 
@@ -201,3 +234,49 @@ def instance_metrics(pred, target, num_classes, iou_threshold=0.5, connectivity=
     _require_gpu(target, "target")
     return ops.instance_metrics(pred, target, num_classes, iou_threshold=float(iou_threshold), connectivity=connectivity,
                                 background=background, return_maps=bool(return_maps))
+
+
+def _check_topology(name, maps, num_classes, connectivity):
+    for t, what in maps:
+        if not isinstance(t, torch.Tensor) or t.dim() not in (3, 4):
+            raise ValueError("%s expects 3-D (N,H,W) or 4-D (N,D,H,W) labels as %s" % (name, what))
+    first = maps[0][0]
+    if len(maps) == 2 and first.shape != maps[1][0].shape:
+        raise ValueError("%s: pred %s and target %s differ in shape" % (name, tuple(first.shape), tuple(maps[1][0].shape)))
+    if first.numel() == 0:
+        raise ValueError("%s: empty label map %s" % (name, tuple(first.shape)))
+    _check_num_classes(name, num_classes)
+    nd = first.dim() - 1
+    if isinstance(connectivity, bool) or not isinstance(connectivity, int) or connectivity < 1 or connectivity > nd:
+        raise ValueError("%s: connectivity must be an integer in 1..%d for %d spatial axes, got %r" % (name, nd, nd, connectivity))
+    if nd == 3 and connectivity == 2:
+        raise ValueError("%s: connectivity 2 (18-adjacency) has no dual adjacency for the complement in 3D; use 1 (6 and 26) or 3 "
+                         "(26 and 6)" % name)
+    for t, what in maps:
+        _require_gpu(t, what)
+
+
+def betti_numbers(labels, num_classes, connectivity=1):
+    """Betti numbers and Euler characteristic of every class of a label map (definitions: "Topology" in the module's docstring).
+    Returns Betti, a namedtuple of device tensors:
+
+        betti  (N,K,3)  int64   b0 (components), b1 (loops; holes in 2D), b2 (cavities; 0 in 2D)
+        euler  (N,K)    int64   chi
+
+    Every k in [0, num_classes) is a class, 0 included.  connectivity: 1 or ndim (2 is refused in 3D)."""
+    _check_topology("betti_numbers", [(labels, "labels")], num_classes, connectivity)
+    return ops.betti_numbers(labels, num_classes, connectivity=connectivity)
+
+
+def betti_error(pred, target, num_classes, connectivity=1):
+    """Betti error of every class of a pair of label maps (definitions: "Topology" in the module's docstring).  Returns
+    BettiError, a namedtuple of device tensors:
+
+        error  (N,K,3)    int64   |b_i(pred) - b_i(target)|, i = 0, 1, 2
+        total  (N,K)      int64   the sum of error over i
+        betti  (N,K,2,3)  int64   the Betti numbers of both maps; index 0 of the pair axis is pred
+        euler  (N,K,2)    int64   chi of both maps
+
+    Both maps go through one call and one workspace; the result equals that of two betti_numbers calls."""
+    _check_topology("betti_error", [(pred, "pred"), (target, "target")], num_classes, connectivity)
+    return ops.betti_error(pred, target, num_classes, connectivity=connectivity)

@@ -2514,6 +2514,51 @@ def instance_metrics(pred, target, num_classes, iou_threshold=0.5, connectivity=
     return InstanceMetrics(*outputs)
 
 
+Betti = collections.namedtuple("Betti", ["betti", "euler"])
+BettiError = collections.namedtuple("BettiError", ["error", "total", "betti", "euler"])
+
+
+def _betti(name, pred, target, num_classes, connectivity):
+    """betti (N,K,M,3), euler (N,K,M), error (N,K,3) or None; M = 1 without a target, else 2 with pred at index 0."""
+    pred = _dev_labels(pred.detach() if isinstance(pred, torch.Tensor) else pred, "labels" if target is None else "pred")
+    if target is not None:
+        target = _dev_labels(target.detach() if isinstance(target, torch.Tensor) else target, "target")
+        _same_device(pred, target)
+        if pred.shape != target.shape:
+            raise ValueError("%s: pred %s and target %s differ in shape" % (name, tuple(pred.shape), tuple(target.shape)))
+    N, K, sp, dev = pred.shape[0], int(num_classes), tuple(pred.shape[1:]), pred.device
+    M = 1 if target is None else 2
+    lib = _lib.load()
+    dims = _lib.dims_array(sp)
+    n = lib.advchain_betti_workspace(N, len(sp), dims)
+    if n < 0:
+        raise NotImplementedError("%s: N=%d, spatial shape %s is too large (more than 2^31 - 1 voxels in an entry, or a workspace "
+                                  "of more than 2^31 - 1 words)" % (name, N, sp))
+    ws = torch.empty(int(n), device=dev, dtype=torch.int32)
+    betti = torch.empty((N, K, M, 3), device=dev, dtype=torch.int64)
+    euler = torch.empty((N, K, M), device=dev, dtype=torch.int64)
+    error = torch.empty((N, K, 3), device=dev, dtype=torch.int64) if target is not None else None
+    _components_check(lib.advchain_betti(_ptr(pred), _ptr(target), _ptr(betti), _ptr(euler), _ptr(error), _ptr(ws), N, K, len(sp),
+                                         dims, int(connectivity), _stream()), "betti")
+    return betti, euler, error
+
+
+@_on_tensor_device
+def betti_numbers(labels, num_classes, connectivity=1):
+    """(N,dims) int64 labels -> Betti(betti int64 (N,K,3): b0, b1, b2; euler int64 (N,K)): the Betti numbers and the Euler
+    characteristic of every class in [0, num_classes) (include/advchain_hip.h: advchain_betti).  No gradient."""
+    betti, euler, _ = _betti("betti_numbers", labels, None, num_classes, connectivity)
+    return Betti(betti.squeeze(2), euler.squeeze(2))
+
+
+@_on_tensor_device
+def betti_error(pred, target, num_classes, connectivity=1):
+    """(N,dims) int64 label maps -> BettiError(error int64 (N,K,3): |b_i(pred) - b_i(target)|; total (N,K): its sum over i; betti
+    (N,K,2,3) and euler (N,K,2): those of both maps, pred at index 0).  No gradient."""
+    betti, euler, error = _betti("betti_error", pred, target, num_classes, connectivity)
+    return BettiError(error, error.sum(dim=2), betti, euler)
+
+
 # ---- erosion, dilation, opening and closing with a Euclidean ball (csrc/seg_morph.hip) -----------------------------------------
 
 # The tiles of the morphology kernels by number of spatial axes; None: the axis is not tiled (k_morph_axis stages whole lines).

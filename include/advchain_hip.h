@@ -950,6 +950,27 @@ int advchain_instance_match(const int64_t* pred, const int64_t* target, int64_t*
                             float* pq, uint8_t* pred_status, uint8_t* target_status, void* workspace, int64_t N, int64_t K,
                             int ndim, const int64_t* dims, int connectivity, int64_t background, double iou_threshold,
                             void* stream);
+/* advchain_betti: Betti numbers, Euler characteristic and Betti error of label maps.  pred and target (N, dims) int64; target may
+ *           be NULL (one map: M = 1), else M = 2 and map 0 is pred.  Per entry n and class k, for EVERY k in [0, K) (there is no
+ *           background): A = {v : label == k}; a label outside [0, K) is in no class and in the complement of every class;
+ *           positions outside the image are in no class.  `connectivity` c is the adjacency of A, its complement gets the dual
+ *           one: 2D c = 1: 4 and 8, c = 2: 8 and 4; 3D c = 1: 6 and 26, c = 3: 26 and 6; c = 2 in 3D (18) has no dual and is
+ *           refused (ADVCHAIN_ERR_ARG).  chi: the Euler characteristic of the cubical complex of A -- c = ndim: voxels are
+ *           closed cubes: vertices - edges + faces - cubes; c = 1: the dual complex: voxels - face pairs + 2x2 squares - 2x2x2
+ *           blocks that lie in A -- summed over the windows of the lattice corners in integers.  b0: the components of A under c.
+ *           cav: the components of the complement under the dual adjacency that hold no voxel with a coordinate 0 or size - 1.
+ *           2D: b1 = b0 - chi, b2 = 0.  3D: b2 = cav, b1 = b0 + b2 - chi.  Outputs, 8-byte aligned, none needs clearing:
+ *             betti (N,K,M,3) int64   b0, b1, b2
+ *             euler (N,K,M) int64     chi
+ *             error (N,K,3) int64 or NULL (only with a target)   |b_i(pred) - b_i(target)|
+ *           One labelling of all classes and one pass over the windows per map; in 3D one more labelling per class and map for
+ *           the cavities (1 + K in all), through the same workspace.  Sums per class are taken in LDS up to 2048 classes and
+ *           with global 64-bit integer atomics above.  K in 1 .. 65535.  Integer atomics only, no memset, no host read-back: the
+ *           same bits on every run, capturable on one stream.
+ * `workspace`: advchain_betti_workspace 4-byte words, host-only query: advchain_components_workspace, whatever K and M are.    */
+int64_t advchain_betti_workspace(int64_t N, int ndim, const int64_t* dims); /* 4-byte words */
+int advchain_betti(const int64_t* pred, const int64_t* target, int64_t* betti, int64_t* euler, int64_t* error, void* workspace,
+                   int64_t N, int64_t K, int ndim, const int64_t* dims, int connectivity, void* stream);
 
 /* ---- erosion, dilation, opening and closing of label maps with a Euclidean ball, 2D and 3D (seg_morph.hip) ---------------------
  * Not in the reference.  labels (N, dims) int64, dims = (H, W) or (D, H, W); K classes; `background` any integer.  A class voxel
