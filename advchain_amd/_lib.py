@@ -38,11 +38,15 @@ PROTOTYPES = {
     "advchain_affine_theta_bwd": (_I, [_P, _P, _F, _P, _P, _P, _L, _I, _P]),
     "advchain_tp_interp_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _F, _P, _P, _P]),
     "advchain_tp_interp_fwd_smoothed_pair": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _F, _P, _P, _F, _P]),
+    "advchain_tp_interp_fwd_smoothed_pair_rows": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _F, _P, _P, _F, _I, _P]),
     "advchain_band_reduce_axis": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _L, _F, _P]),
     "advchain_band_reduce_rows_dense": (_I, [_P, _P, _P, _P, _P, _L, _L, _L, _L, _F, _P]),
     "advchain_bias_field_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _F, _I, _F, _P]),
     "advchain_bias_field_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _F, _I, _F, _P]),
     "advchain_bias_rows_per_wg": (_I, [_P, _L]),
+    "advchain_set_tp_wide_loads": (None, [_I]),
+    "advchain_get_tp_wide_loads": (_I, []),
+    "advchain_tp_wide_band": (_I, [_L]),
     "advchain_bias_field_fwd_rows": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _F, _I, _F, _I, _P]),
     "advchain_bias_field_bwd_rows": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _F, _I, _F, _I, _P]),
     "advchain_bias_field_bwd_reduced": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _F, _I, _F, _P, _P, _L, _I, _P]),

@@ -13,6 +13,8 @@
 //                                     adv_transformation_base.py:151-155, adv_noise.py:56-63 etc.
 #include "sampler_common.h"
 
+#include <atomic>
+
 namespace advchain {
 
 constexpr int kBandMax = 8;
@@ -79,9 +81,96 @@ __host__ __device__ inline TpGeom tp_geom(int S2) {
 // VEC = 4 (S2 % 4 == 0, 16-byte aligned planes): a thread produces 4 consecutive x and hands them to the epilogue
 // together, which then moves 16 bytes per lane (these epilogues are pure streaming: their time is their number of
 // vector-memory instructions).  epi(i1, x, val) with val = float[VEC].
-template <int VEC, class Epi>
-__device__ __forceinline__ void tp_rows(const float* __restrict__ coef, const BandTables& T, const Dims& full, int i0,
-                                        int i1_begin, int i1_end, float* lds, Epi&& epi) {
+//
+// WB = 2 or 4 (VEC = 4 only): the innermost band is WB wide, known at compile time, and the tables come by 16-byte requests.
+// A thread's four columns are neighbours and w is laid out [S][B], so their bands are 16 bytes of start and 16 * WB bytes of w:
+// 1 + WB requests instead of 4 * (1 + WB) dword loads (at 16 rows a workgroup the 20 dword loads of a cubic band were half of
+// a thread's vector-memory instructions).  The row tables of the i1 chunk are contiguous too: threads 0..63 take a quad of
+// w1 each, threads 64..71 a quad of start.  The packed tables are only 4-byte aligned (bands.py concatenates the axes; in 2D
+// A2.w starts 1 + S1 * B floats into ftab): the quads are packed aligned(4) types like FloatPair (sampler_common.h) --
+// gfx950 under ROCm runs in unaligned access mode and the compiler emits global_load_dwordx4 for them.  A quad that would
+// reach past the end of its table is loaded element by element.  WB = 0: the dword loads, for every band width and VEC = 1.
+// The same values reach the same sums in the same order either way.
+struct __attribute__((packed, aligned(4))) IntQuad { int v[4]; };
+
+// Four consecutive 4-byte words from a 4-byte aligned address, of which the first n (1..) exist.
+__device__ __forceinline__ IntQuad tp_load_quad(const void* p, int n) {
+  IntQuad q;
+  if (n >= 4) {
+    q = *reinterpret_cast<const IntQuad*>(p);
+  } else {
+    const int* pi = reinterpret_cast<const int*>(p);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) q.v[j] = j < n ? pi[j] : 0;
+  }
+  return q;
+}
+
+// Start and weights of column group xg (columns 4 xg .. 4 xg + 3) by 16-byte requests.
+template <int WB>
+__device__ __forceinline__ void tp_load_cols_wide(const BandAxis& A2, int xg, int (&s2)[4], float (&w2)[4][WB]) {
+  const IntQuad s = *reinterpret_cast<const IntQuad*>(A2.start + xg * 4);
+  IntQuad w[WB];
+#pragma unroll
+  for (int j = 0; j < WB; ++j) w[j] = *reinterpret_cast<const IntQuad*>(A2.w + (xg * 4) * WB + 4 * j);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    s2[q] = s.v[q];
+#pragma unroll
+    for (int c = 0; c < WB; ++c) w2[q][c] = __int_as_float(w[(q * WB + c) / 4].v[(q * WB + c) % 4]);
+  }
+}
+
+// The table values a workgroup of tp_run needs, in registers: request() issues the loads, tp_run() consumes them.  A kernel
+// with work of its own in front of the rows (k_tp_interp_fwd_gs: the smoothing) requests first, so that the two global round
+// trips overlap instead of following each other.
+template <int VEC, int WB>
+struct TpReq {
+  static_assert(WB == 0 || (VEC == 4 && (WB == 2 || WB == 4)), "wide band loads: VEC = 4, bands of 2 or 4");
+  static constexpr int NW = WB ? WB : kBandMax;
+  int s0;
+  int s2f[VEC];
+  float w2f[VEC][NW];
+  IntQuad rowq;      // WB != 0: the thread's quad of the row tables (threads 0..63: w1, 64..71: start)
+
+  __device__ __forceinline__ void request(const BandTables& T, const Dims& full, int i0, int i1_begin, int i1_end) {
+    const BandAxis& A0 = T.a[0];
+    const BandAxis& A1 = T.a[1];
+    const BandAxis& A2 = T.a[2];
+    const int ncol = full.s2 / VEC;
+    int XT = 64;
+    if (VEC > 1) { XT = 1; while (XT < ncol && XT < 64) XT *= 2; }
+    const int tx = threadIdx.x % XT;
+    if constexpr (WB != 0) {
+      const int nrow = i1_end - i1_begin;                  // <= kTpChunk: at most 64 quads of w1 and 8 of start
+      const int t = threadIdx.x;
+      rowq = IntQuad{{0, 0, 0, 0}};
+      if (t < 64) {
+        const int n = nrow * A1.B - 4 * t;
+        if (n > 0) rowq = tp_load_quad(A1.w + i1_begin * A1.B + 4 * t, n);
+      } else if (t < 64 + kTpChunk / 4) {
+        const int n = nrow - 4 * (t - 64);
+        if (n > 0) rowq = tp_load_quad(A1.start + i1_begin + 4 * (t - 64), n);
+      }
+      s0 = A0.start[i0];
+      tp_load_cols_wide<WB>(A2, min(tx, ncol - 1), s2f, w2f);
+    } else {
+      s0 = A0.start[i0];
+#pragma unroll
+      for (int q = 0; q < VEC; ++q) {
+        const int col = min(tx * VEC + q, full.s2 - 1);
+        s2f[q] = A2.start[col];
+#pragma unroll
+        for (int c = 0; c < kBandMax; ++c) w2f[q][c] = c < A2.B ? A2.w[col * A2.B + c] : 0.f;
+      }
+    }
+  }
+};
+
+template <int VEC, int WB, class Epi>
+__device__ __forceinline__ void tp_run(const float* __restrict__ coef, const BandTables& T, const Dims& full, int i0,
+                                       int i1_begin, int i1_end, float* lds, TpReq<VEC, WB>& rq, bool requested, Epi&& epi) {
+  constexpr int NW = TpReq<VEC, WB>::NW;
   const BandAxis& A0 = T.a[0];
   const BandAxis& A1 = T.a[1];
   const BandAxis& A2 = T.a[2];
@@ -99,22 +188,32 @@ __device__ __forceinline__ void tp_rows(const float* __restrict__ coef, const Ba
   __shared__ int s1_s[kTpChunk];
   __shared__ float w1_s[kTpChunk * kBandMax];
   const int nrow = i1_end - i1_begin;                      // <= kTpChunk
-  for (int e = threadIdx.x; e < nrow * (A1.B + 1); e += kBlock) {
-    const int r = e / (A1.B + 1), b = e - r * (A1.B + 1);
-    if (b == 0) s1_s[r] = A1.start[i1_begin + r];
-    else w1_s[r * kBandMax + b - 1] = A1.w[(i1_begin + r) * A1.B + b - 1];
+  if constexpr (WB != 0) {
+    if (!requested) rq.request(T, full, i0, i1_begin, i1_end);
+    const int t = threadIdx.x;
+    if (t < 64) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int e = 4 * t + j;
+        if (e < nrow * A1.B) w1_s[(e / A1.B) * kBandMax + e % A1.B] = __int_as_float(rq.rowq.v[j]);
+      }
+    } else if (t < 64 + kTpChunk / 4) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int e = 4 * (t - 64) + j;
+        if (e < nrow) s1_s[e] = rq.rowq.v[j];
+      }
+    }
+  } else {
+    for (int e = threadIdx.x; e < nrow * (A1.B + 1); e += kBlock) {
+      const int r = e / (A1.B + 1), b = e - r * (A1.B + 1);
+      if (b == 0) s1_s[r] = A1.start[i1_begin + r];
+      else w1_s[r * kBandMax + b - 1] = A1.w[(i1_begin + r) * A1.B + b - 1];
+    }
+    if (!requested) rq.request(T, full, i0, i1_begin, i1_end);
   }
-  const int s0 = A0.start[i0];
+  const int s0 = rq.s0;
   const float* w0 = A0.w + i0 * A0.B;
-  int s2f[VEC];
-  float w2f[VEC][kBandMax];
-#pragma unroll
-  for (int q = 0; q < VEC; ++q) {
-    const int col = min(tx * VEC + q, full.s2 - 1);
-    s2f[q] = A2.start[col];
-#pragma unroll
-    for (int c = 0; c < kBandMax; ++c) w2f[q][c] = c < A2.B ? A2.w[col * A2.B + c] : 0.f;
-  }
   __syncthreads();
   // rows blended per phase: as many as the LDS buffer holds (with 4 rows per phase a workgroup paid two barriers and a
   // dependent start[] -> coef[] load chain per 4 rows: 52 us for a 50 MB write at 4x3x128x128x64)
@@ -148,17 +247,30 @@ __device__ __forceinline__ void tp_rows(const float* __restrict__ coef, const Ba
     // registers for all rows (per-row table loads were a dependent global-load chain in the inner loop)
     for (int xg = tx; xg < ncol; xg += XT) {
       int s2[VEC];
-      float w2[VEC][kBandMax];
+      float w2[VEC][NW];
+      if constexpr (WB != 0) {
+        if (xg == tx) {             // (requested before the first barrier)
 #pragma unroll
-      for (int q = 0; q < VEC; ++q) {
-        if (xg == tx) {           // (requested before the first barrier)
-          s2[q] = s2f[q];
+          for (int q = 0; q < VEC; ++q) {
+            s2[q] = rq.s2f[q];
 #pragma unroll
-          for (int c = 0; c < kBandMax; ++c) w2[q][c] = w2f[q][c];
+            for (int c = 0; c < NW; ++c) w2[q][c] = rq.w2f[q][c];
+          }
         } else {
-          s2[q] = A2.start[xg * VEC + q];
+          tp_load_cols_wide<NW>(A2, xg, s2, w2);
+        }
+      } else {
 #pragma unroll
-          for (int c = 0; c < kBandMax; ++c) w2[q][c] = c < A2.B ? A2.w[(xg * VEC + q) * A2.B + c] : 0.f;
+        for (int q = 0; q < VEC; ++q) {
+          if (xg == tx) {           // (requested before the first barrier)
+            s2[q] = rq.s2f[q];
+#pragma unroll
+            for (int c = 0; c < kBandMax; ++c) w2[q][c] = rq.w2f[q][c];
+          } else {
+            s2[q] = A2.start[xg * VEC + q];
+#pragma unroll
+            for (int c = 0; c < kBandMax; ++c) w2[q][c] = c < A2.B ? A2.w[(xg * VEC + q) * A2.B + c] : 0.f;
+          }
         }
       }
       for (int r = ry; r < RPP; r += ROWS) {
@@ -169,8 +281,8 @@ __device__ __forceinline__ void tp_rows(const float* __restrict__ coef, const Ba
         for (int q = 0; q < VEC; ++q) {
           float v = 0.f;
 #pragma unroll
-          for (int c = 0; c < kBandMax; ++c)
-            if (c < A2.B) v += w2[q][c] * lds[r * g2 + s2[q] + c];
+          for (int c = 0; c < NW; ++c)
+            if (WB != 0 || c < A2.B) v += w2[q][c] * lds[r * g2 + s2[q] + c];
           val[q] = v;
         }
         epi(i1, xg * VEC, val);
@@ -178,6 +290,13 @@ __device__ __forceinline__ void tp_rows(const float* __restrict__ coef, const Ba
     }
     __syncthreads();
   }
+}
+
+template <int VEC, int WB, class Epi>
+__device__ __forceinline__ void tp_rows(const float* __restrict__ coef, const BandTables& T, const Dims& full, int i0,
+                                        int i1_begin, int i1_end, float* lds, Epi&& epi) {
+  TpReq<VEC, WB> rq;
+  tp_run<VEC, WB>(coef, T, full, i0, i1_begin, i1_end, lds, rq, false, epi);
 }
 
 // Where a workgroup's partial of the step-count norm goes.  An empty ORD pack (every default-mode launch): a float atomic
@@ -203,7 +322,7 @@ static __global__ void __launch_bounds__(kBlock) k_tp_partials_sum(const float* 
 
 // out[plane][v] = (add_identity ? identity_coord(channel) : 0) + scale * interp ; optional sum of interp^2
 // (64 slot accumulators, or one partial per workgroup: tp_sumsq_put) for the 3D step-count rule.  grid = (i1 chunks, S0, planes).
-template <int VEC, class... ORD>
+template <int VEC, int WB, class... ORD>
 __global__ void __launch_bounds__(kBlock)
 k_tp_interp_fwd(const float* __restrict__ coef, float* __restrict__ out, BandTables T, Dims full, int C,
                 int add_identity, float scale, float* __restrict__ sumsq, float* __restrict__ disp_out) {
@@ -217,7 +336,7 @@ k_tp_interp_fwd(const float* __restrict__ coef, float* __restrict__ out, BandTab
   float sq[1] = {0.f};
   float dmax = 0.f;
   const float to_vox = fabsf(scale) * 0.5f * (float)((c == 0 ? full.s2 : (c == 1 ? full.s1 : full.s0)) - 1);
-  tp_rows<VEC>(coef + (int64_t)plane * G, T, full, i0, i1b, i1e, lds, [&](int i1, int x, const float (&val)[VEC]) {
+  tp_rows<VEC, WB>(coef + (int64_t)plane * G, T, full, i0, i1b, i1e, lds, [&](int i1, int x, const float (&val)[VEC]) {
     float o[VEC];
 #pragma unroll
     for (int q = 0; q < VEC; ++q) {
@@ -244,17 +363,21 @@ k_tp_interp_fwd(const float* __restrict__ coef, float* __restrict__ out, BandTab
 // 2 x 9-tap smoothing of its <= 1024 values, which is nothing next to its 32 rows of output.
 constexpr int kGsFuseMax = 1024;
 struct GaussW9 { float w[9]; };
-template <int VEC>
+template <int VEC, int WB>
 __global__ void __launch_bounds__(kBlock)
 k_tp_interp_fwd_gs(const float* __restrict__ vel, float* __restrict__ s1, float* __restrict__ out, BandTables T, Dims full, int C,
-                   int add_identity, float scale, float* __restrict__ disp_out, GaussW9 gw, float gscale, int P) {
+                   int add_identity, float scale, float* __restrict__ disp_out, GaussW9 gw, float gscale, int P, int rows) {
   __shared__ float lds[kTpMaxLds];
   __shared__ float gs[2][kGsFuseMax];
   const int plane = blockIdx.z, i0 = blockIdx.y;
-  const int i1b = blockIdx.x * kTpChunk, i1e = min(i1b + kTpChunk, full.s1);
+  const int i1b = blockIdx.x * rows, i1e = min(i1b + rows, full.s1);      // rows <= kTpChunk (launcher)
   const int g1 = T.a[1].g, g2 = T.a[2].g, Vg = g1 * g2;        // (2D: a trivial leading axis)
   const int V = (int)full.voxels();
   const int c = plane % C;
+  // the wide form asks for its tables before the smoothing, which they do not depend on: one global round trip a workgroup
+  // instead of two in a row (the dword form keeps its order: tables behind the smoothing)
+  TpReq<VEC, WB> rq;
+  if constexpr (WB != 0) rq.request(T, full, i0, i1b, i1e);
   {
     const float* src = vel + (int64_t)(plane % P) * Vg;
     const float sc = plane >= P ? -gscale : gscale;
@@ -282,7 +405,7 @@ k_tp_interp_fwd_gs(const float* __restrict__ vel, float* __restrict__ s1, float*
   }
   float dmax = 0.f;
   const float to_vox = fabsf(scale) * 0.5f * (float)((c == 0 ? full.s2 : (c == 1 ? full.s1 : full.s0)) - 1);
-  tp_rows<VEC>(gs[0], T, full, i0, i1b, i1e, lds, [&](int i1, int x, const float (&val)[VEC]) {
+  tp_run<VEC, WB>(gs[0], T, full, i0, i1b, i1e, lds, rq, WB != 0, [&](int i1, int x, const float (&val)[VEC]) {
     float o[VEC];
 #pragma unroll
     for (int q = 0; q < VEC; ++q) {
@@ -763,7 +886,7 @@ __device__ __forceinline__ float bias_value(float L, int use_log, float eps, flo
 // kTpChunk = 32 of the interpolation kernels a 32 x 256 x 256 launch was 256 workgroups, one a CU (16.4 us; 14.4 us with two).
 // A voxel's value depends on its row's blend and its column's band, not on the workgroup that computes it: same bits.
 // grid = (ceil(S1 / rows), S0, N)
-template <int VEC>
+template <int VEC, int WB>
 __global__ void __launch_bounds__(kBlock)
 k_bias_fwd(const float* __restrict__ cp, const float* __restrict__ data, float* __restrict__ out,
            float* __restrict__ field, BandTables T, Dims full, int C, float eps, int use_log, float cp_scale, int rows) {
@@ -772,7 +895,7 @@ k_bias_fwd(const float* __restrict__ cp, const float* __restrict__ data, float* 
   const int i1b = blockIdx.x * rows, i1e = min(i1b + rows, full.s1);
   const int64_t G = (int64_t)T.a[0].g * T.a[1].g * T.a[2].g;
   const int V = (int)full.voxels();
-  tp_rows<VEC>(cp + (int64_t)n * G, T, full, i0, i1b, i1e, lds, [&](int i1, int x, const float (&val)[VEC]) {
+  tp_rows<VEC, WB>(cp + (int64_t)n * G, T, full, i0, i1b, i1e, lds, [&](int i1, int x, const float (&val)[VEC]) {
     const int v = (i0 * full.s1 + i1) * full.s2 + x;
     float b[VEC];
 #pragma unroll
@@ -804,7 +927,7 @@ k_bias_fwd(const float* __restrict__ cp, const float* __restrict__ data, float* 
 // with the first loads of the kernel and put into LDS after tp_rows' last barrier.  Dynamic LDS: Wd[g2 * WB] (rounded up to
 // 4 floats), then the slab.  VEC = 4 only.
 constexpr int kBiasRedWq = kBrMaxW / 4 / kBlock;      // float4 of the dense table per thread at most
-template <int VEC, bool RED>
+template <int VEC, bool RED, int TW>      // TW: the WB of tp_run
 __global__ void __launch_bounds__(kBlock)
 k_bias_bwd(const float* __restrict__ cp, const float* __restrict__ data, const float* __restrict__ gout,
            float* __restrict__ gL, float* __restrict__ gdata, BandTables T, Dims full, int C, float eps, int use_log,
@@ -832,7 +955,7 @@ k_bias_bwd(const float* __restrict__ cp, const float* __restrict__ data, const f
     }
     if (threadIdx.x < g2) lo_r = lo_g[threadIdx.x];
   }
-  tp_rows<VEC>(cp + (int64_t)n * G, T, full, i0, i1b, i1e, lds, [&](int i1, int x, const float (&val)[VEC]) {
+  tp_rows<VEC, TW>(cp + (int64_t)n * G, T, full, i0, i1b, i1e, lds, [&](int i1, int x, const float (&val)[VEC]) {
     const int v = (i0 * full.s1 + i1) * full.s2 + x;
     float b[VEC], e[VEC], sgo[VEC];
     bool pass[VEC];
@@ -1657,6 +1780,18 @@ static bool unpack_tables(const int32_t* itab, const float* ftab, const int64_t*
   return true;
 }
 
+// Which form of the band-table loads the VEC = 4 kernels built on tp_run take: the compile-time innermost band width (2 or 4:
+// 16-byte requests) or 0 (dword loads: every other width, and everything while advchain_set_tp_wide_loads(0) holds -- tests
+// and tools compare the two forms in one process; the results are the same bits).
+static std::atomic<int> g_tp_wide{1};
+extern "C" int advchain_tp_wide_band(int64_t B2);
+static int tp_wide_band(const BandTables& T) {
+  return advchain_tp_wide_band(T.a[2].B);
+}
+// LAUNCH(WB) with the band width tp_wide_band picked as a compile-time constant
+#define TP_WIDE_GO(WB_, LAUNCH) \
+  switch (WB_) { case 2: { LAUNCH(2); } break; case 4: { LAUNCH(4); } break; default: { LAUNCH(0); } break; }
+
 // advchain_tp_interp_fwd (ORD empty) and the first stage of advchain_tp_interp_sumsq_ordered (ORD = SumsqOrdered): the same
 // choice of kernel either way.  `nwg`: the number of workgroups launched.
 template <class... ORD>
@@ -1690,17 +1825,27 @@ static int tp_interp_fwd_launch(const float* coef, float* out, const int32_t* it
   }
   *nwg = (int64_t)grid.x * grid.y * grid.z;
   // short rows (S2 < 128) leave a thread only two rows to amortise the bands of its 4 columns: measured slower (3D 53 -> 61 us)
-  if (full.s2 % 4 == 0 && full.s2 >= 128 && (reinterpret_cast<uintptr_t>(out) & 15) == 0)
-    hipLaunchKernelGGL((k_tp_interp_fwd<4, ORD...>), grid, dim3(kBlock), 0, (hipStream_t)stream, coef, out, T, full, (int)C,
-                       add_identity, scale, sumsq, disp_out);
-  else
-    hipLaunchKernelGGL((k_tp_interp_fwd<1, ORD...>), grid, dim3(kBlock), 0, (hipStream_t)stream, coef, out, T, full, (int)C,
+  if (full.s2 % 4 == 0 && full.s2 >= 128 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
+#define TP_GO(WB_) hipLaunchKernelGGL((k_tp_interp_fwd<4, WB_, ORD...>), grid, dim3(kBlock), 0, (hipStream_t)stream, coef, out, T, full, (int)C, \
+                                      add_identity, scale, sumsq, disp_out)
+    TP_WIDE_GO(tp_wide_band(T), TP_GO)
+#undef TP_GO
+  } else
+    hipLaunchKernelGGL((k_tp_interp_fwd<1, 0, ORD...>), grid, dim3(kBlock), 0, (hipStream_t)stream, coef, out, T, full, (int)C,
                        add_identity, scale, sumsq, disp_out);
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
 }
 
 extern "C" {
+
+// Test and tool switch (process-wide, like advchain_set_deterministic): 0 keeps every kernel built on tp_run on the dword table
+// loads, anything else (the default) lets bands of 2 and 4 take the 16-byte requests.
+void advchain_set_tp_wide_loads(int on) { g_tp_wide.store(on ? 1 : 0, std::memory_order_relaxed); }
+int advchain_get_tp_wide_loads(void) { return g_tp_wide.load(std::memory_order_relaxed); }
+// Host-only: the band width whose 16-byte form a table with innermost band B2 takes right now where a thread produces four
+// columns (2 or 4), or 0 for the dword loads.
+int advchain_tp_wide_band(int64_t B2) { return (g_tp_wide.load(std::memory_order_relaxed) && (B2 == 2 || B2 == 4)) ? (int)B2 : 0; }
 
 int advchain_tp_interp_fwd(const float* coef, float* out, const int32_t* itab, const float* ftab, const int64_t* S,
                            const int64_t* g, const int64_t* B, int64_t planes, int64_t C, int ndim, int add_identity,
@@ -1738,12 +1883,17 @@ int advchain_tp_interp_sumsq_ordered(const float* coef, const int32_t* itab, con
 // smoothed batch [v; -v]) and out (2P planes of S1 x S2) = (add_identity ? identity : 0) + scale * up(s1).  2D, planes of at most
 // 1024 values, the 9-tap window.  ADVCHAIN_ERR_UNSUPPORTED (-2), nothing enqueued, for anything else: issue the two calls.
 // (kTpChunk = 32 rows a workgroup stays: with the rows as a run-time argument 128 planes of 256 x 256 took 22.9 us at 32 rows,
-// 29.4 at 16 and 28.2 at 64 as two chunks of the row loop -- profiles/r20/gauss_lanes.)
-int advchain_tp_interp_fwd_smoothed_pair(const float* vel, float* s1, float* out, const int32_t* itab, const float* ftab,
-                                         const int64_t* S, const int64_t* g, const int64_t* B, int64_t P, int64_t C,
-                                         int add_identity, float scale, float* disp_out, const float* weights9, float gscale,
-                                         void* stream) {
+// 29.4 at 16 and 28.2 at 64 as two chunks of the row loop -- profiles/r20/gauss_lanes; with the tables by 16-byte requests
+// 16.7 at 32, 19.9 at 16, 26.0 at 8 -- profiles/r31/tp_bands: every workgroup of a plane repeats the smoothing.)  The _rows
+// entry takes the value as an argument (0: kTpChunk) for that sweep; the entry without it passes 0.
+int advchain_tp_interp_fwd_smoothed_pair_rows(const float* vel, float* s1, float* out, const int32_t* itab, const float* ftab,
+                                              const int64_t* S, const int64_t* g, const int64_t* B, int64_t P, int64_t C,
+                                              int add_identity, float scale, float* disp_out, const float* weights9, float gscale,
+                                              int rows_per_wg, void* stream) {
   ADVCHAIN_CHECK_ARG(vel && out && itab && ftab && weights9, "tp_interp_fwd_smoothed_pair: null pointer");
+  ADVCHAIN_CHECK_ARG(rows_per_wg == 0 || rows_per_wg == 4 || rows_per_wg == 8 || rows_per_wg == 16 || rows_per_wg == 32,
+                     "tp_interp_fwd_smoothed_pair: rows_per_wg must be 0, 4, 8, 16 or 32");
+  const int rows = rows_per_wg ? rows_per_wg : kTpChunk;
   ADVCHAIN_CHECK_ARG(P >= 0 && 2 * P < 65536 && C >= 1, "tp_interp_fwd_smoothed_pair: bad planes/C");
   BandTables T;
   ADVCHAIN_CHECK_ARG(unpack_tables(itab, ftab, S, g, B, T), "tp_interp_fwd_smoothed_pair: bad band tables");
@@ -1753,15 +1903,25 @@ int advchain_tp_interp_fwd_smoothed_pair(const float* vel, float* s1, float* out
   ADVCHAIN_CHECK_ARG(full.voxels() < (1ll << 31), "tp_interp_fwd_smoothed_pair: volume too large");
   GaussW9 gw;
   for (int k = 0; k < 9; ++k) gw.w[k] = weights9[k];
-  dim3 grid((unsigned)((full.s1 + kTpChunk - 1) / kTpChunk), 1u, (unsigned)(2 * P));
-  if (full.s2 % 4 == 0 && full.s2 >= 128 && (reinterpret_cast<uintptr_t>(out) & 15) == 0)
-    hipLaunchKernelGGL(k_tp_interp_fwd_gs<4>, grid, dim3(kBlock), 0, (hipStream_t)stream, vel, s1, out, T, full, (int)C, add_identity,
-                       scale, disp_out, gw, gscale, (int)P);
-  else
-    hipLaunchKernelGGL(k_tp_interp_fwd_gs<1>, grid, dim3(kBlock), 0, (hipStream_t)stream, vel, s1, out, T, full, (int)C, add_identity,
-                       scale, disp_out, gw, gscale, (int)P);
+  dim3 grid((unsigned)((full.s1 + rows - 1) / rows), 1u, (unsigned)(2 * P));
+  if (full.s2 % 4 == 0 && full.s2 >= 128 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
+#define TP_GO(WB_) hipLaunchKernelGGL((k_tp_interp_fwd_gs<4, WB_>), grid, dim3(kBlock), 0, (hipStream_t)stream, vel, s1, out, T, full, (int)C, \
+                                      add_identity, scale, disp_out, gw, gscale, (int)P, rows)
+    TP_WIDE_GO(tp_wide_band(T), TP_GO)
+#undef TP_GO
+  } else
+    hipLaunchKernelGGL((k_tp_interp_fwd_gs<1, 0>), grid, dim3(kBlock), 0, (hipStream_t)stream, vel, s1, out, T, full, (int)C, add_identity,
+                       scale, disp_out, gw, gscale, (int)P, rows);
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
+}
+
+int advchain_tp_interp_fwd_smoothed_pair(const float* vel, float* s1, float* out, const int32_t* itab, const float* ftab,
+                                         const int64_t* S, const int64_t* g, const int64_t* B, int64_t P, int64_t C,
+                                         int add_identity, float scale, float* disp_out, const float* weights9, float gscale,
+                                         void* stream) {
+  return advchain_tp_interp_fwd_smoothed_pair_rows(vel, s1, out, itab, ftab, S, g, B, P, C, add_identity, scale, disp_out, weights9,
+                                                   gscale, 0, stream);
 }
 
 // One adjoint pass along `axis` (0..2 of the padded 3-axis view).  in: (outer, S_axis, inner) -> out: (outer, g_axis, inner)
@@ -1860,7 +2020,9 @@ int advchain_band_reduce_rows_dense(const float* in, const float* in2, float* ou
 // start and the weights of its four columns, 20 vector loads -- costs as much as about seven rows of the forward's epilogue, so
 // fewer rows a workgroup is more prologue per byte: at 32 x 256 x 256 the forward takes 16.3 / 14.4 / 16.6 / 25.7 us at 32 / 16 /
 // 8 / 4 rows (256 / 512 / 1024 / 2048 workgroups), at 4 x 128 x 128 x 64 30.8 / 49.4 / 91.7 / 174.7 us (2048 .. 16384).  One
-// workgroup a CU is the only grid that more workgroups beat.
+// workgroup a CU is the only grid that more workgroups beat.  With the tables by 16-byte requests (tp_run, WB = 4: 5 loads for
+// the 20) the same sweep reads 10.9 / 9.9 / 10.6 / 12.2 us and 16.4 / 19.8 / 29.8 / 50.0 us (profiles/r31/tp_bands): every
+// value faster, the curve flatter, the same value best at either shape -- the rule stays.
 constexpr int64_t kBiasMinWg = 512;
 static int bias_rows_rule(int64_t S0, int64_t S1, int64_t N) {
   for (int rows = 32; rows > 4; rows /= 2)
@@ -1891,11 +2053,13 @@ int advchain_bias_field_fwd_rows(const float* cp, const float* data, float* out,
   const int rows = rows_per_wg ? rows_per_wg : bias_rows_rule(S[0], S[1], N);
   ADVCHAIN_CHECK_ARG(S[0] < 65536 && (S[1] + rows - 1) / rows < (1ll << 31), "bias_field_fwd: grid too large");
   dim3 grid((unsigned)((full.s1 + rows - 1) / rows), (unsigned)full.s0, (unsigned)N);
-  if (full.s2 % 4 == 0 && ((reinterpret_cast<uintptr_t>(data) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(field)) & 15) == 0)
-    hipLaunchKernelGGL(k_bias_fwd<4>, grid, dim3(kBlock), 0, (hipStream_t)stream, cp, data, out, field, T, full, (int)C, eps,
-                       use_log, cp_scale, rows);
-  else
-    hipLaunchKernelGGL(k_bias_fwd<1>, grid, dim3(kBlock), 0, (hipStream_t)stream, cp, data, out, field, T, full, (int)C, eps,
+  if (full.s2 % 4 == 0 && ((reinterpret_cast<uintptr_t>(data) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(field)) & 15) == 0) {
+#define TP_GO(WB_) hipLaunchKernelGGL((k_bias_fwd<4, WB_>), grid, dim3(kBlock), 0, (hipStream_t)stream, cp, data, out, field, T, full, (int)C, eps, \
+                                      use_log, cp_scale, rows)
+    TP_WIDE_GO(tp_wide_band(T), TP_GO)
+#undef TP_GO
+  } else
+    hipLaunchKernelGGL((k_bias_fwd<1, 0>), grid, dim3(kBlock), 0, (hipStream_t)stream, cp, data, out, field, T, full, (int)C, eps,
                        use_log, cp_scale, rows);
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
@@ -1925,11 +2089,13 @@ int advchain_bias_field_bwd_rows(const float* cp, const float* data, const float
   ADVCHAIN_CHECK_ARG(S[0] < 65536 && (S[1] + rows - 1) / rows < (1ll << 31), "bias_field_bwd: grid too large");
   dim3 grid((unsigned)((full.s1 + rows - 1) / rows), (unsigned)full.s0, (unsigned)N);
   if (full.s2 % 4 == 0 && ((reinterpret_cast<uintptr_t>(data) | reinterpret_cast<uintptr_t>(grad_out) |
-                            reinterpret_cast<uintptr_t>(grad_L) | reinterpret_cast<uintptr_t>(grad_data)) & 15) == 0)
-    hipLaunchKernelGGL((k_bias_bwd<4, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, cp, data, grad_out, grad_L, grad_data, T,
-                       full, (int)C, eps, use_log, cp_scale, rows, (float*)nullptr, (const float*)nullptr, (const int*)nullptr, 0);
-  else
-    hipLaunchKernelGGL((k_bias_bwd<1, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, cp, data, grad_out, grad_L, grad_data, T,
+                            reinterpret_cast<uintptr_t>(grad_L) | reinterpret_cast<uintptr_t>(grad_data)) & 15) == 0) {
+#define TP_GO(WB_) hipLaunchKernelGGL((k_bias_bwd<4, false, WB_>), grid, dim3(kBlock), 0, (hipStream_t)stream, cp, data, grad_out, grad_L, grad_data, T, \
+                                      full, (int)C, eps, use_log, cp_scale, rows, (float*)nullptr, (const float*)nullptr, (const int*)nullptr, 0)
+    TP_WIDE_GO(tp_wide_band(T), TP_GO)
+#undef TP_GO
+  } else
+    hipLaunchKernelGGL((k_bias_bwd<1, false, 0>), grid, dim3(kBlock), 0, (hipStream_t)stream, cp, data, grad_out, grad_L, grad_data, T,
                        full, (int)C, eps, use_log, cp_scale, rows, (float*)nullptr, (const float*)nullptr, (const int*)nullptr, 0);
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
@@ -1975,8 +2141,10 @@ int advchain_bias_field_bwd_reduced(const float* cp, const float* data, const fl
   ADVCHAIN_CHECK_ARG(full.voxels() < (1ll << 31), "bias_field_bwd_reduced: volume too large");
   ADVCHAIN_CHECK_ARG(S[0] < 65536 && (S[1] + rows - 1) / rows < (1ll << 31), "bias_field_bwd_reduced: grid too large");
   dim3 grid((unsigned)((full.s1 + rows - 1) / rows), (unsigned)full.s0, (unsigned)N);
-  hipLaunchKernelGGL((k_bias_bwd<4, true>), grid, dim3(kBlock), lds, (hipStream_t)stream, cp, data, grad_out, (float*)nullptr,
-                     grad_data, T, full, (int)C, eps, use_log, cp_scale, rows, t1, wd, (const int*)lo, (int)WB);
+#define TP_GO(WB_) hipLaunchKernelGGL((k_bias_bwd<4, true, WB_>), grid, dim3(kBlock), lds, (hipStream_t)stream, cp, data, grad_out, (float*)nullptr, \
+                                      grad_data, T, full, (int)C, eps, use_log, cp_scale, rows, t1, wd, (const int*)lo, (int)WB)
+  TP_WIDE_GO(tp_wide_band(T), TP_GO)
+#undef TP_GO
   ADVCHAIN_LAUNCH_CHECK();
   return ADVCHAIN_OK;
 }

@@ -235,6 +235,17 @@ def is_deterministic():
     return bool(_lib.load().advchain_get_deterministic())
 
 
+def set_tp_wide_loads(on):
+    """Process-wide: whether the row-blended kernels (raw_tp_interp, the smoothed pair, the bias field) fetch bands of 2 and
+    4 by 16-byte requests (the default) or every band by dword loads (advchain_set_tp_wide_loads; the composite entries of
+    demons_compose.cpp follow it too).  The same bits either way: tests and tools compare the two forms in one process."""
+    _lib.load().advchain_set_tp_wide_loads(1 if on else 0)
+
+
+def tp_wide_loads():
+    return bool(_lib.load().advchain_get_tp_wide_loads())
+
+
 def _scatter_workspace(N, dims, device):
     n = _lib.load().advchain_scatter_workspace(N, len(dims), _lib.dims_array(dims))
     return torch.empty(n, device=device, dtype=torch.int32)

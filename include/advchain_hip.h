@@ -379,6 +379,12 @@ int advchain_tp_interp_fwd_smoothed_pair(const float* vel, float* s1, float* out
                                          const int64_t* S, const int64_t* g, const int64_t* B, int64_t P, int64_t C,
                                          int add_identity, float scale, float* disp_out, const float* weights9, float gscale,
                                          void* stream);
+/* The same with the i1 rows a workgroup takes as an argument: rows_per_wg in {4, 8, 16, 32}, or 0 for the library's choice
+ * (32; the entry above passes 0).  Every output bit is the same whatever the value -- for the row sweeps of the tools.       */
+int advchain_tp_interp_fwd_smoothed_pair_rows(const float* vel, float* s1, float* out, const int32_t* itab, const float* ftab,
+                                              const int64_t* S, const int64_t* g, const int64_t* B, int64_t P, int64_t C,
+                                              int add_identity, float scale, float* disp_out, const float* weights9, float gscale,
+                                              int rows_per_wg, void* stream);
 /* adjoint along one axis: in (outer, S_axis, inner) -> out (outer, g_axis, inner),
  * out = W_axis^T ((in - in2) * scale); in2 may be NULL.
  * replaces: upsample_{bi,tri}linear backward / conv_transpose backward w.r.t. its input.        */
@@ -392,6 +398,14 @@ int advchain_band_reduce_axis(const float* in, const float* in2, float* out, con
  * Same sums in the same order as that entry. */
 int advchain_band_reduce_rows_dense(const float* in, const float* in2, float* out, const float* wd, const int32_t* lo,
                                     int64_t rows, int64_t S, int64_t g, int64_t WB, float scale, void* stream);
+/* How the row-blended kernels (advchain_tp_interp_fwd, _smoothed_pair, the bias field entries below) fetch their band tables
+ * where a thread produces four columns: 16-byte requests for innermost bands of 2 or 4 (the default), or dword loads for
+ * every band (on = 0).  Process-wide, host-only; every output bit is the same either way -- for tests and tools that compare
+ * the two forms in one process.                                                                                              */
+void advchain_set_tp_wide_loads(int on);
+int advchain_get_tp_wide_loads(void);
+/* The band width whose 16-byte form a table with innermost band B2 takes at the moment (2 or 4), 0 for the dword loads. */
+int advchain_tp_wide_band(int64_t B2);
 
 /* ---- bias field ------------------------------------------------------------------------
  * replaces: AdvBias.compute_smoothed_bias + clip_bias + multiply, adv_bias.py:279-356,186:

@@ -203,6 +203,40 @@ def main():
     add("affine_warp fwd+bwd C=4", aff_fb, (32 + 48) * NV)
     add("tp_interp (phi0 init)", lambda: ops.raw_tp_interp(t.param, tabs, d, add_identity=True, scale=1 / 256.), 4 * d * NV)
     add("tp_adjoint (upsample bwd)", lambda: ops.raw_tp_adjoint(gq, tabs, gfull2=gq, scale=1 / 256.), 8 * d * NV)
+    if d == 2:
+        # the banded row-blended kernels of a cfg-2 step (fields.hip: tp_run), with the bytes each has to move: the paired field
+        # written (2 N d planes; the <= 1024-value velocity planes are nothing), data in and data * field and the field out,
+        # data and the gradient in and grad_data out (t1, N x S1 x g2, is 1/64 of a plane)
+        from advchain_amd import _lib as _l
+        from advchain_amd.augmentor import AdvBias
+        tb = AdvBias(2, dict(epsilon=0.3, control_point_spacing=[s // 2 for s in dims], downscale=2, data_size=[N, 1] + list(dims),
+                             interpolation_order=3, init_mode="random", space="log"), device=dev)
+        tb.init_parameters()
+        btab, cp = tb._tables, tb.param.detach().clone()
+        bt = (ops._ptr(btab.itab), ops._ptr(btab.ftab), _l.dims_array(btab.S), _l.dims_array(btab.g), _l.dims_array(btab.B))
+        mt = (ops._ptr(tabs.itab), ops._ptr(tabs.ftab), _l.dims_array(tabs.S), _l.dims_array(tabs.g), _l.dims_array(tabs.B))
+        blib, bst = _l.load(), ops._stream()
+        vel = t.param.detach().contiguous()
+        s1p = torch.empty((2 * N,) + tuple(vel.shape[1:]), device=dev)
+        php = torch.empty((2 * N, d) + tuple(dims), device=dev)
+        bout, bfield, bgd = torch.empty_like(x1), torch.empty_like(x1), torch.empty_like(x1)
+        wd_, lo_, WB_ = btab.dense_inner
+        bt1 = torch.empty((N, 1, dims[0], int(btab.g[2])), device=dev)
+
+        def up_pair():
+            _l.check(blib.advchain_tp_interp_fwd_smoothed_pair(ops._ptr(vel), ops._ptr(s1p), ops._ptr(php), *mt, N * d, d, 1, 1 / 256.,
+                                                               None, ops._GAUSS9, 1.5, bst), "smoothed_pair")
+
+        def bias_f():
+            _l.check(blib.advchain_bias_field_fwd(ops._ptr(cp), ops._ptr(x1), ops._ptr(bout), ops._ptr(bfield), *bt, N, 1, 0.3, 1, 1.0,
+                                                  bst), "bias_fwd")
+
+        def bias_b():
+            _l.check(blib.advchain_bias_field_bwd_reduced(ops._ptr(cp), ops._ptr(x1), ops._ptr(g1), ops._ptr(bt1), ops._ptr(bgd), *bt, N, 1,
+                                                          0.3, 1, 1.0, ops._ptr(wd_), ops._ptr(lo_), WB_, 0, bst), "bias_bwd_reduced")
+        add("tp_interp smoothed pair (k_tp_interp_fwd_gs), %d planes" % (2 * N * d), up_pair, 8 * d * NV)
+        add("bias_field fwd (k_bias_fwd)", bias_f, 12 * NV)
+        add("bias_field bwd reduced (k_bias_bwd<., true>)", bias_b, 12 * NV)
     add("axpy", lambda: ops.raw_axpy(x1, g1, 0.5), 12 * NV)
     add("normalized_axpy", lambda: ops.normalized_axpy(x1, g1, 1.0), 20 * NV)
     from advchain_amd.common.loss import calc_segmentation_consistency

@@ -31,8 +31,8 @@ ENTRIES = {   # entry -> (regexes of the kernels an entry launch runs, regex of 
     "advchain_tp_interp_fwd": ([r"k_tp_interp_fwd<"], r"k_tp_interp_fwd<"),
     "advchain_band_reduce_axis": ([r"k_band_reduce"], r"k_band_reduce"),
     "advchain_bias_field_fwd": ([r"k_bias_field_fwd|k_bias_fwd"], r"k_bias_field_fwd|k_bias_fwd"),
-    "advchain_bias_field_bwd": ([r"k_bias_field_bwd|k_bias_bwd<\d, false>|k_bias_bwd<\d>"], r"k_bias_field_bwd|k_bias_bwd<\d, false>|k_bias_bwd<\d>"),
-    "advchain_bias_field_bwd_reduced": ([r"k_bias_bwd<\d, true>"], r"k_bias_bwd<\d, true>"),      # (grad_L stays in LDS)
+    "advchain_bias_field_bwd": ([r"k_bias_field_bwd|k_bias_bwd<\d, false[,>]|k_bias_bwd<\d>"], r"k_bias_field_bwd|k_bias_bwd<\d, false[,>]|k_bias_bwd<\d>"),
+    "advchain_bias_field_bwd_reduced": ([r"k_bias_bwd<\d, true[,>]"], r"k_bias_bwd<\d, true[,>]"),      # (grad_L stays in LDS)
     "advchain_consistency_fwd": ([r"k_softmax_diff", r"k_edge_fwd"], r"k_softmax_diff"),
     "advchain_consistency_bwd": ([r"k_consistency_bwd"], r"k_consistency_bwd"),
     "advchain_axpy": ([r"k_axpy"], r"k_axpy"),
