@@ -107,6 +107,11 @@ PROTOTYPES = {
     "advchain_dice_workspace": (_L, [_L, _L, _I, _P]),
     "advchain_dice_fwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _F, _F, _F, _P]),
     "advchain_dice_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _F, _F, _P]),
+    "advchain_skeleton_workspace": (_L, [_L, _L, _I, _P, _I, _I]),
+    "advchain_soft_skeleton_fwd": (_I, [_P, _P, _P, _L, _L, _I, _P, _I, _I, _P]),
+    "advchain_soft_skeleton_bwd": (_I, [_P, _P, _P, _P, _L, _L, _I, _P, _I, _P]),
+    "advchain_cldice_fwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _I, _I, _F, _P]),
+    "advchain_cldice_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _P]),
     "advchain_edt": (_I, [_P, _I, _P, _I, _P, _L, _I, _P, _P]),
     "advchain_signed_maps_workspace": (_L, [_L, _L, _I, _P]),
     "advchain_signed_maps": (_I, [_P, _P, _P, _P, _L, _L, _I, _P, _P]),

@@ -33,6 +33,7 @@ PER_FILE_FLAGS = {
     "seg_boundary.hip": ["-ffp-contract=off"],          # the same
     "edt.hip": ["-ffp-contract=off"],                   # f + (s delta)^2 rounds the same in every pass and tiling
     "seg_morph.hip": ["-ffp-contract=off"],             # its fp32 fields round as those of edt.hip, in every pass
+    "seg_skeleton.hip": ["-ffp-contract=off"],          # one rounding per operation of the pooling composition (bitwise)
     "seg_surface.hip": ["-ffp-contract=off"],           # x_j + g (x_j1 - x_j) in fp64 as written: numpy's expression
 }
 

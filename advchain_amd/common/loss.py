@@ -2,7 +2,8 @@
 ``contour_loss`` / ``One_Hot`` / ``cross_entropy_2D`` (loss.py:102-220, 252-326, on csrc/seg_loss.hip); ``dice_loss`` /
 ``dice_ce_loss`` / ``cross_entropy_3D`` (not in the reference; csrc/seg_dice.hip) complete the supervised loss of a 2D or 3D step;
 ``distance_transform_edt`` / ``signed_distance_maps`` / ``boundary_loss`` (not in the reference; csrc/edt.hip, csrc/seg_boundary.hip)
-are the exact Euclidean distance maps of masks and label maps on the device and the boundary loss on them.
+are the exact Euclidean distance maps of masks and label maps on the device and the boundary loss on them;
+``soft_skeletonize`` / ``cldice_loss`` (not in the reference; csrc/seg_skeleton.hip) are the soft skeletons and the soft-clDice loss.
 
 'mse', 'contour' and 'kl' all run in the fused HIP kernels (:func:`advchain_amd.ops.consistency_sums`:
 softmax + mask + squared error + KL sum + 3^d edge stencils in two launches forward, one backward per operand that
@@ -302,6 +303,72 @@ def dice_ce_loss(input, target, weight=None, ignore_background=False, batch_dice
     _dice_arguments("dice_ce_loss", input, target, weight, ignore_background, smooth, (dice_weight, ce_weight))
     return ops.dice_loss(input, target, weight=weight, ignore_background=ignore_background, batch_dice=batch_dice,
                          smooth=smooth, dice_weight=dice_weight, ce_weight=ce_weight)
+
+
+# ---- soft skeletons and the soft-clDice loss (not in the reference; csrc/seg_skeleton.hip) ---------------------------------------
+
+def _check_iterations(name, iterations):
+    if isinstance(iterations, bool) or not isinstance(iterations, int) or not 0 <= iterations <= ops.SKELETON_MAX_ITERATIONS:
+        raise ValueError("%s: iterations must be an int in [0, %d], got %r" % (name, ops.SKELETON_MAX_ITERATIONS, iterations))
+
+
+def soft_skeletonize(maps, iterations=3):
+    """Soft skeleton of probability maps (Shit et al., clDice, CVPR 2021; csrc/seg_skeleton.hip).  maps: (N,C,H,W) or
+    (N,C,D,H,W) fp32; every plane is skeletonised on its own; returns fp32 of the same shape.  With E the minimum over a voxel
+    and its in-image face neighbours, D the maximum over the in-image 3x3(x3) box (a position outside the image is nothing):
+
+        skel = relu(x - D(E(x)));  iterations times:  x <- E(x),  delta = relu(x - D(E(x))),  skel <- skel + relu(delta - skel delta)
+
+    each operation rounded once in fp32: bit for bit the published max_pool composition.  iterations: an int in [0, 32].
+    Differentiable with respect to maps: the gradient of this composition with relu'(0) = 0 and, among equal window values, the
+    first winning (E: centre, then axis by axis, minus before plus; D: centre, then raster order) -- on hard masks this
+    differs from torch's tie rules (INTEGRATION.md "Known deviations").  Bitwise reproducible."""
+    if not isinstance(maps, torch.Tensor) or maps.dim() not in (4, 5):
+        raise ValueError("soft_skeletonize expects 4-D (N,C,H,W) or 5-D (N,C,D,H,W) maps")
+    _check_iterations("soft_skeletonize", iterations)
+    if maps.dtype != torch.float32:
+        raise ValueError("soft_skeletonize: maps must be float32, got %s" % maps.dtype)
+    if maps.size(1) > MAX_CLASSES:
+        raise NotImplementedError("soft_skeletonize takes at most %d channels, got %d" % (MAX_CLASSES, maps.size(1)))
+    _require_gpu(maps, "maps")
+    return ops.soft_skeletonize(maps, iterations=iterations)
+
+
+def cldice_loss(input, target, iterations=3, weight=None, ignore_background=True, batch=False, smooth=1.0):
+    """soft-clDice loss of logits (Shit et al., CVPR 2021; csrc/seg_skeleton.hip): the centerline Dice of the soft skeletons
+    (:func:`soft_skeletonize`) of prediction and target.  input: (N,K,H,W) or (N,K,D,H,W) fp32 or bf16 logits, read as they are,
+    the softmax over K runs inside the kernels (float16 is refused); target: (N,dims) int64 labels or a (N,K,dims) fp32 soft
+    target, a constant (one that requires a gradient is refused).  With p = softmax(input), t the one-hot labels (a label
+    outside [0, K), -100 included, is in no class) or the soft target, m = 0 where the label is -100 and 1 elsewhere (m masks the
+    summands only: those voxels still take part in the neighbourhoods), S^p = skel(p), S^t = skel(t) per plane, and sums over
+    the voxels of batch entry n (batch: over the whole batch, N -> 1)
+
+        Tprec_nk = (sum m S^p_k t_k + smooth) / (sum m S^p_k + smooth),  Tsens_nk = (sum m S^t_k p_k + smooth) / (sum m S^t_k + smooth)
+        loss = 1 - (1/rows) sum_nk omega_k 2 Tprec_nk Tsens_nk / (Tprec_nk + Tsens_nk),   omega_k = w_k / sum of the counted w_j
+
+    Class 0 is not counted with ignore_background.  With K = 2, ignore_background=True, batch=True and smooth=1 this is the
+    published ``soft_cldice`` exactly.  smooth == 0 with an empty skeleton gives NaN.  iterations: an int in [0, 32].  Returns an
+    fp32 scalar, bitwise reproducible; the gradient has the logits' dtype (computed in fp32, rounded once) and follows the tie
+    rule of :func:`soft_skeletonize`.  Combine with Dice as ``(1 - a) * dice_loss(x, y) + a * cldice_loss(x, y)``."""
+    _check_iterations("cldice_loss", iterations)
+    if isinstance(input, torch.Tensor) and input.dtype == torch.float16:
+        raise ValueError("cldice_loss: logits must be float32 or bfloat16, got torch.float16")
+    if isinstance(target, torch.Tensor) and target.is_floating_point() and target.requires_grad and torch.is_grad_enabled():
+        raise ValueError("cldice_loss: the target is a constant and gets no gradient (detach it)")
+    if isinstance(input, torch.Tensor) and isinstance(target, torch.Tensor) and input.dim() in (4, 5):
+        if target.dim() == input.dim() - 1:
+            want = (input.shape[0],) + tuple(input.shape[2:])
+            if tuple(target.shape) != want:
+                raise ValueError("cldice_loss: label target must be %s, got %s" % (want, tuple(target.shape)))
+        elif target.dim() == input.dim():
+            if target.shape != input.shape:
+                raise ValueError("cldice_loss: soft target must have the input's shape %s, got %s"
+                                 % (tuple(input.shape), tuple(target.shape)))
+        else:
+            raise NotImplementedError("cldice_loss: target must be (N,dims) labels or (N,C,dims) soft targets")
+    _dice_arguments("cldice_loss", input, target, weight, ignore_background, smooth)
+    return ops.cldice_loss(input, target, iterations=iterations, weight=weight, ignore_background=bool(ignore_background),
+                           batch=bool(batch), smooth=float(smooth))
 
 
 # ---- Euclidean distance maps and the boundary loss (not in the reference; csrc/edt.hip, csrc/seg_boundary.hip) -------------------

@@ -195,6 +195,9 @@ TILED_SCATTER = True  # LDS-tiled owner-computes scatter (False: global-atomic k
 FUSED_LOSS = True     # the consistency loss straight from the logits (no P / D intermediates); False: A/B tests
 WIDE_LOSS_MIN_K = 17  # class counts from here on take the run-time-K loss kernels (loss_lp.hip: any K < 65536, no P / D); below:
                       # the K <= 16 kernels of loss.hip, unchanged.  Tests and tools lower it to compare the two implementations
+SKELETON_FUSED_MAX_ITERATIONS = 4   # ADVCHAIN_SKELETON_FUSED_MAX: soft skeletons of up to this many iterations can run as one LDS-tile
+                      # launch (seg_skeleton.hip); beyond, and for volumes, level by level with the same bits
+SKELETON_MAX_ITERATIONS = 32        # ADVCHAIN_SKELETON_MAX_ITERATIONS
 REF_GRAD_REG_MAX_K = 4  # the gradient w.r.t. the reference (loss_ref.hip) keeps K = 2..this many classes in registers (at most 4);
                       # 0: the run-time-K form for every class count.  Tests and tools lower it to compare the two forms
 FUSE_2D = True        # the leading sub-pixel squarings of a 2D chain in one launch (expo_fused2d.hip); False: A/B tests
@@ -2164,6 +2167,121 @@ def dice_loss(x, target, weight=None, ignore_background=False, batch_dice=False,
     _same_device(x, labels, soft, weight)
     flags = (1 if ignore_background else 0) | (2 if batch_dice else 0)
     return _Dice.apply(x, labels, soft, weight, (flags, float(smooth), float(dice_weight), float(ce_weight)))
+
+
+# ---- soft skeletons and the soft-clDice loss (csrc/seg_skeleton.hip) ---------------------------------------------------------
+
+_SKELETON_ROUTES = {None: 0, "fused": 1, "levels": 2}
+
+
+def _skeleton_route(route, iterations):
+    if route not in _SKELETON_ROUTES:
+        raise ValueError("route must be None, 'fused' or 'levels', got %r" % (route,))
+    if route == "fused" and iterations > SKELETON_FUSED_MAX_ITERATIONS:
+        raise ValueError("the fused route takes at most %d iterations, got %d" % (SKELETON_FUSED_MAX_ITERATIONS, iterations))
+    return _SKELETON_ROUTES[route]
+
+
+def _skeleton_workspace(N, K, sp, iterations, what, device):
+    n = _lib.load().advchain_skeleton_workspace(N, K, len(sp), _lib.dims_array(sp), iterations, what)
+    if n < 0:
+        raise ValueError("bad skeleton shape: N=%d, C=%d, dims=%s, iterations=%d" % (N, K, tuple(sp), iterations))
+    return torch.empty(max(int(n), 4), device=device, dtype=torch.float32)
+
+
+class _SoftSkeleton(torch.autograd.Function):
+    """Soft skeleton of every plane of (N,C,dims) fp32 maps (include/advchain_hip.h: advchain_soft_skeleton_fwd)."""
+
+    @staticmethod
+    def forward(ctx, x, iterations, route):
+        N, C = x.shape[:2]
+        sp = tuple(x.shape[2:])
+        ws = _skeleton_workspace(N, C, sp, iterations, 0, x.device)
+        out = torch.empty_like(x)
+        _lib.check(_lib.load().advchain_soft_skeleton_fwd(_ptr(x), _ptr(out), _ptr(ws), N, C, len(sp), _lib.dims_array(sp),
+                                                          iterations, route, _stream()), "soft_skeleton_fwd")
+        ctx.save_for_backward(x)
+        ctx.iterations = iterations
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, = ctx.saved_tensors
+        N, C = x.shape[:2]
+        sp = tuple(x.shape[2:])
+        g = _dev(gout, "grad")
+        ws = _skeleton_workspace(N, C, sp, ctx.iterations, 1, x.device)
+        gx = torch.empty_like(x)
+        _lib.check(_lib.load().advchain_soft_skeleton_bwd(_ptr(x), _ptr(g), _ptr(gx), _ptr(ws), N, C, len(sp),
+                                                          _lib.dims_array(sp), ctx.iterations, _stream()), "soft_skeleton_bwd")
+        return gx, None, None
+
+
+@_on_tensor_device
+def soft_skeletonize(maps, iterations=3, route=None):
+    """Soft skeleton (iterated min / max pooling, clDice) of every plane of (N,C,H,W) or (N,C,D,H,W) fp32 maps, the bits of the
+    published torch composition in fp32; differentiable.  `route` (tests and tools): None, 'fused' or 'levels'."""
+    x = _dev(maps, "maps")
+    if x.dim() not in (4, 5):
+        raise ValueError("soft_skeletonize takes 4-D (N,C,H,W) or 5-D (N,C,D,H,W) maps, got %d-D" % x.dim())
+    return _SoftSkeleton.apply(x, int(iterations), _skeleton_route(route, int(iterations)))
+
+
+class _ClDice(torch.autograd.Function):
+    """soft-clDice of (N,K,dims) logits (include/advchain_hip.h: advchain_cldice_fwd); differentiable w.r.t. the logits."""
+
+    @staticmethod
+    def forward(ctx, x, labels, soft, weight, cfg):
+        iterations, route, flags, smooth = cfg
+        N, K = x.shape[:2]
+        sp = tuple(x.shape[2:])
+        dims = _lib.dims_array(sp)
+        need = ctx.needs_input_grad[0]
+        ws = _skeleton_workspace(N, K, sp, iterations, 2, x.device)
+        lse = torch.empty((N,) + sp, device=x.device, dtype=torch.float32)
+        skel_t = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+        coef = torch.empty((N, K, 3), device=x.device, dtype=torch.float32) if need else None
+        value = torch.empty((), device=x.device, dtype=torch.float32)
+        _lib.check(_lib.load().advchain_cldice_fwd(_ptr(x), int(x.dtype == torch.bfloat16), _ptr(labels), _ptr(soft), _ptr(weight),
+                                                   _ptr(lse), _ptr(skel_t), _ptr(coef), _ptr(ws), _ptr(value), N, K, len(sp), dims,
+                                                   iterations, route, flags, smooth, _stream()), "cldice_fwd")
+        if need:
+            ctx.save_for_backward(x, labels, soft, lse, skel_t, coef)
+        ctx.iterations = iterations
+        return value
+
+    @staticmethod
+    def backward(ctx, gloss):
+        x, labels, soft, lse, skel_t, coef = ctx.saved_tensors
+        N, K = x.shape[:2]
+        sp = tuple(x.shape[2:])
+        gs = _dev(gloss.reshape(1), "grad")
+        ws = _skeleton_workspace(N, K, sp, ctx.iterations, 3, x.device)
+        gx = torch.empty_like(x)
+        _lib.check(_lib.load().advchain_cldice_bwd(_ptr(x), int(x.dtype == torch.bfloat16), _ptr(labels), _ptr(soft), _ptr(lse),
+                                                   _ptr(skel_t), _ptr(coef), _ptr(gs), _ptr(gx), _ptr(ws), N, K, len(sp),
+                                                   _lib.dims_array(sp), ctx.iterations, _stream()), "cldice_bwd")
+        return gx, None, None, None, None
+
+
+@_on_tensor_device
+def cldice_loss(x, target, iterations=3, weight=None, ignore_background=True, batch=False, smooth=1.0, route=None):
+    """soft-clDice loss on the HIP kernels.  x (N,K,H,W) or (N,K,D,H,W) fp32 / bf16 logits; target: int64 labels (N,dims) (-100:
+    masked out of the sums) or a constant fp32 soft target of x's shape; weight: K class weights or None.  Returns an fp32
+    scalar.  `route` (tests and tools): None, 'fused' or 'levels'."""
+    x = _dev_logits(x, "input")
+    if x.dim() not in (4, 5):
+        raise ValueError("cldice_loss takes 4-D (N,C,H,W) or 5-D (N,C,D,H,W) input, got %d-D" % x.dim())
+    _require_device(target, "target")
+    N, K = x.shape[:2]
+    labels, soft = _labels_or_soft(x, target, "label target must be %s, got %s",
+                                   "cldice_loss: target must be (N,dims) labels or (N,C,dims) soft targets")
+    if soft is not None:
+        soft = soft.detach()
+    weight = _class_weight_tensor(weight, K, x.device)
+    _same_device(x, labels, soft, weight)
+    flags = (1 if ignore_background else 0) | (2 if batch else 0)
+    return _ClDice.apply(x, labels, soft, weight, (int(iterations), _skeleton_route(route, int(iterations)), flags, float(smooth)))
 
 
 # ---- Euclidean distance transform, signed distance maps (csrc/edt.hip) and the boundary loss (csrc/seg_boundary.hip) -----------

@@ -795,6 +795,45 @@ int advchain_dice_bwd(const void* logits, int logits_bf16, const int64_t* labels
                       const float* lse, const float* coef, const float* grad_scale, void* grad_logits, float* grad_soft,
                       int64_t N, int64_t K, int ndim, const int64_t* dims, float dice_w, float ce_w, void* stream);
 
+/* ---- soft skeletons and the soft-clDice loss, 2D and 3D (seg_skeleton.hip) -------------------------------------------------
+ * Not in the reference (Shit et al., clDice, CVPR 2021).  On every plane of maps (N,K,dims) fp32, with E the minimum over a
+ * voxel and its in-image face neighbours and D the maximum over the in-image 3x3(x3) box:
+ *   x_0 = x, x_{j+1} = E(x_j), delta_j = relu(x_j - D(x_{j+1})), skel_0 = delta_0,
+ *   skel_j = skel_{j-1} + relu(delta_j - skel_{j-1} delta_j),  j = 1..iterations (0..ADVCHAIN_SKELETON_MAX_ITERATIONS),
+ * each operation rounded once in fp32: the bits of the published max_pool composition.  route: ADVCHAIN_SKELETON_AUTO, _FUSED
+ * (one launch, the chain of a tile with a halo of iterations + 2 in LDS; at most ADVCHAIN_SKELETON_FUSED_MAX iterations, an
+ * error beyond) or _LEVELS (iterations + 2 launches, any count); the same bits on both.  `workspace`: advchain_skeleton_workspace
+ * floats for `what` = 0 (soft_skeleton_fwd), 1 (soft_skeleton_bwd), 2 (cldice_fwd), 3 (cldice_bwd), 16-byte aligned, no clearing
+ * needed; a host-only query, -1 for bad sizes.  No float atomics, no memset, no host read-back: bitwise reproducible,
+ * capturable on one stream.                                                                                                  */
+#define ADVCHAIN_SKELETON_MAX_ITERATIONS 32
+#define ADVCHAIN_SKELETON_FUSED_MAX 4
+#define ADVCHAIN_SKELETON_AUTO 0
+#define ADVCHAIN_SKELETON_FUSED 1
+#define ADVCHAIN_SKELETON_LEVELS 2
+int64_t advchain_skeleton_workspace(int64_t N, int64_t K, int ndim, const int64_t* dims, int iterations, int what); /* floats */
+int advchain_soft_skeleton_fwd(const float* maps, float* skeleton, float* workspace, int64_t N, int64_t K, int ndim,
+                               const int64_t* dims, int iterations, int route, void* stream);
+/* its gradient, in gather form (the erosion chain is recomputed into the workspace with a 1-byte selection code per voxel and
+ *           level; 2 iterations + 4 launches): grad_maps (N,K,dims) from grad_skeleton (N,K,dims).  relu'(0) = 0; among equal
+ *           window values the first wins: centre, then axis by axis, minus before plus (E); centre, then raster order (D).     */
+int advchain_soft_skeleton_bwd(const float* maps, const float* grad_skeleton, float* grad_maps, float* workspace, int64_t N,
+                               int64_t K, int ndim, const int64_t* dims, int iterations, void* stream);
+/* soft-clDice of logits (N,K,dims) fp32 / bf16 against labels (N,dims) int64 or a soft target (N,K,dims) fp32 (exactly one):
+ *   p = softmax over K (inside the kernels), t = one-hot (a label outside [0,K), -100 included: no class), m = 0 at -100,
+ *   S^p = skel(p), S^t = skel(t);  over the voxels of entry n (ADVCHAIN_DICE_BATCH: of every entry, N -> 1)
+ *   Tprec = (sum m S^p t + smooth) / (sum m S^p + smooth),  Tsens = (sum m S^t p + smooth) / (sum m S^t + smooth),
+ *   value = 1 - 1/rows sum_nk omega_k 2 Tprec Tsens / (Tprec + Tsens),   omega_k = w_k / sum of the counted w_j
+ * (flags as advchain_dice_fwd).  lse (N*voxels), skeleton_target (N*K*voxels) and coef (N*K*3: dL/dS^p = m (A t + B), the
+ * direct dL/dp = m C S^t) are kept for the backward; coef may be NULL.                                                      */
+int advchain_cldice_fwd(const void* logits, int logits_bf16, const int64_t* labels, const float* soft, const float* weight,
+                        float* lse, float* skeleton_target, float* coef, float* workspace, float* value, int64_t N, int64_t K,
+                        int ndim, const int64_t* dims, int iterations, int route, int flags, float smooth, void* stream);
+/* its gradient for the logits (their dtype, computed in fp32 and rounded once); gs = *grad_scale (device scalar, NULL = 1). */
+int advchain_cldice_bwd(const void* logits, int logits_bf16, const int64_t* labels, const float* soft, const float* lse,
+                        const float* skeleton_target, const float* coef, const float* grad_scale, void* grad_logits,
+                        float* workspace, int64_t N, int64_t K, int ndim, const int64_t* dims, int iterations, void* stream);
+
 /* ---- Euclidean distance transform and signed distance maps, 2D and 3D (edt.hip) --------------------------------------------
  * Not in the reference.  Exact and separable: one pass along the contiguous axis (both sides of every row), then per further
  * axis the lower envelope min_j f(j) + (s (i - j))^2 from LDS-staged lines.  `dims` is (H, W) or (D, H, W); `sampling` is NULL
