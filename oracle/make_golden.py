@@ -5,7 +5,7 @@ fixtures it writes are data: seeded/closed-form inputs and the reference's outpu
 
     python oracle/make_golden.py            # rewrites every fixture
 
-Fixture families: G1 grid_sample, G2 AdvBias, G3 AdvMorph, G4 AdvAffine,
+Fixture families: G1 grid_sample, G2 AdvBias (G2b: orders other than 3), G3 AdvMorph, G4 AdvAffine,
 G5 consistency loss, G6 full solver traces (per-step dist / raw grads / params for the
 teacher-forced protocol), plus the RNG-free known-answer sums of SURVEY Appendix B.
 """
@@ -161,6 +161,42 @@ def g2_bias(aug):
                 out[key + "field"], out[key + "out"] = t.bias_field.detach(), o.detach()
     out["meta"] = meta
     save("g2_bias", out)
+
+
+# ----------------------------------------------------------------------------- G2b
+G2B_CASES = ("2d_o0_ds4", "2d_o2_wide_sp", "2d_o5_ds1", "2d_o7_ds1", "2d_2x2", "3d_o1_nc", "3d_o2_ds4")
+
+
+def g2b_bias_orders(aug):
+    """The reference's AdvBias beyond order 3 (orders 0, 1, 2, 5, 7; downscale 1, 2, 4; 3D at orders 1 and 2; both spaces) on
+    cases of tests/bias_config_cases.py with that module's seeded inputs, in the record layout of g2_bias.  A configuration
+    the reference cannot run is left out and named on stdout."""
+    from tests import bias_config_cases as K
+    out, meta = {}, {}
+    for name in G2B_CASES:
+        sd = K.CASES[name][0]
+        cfg = K.config(name)
+        param, data, w = (x.clone() for x in K.inputs(name))
+        try:
+            t = aug.AdvBias(spatial_dims=sd, config_dict=cfg, use_gpu=False, device=CPU)
+            t.init_parameters()
+            assert tuple(t.param.shape) == tuple(param.shape), (name, t.param.shape, param.shape)
+            p = param.requires_grad_(True)
+            t.param = p
+            o = t.forward(data)
+            (o * w).sum().backward()
+        except Exception as e:      # noqa: BLE001
+            print("g2b: the reference cannot run %s: %r" % (name, e))
+            continue
+        key = name + "_"
+        meta[key] = dict(spatial_dims=sd, config=cfg, cp_grid=list(t.param.shape),
+                         crop_start=t._crop_start.tolist(), crop_end=t._crop_end.tolist(),
+                         stride=list(t._stride), padding=list(t._padding), kernel=list(t.interp_kernel.shape))
+        out[key + "param"], out[key + "grad_param"] = p.detach(), p.grad
+        out[key + "data"], out[key + "w"] = data, w
+        out[key + "field"], out[key + "out"] = t.bias_field.detach(), o.detach()
+    out["meta"] = meta
+    save("g2b_bias_orders", out)
 
 
 # ----------------------------------------------------------------------------- G3
@@ -1191,6 +1227,8 @@ def main():
         g1_grid_sample()
     if want("g2"):
         g2_bias(aug)
+    if want("g2b"):
+        g2b_bias_orders(aug)
     if want("g3"):
         g3_morph(aug)
     if want("g4"):

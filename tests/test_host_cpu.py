@@ -30,14 +30,19 @@ def build_chain(spec):
 
 def test_band_tables_reproduce_the_reference_bias_field(cpu_ops):
     from advchain_amd.augmentor import AdvBias
-    fx = Fixture("g2_bias")
+    # g2_bias: order 3, bands of at most 5; g2b_bias_orders: orders 0, 1, 2, 5 and 7, bands of 1 to 7
+    for fx, band_max in ((Fixture("g2_bias"), 5), (Fixture("g2b_bias_orders"), 7)):
+        _bias_fixture_on_band_tables(AdvBias, fx, band_max)
+
+
+def _bias_fixture_on_band_tables(AdvBias, fx, band_max):
     for key, m in fx.json().items():
         t = AdvBias(spatial_dims=m["spatial_dims"], config_dict=m["config"], device=CPU)
         t.init_parameters()
         assert list(t.param.shape) == m["cp_grid"]
         assert t._crop_start.tolist() == m["crop_start"] and t._crop_end.tolist() == m["crop_end"]
         assert t._stride == m["stride"]
-        assert max(t._tables.B) <= 5
+        assert max(t._tables.B) <= band_max
         p = fx.t(key + "param").requires_grad_(True)
         t.param = p
         if key + "data" in fx:
