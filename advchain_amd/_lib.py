@@ -130,6 +130,10 @@ PROTOTYPES = {
     "advchain_instance_match": (_I, [_P] * 14 + [_L, _L, _I, _P, _I, _L, _D, _P]),
     "advchain_betti_workspace": (_L, [_L, _I, _P]),
     "advchain_betti": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _P]),
+    "advchain_confusion_limit": (_L, [_I]),
+    "advchain_confusion": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _L, _I, _P]),
+    "advchain_overlap": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _I, _L, _I, _P]),
+    "advchain_overlap_scores": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _P]),
     "advchain_morph_workspace": (_L, [_I, _L, _L, _I, _P]),
     "advchain_morph": (_I, [_P, _P, _D, _I, _P, _P, _L, _L, _L, _I, _P, _P]),
     "advchain_boundary_workspace": (_L, [_L, _L, _I, _P]),

@@ -96,13 +96,45 @@ and b1 = b0 + b2 - chi.  This is Euler-Poincare for the adjacency pairs above (K
 Cost.  One labelling of all classes and one streaming pass over the windows per map; in 3D one more labelling per class for the
 cavities, 1 + K labellings per map in all (2D needs none: b1 follows from chi).  The workspace is that of one labelling whatever K
 is.  Every value is the same bits on every run; integer atomics only, nothing is read back to the host, and the call can be
-captured in a graph.  There is no gradient: the inputs are detached."""
+captured in a graph.  There is no gradient: the inputs are detached.
+
+Confusion matrix and voxel overlap (``confusion_matrix``, ``overlap_metrics``, ``overlap_scores``; csrc/seg_confusion.hip).  The
+first numbers of any report: which class is taken for which, and per class Dice, IoU, precision, recall and specificity.
+
+Inputs.  target is an int64 label map (N, dims).  pred is either an int64 label map of the same shape or fp32 / bf16 logits (or
+probabilities) (N, K, dims); the prediction is then the argmax over the class axis, taken inside the kernel with the rule of
+torch.argmax on the CPU: the first maximal class wins, a NaN is larger than everything (the first NaN wins), a row of -inf gives
+class 0.  bf16 values are widened to fp32, which is exact, so they are compared exactly.
+
+Sets.  A_k = {v : pred[v] == k} and B_k = {v : target[v] == k} for every k in [0, K), class 0 included.  A label outside [0, K) is
+in no class and is never used as an address.  ``ignore_index`` is None or an int: a voxel whose TARGET equals it is left out of
+every count (the "void" label, usually -100); a prediction equal to it means nothing.  With None nothing is left out, and a
+target of -100 is a counted voxel of no class: the counts are then exactly those of surface_distance_metrics(...).overlap.
+
+Counts.  matrix[n,t,p] = #{counted v : target = t, pred = p}: rows are the truth, columns the prediction (sklearn's convention).
+pred_only[n,k] = #{counted v : pred = k, target outside [0, K)}, target_only[n,k] = #{counted v : target = k, pred outside
+[0, K)}, counted[n] = the voxels not left out.  |A_k| = column sum + pred_only[k], |B_k| = row sum + target_only[k], |A_k n B_k|
+is the diagonal.  A voxel outside [0, K) in both maps is counted and is in no other number.  With reduce_batch=True the leading N
+is dropped and every entry adds into the same counters.
+
+Quotients.  TP = |A n B|, FP = |A| - TP, FN = |B| - TP, TN = counted - TP - FP - FN.  Each quotient is taken in float64 from these
+integers and rounded to fp32 once:
+
+    dice         2 TP / (|A| + |B|)       NaN when |A| + |B| == 0
+    iou          TP / (|A| + |B| - TP)    NaN when |A| + |B| == 0
+    precision    TP / |A|                 NaN when |A| == 0
+    recall       TP / |B|                 NaN when |B| == 0      (the sensitivity)
+    specificity  TN / (TN + FP)           NaN when TN + FP == 0  (every counted voxel is in B)
+
+Averages over classes or cases (macro, micro, per-case means) are one line of torch on these tensors.  One streaming pass over the
+inputs; integer atomics only, every value is the same bits on every run and for every alignment of the storage, nothing is read
+back to the host, and the calls can be captured in a graph.  There is no gradient: the inputs are detached."""
 import math
 
 import torch
 
 from .. import ops
-from ..ops import Betti, BettiError, InstanceMetrics, SurfaceDice, SurfaceMetrics  # noqa: F401
+from ..ops import Betti, BettiError, Confusion, InstanceMetrics, OverlapMetrics, OverlapScores, SurfaceDice, SurfaceMetrics  # noqa: F401
 from .loss import _check_num_classes, _check_sampling, _require_gpu
 from .postprocess import _check_labels
 
@@ -280,3 +312,100 @@ def betti_error(pred, target, num_classes, connectivity=1):
     Both maps go through one call and one workspace; the result equals that of two betti_numbers calls."""
     _check_topology("betti_error", [(pred, "pred"), (target, "target")], num_classes, connectivity)
     return ops.betti_error(pred, target, num_classes, connectivity=connectivity)
+
+
+def _check_confusion(name, pred, target, num_classes, ignore_index, return_labels):
+    """Every ValueError of the confusion family, before any GPU work."""
+    if not isinstance(target, torch.Tensor) or target.dim() not in (3, 4):
+        raise ValueError("%s expects 3-D (N,H,W) or 4-D (N,D,H,W) labels as target" % name)
+    if target.dtype != torch.int64:
+        raise ValueError("%s: target must be int64 labels, got %s" % (name, target.dtype))
+    if target.numel() == 0:
+        raise ValueError("%s: empty label map %s" % (name, tuple(target.shape)))
+    _check_num_classes(name, num_classes)
+    if not isinstance(pred, torch.Tensor):
+        raise ValueError("%s expects a tensor as pred: int64 labels or float32 / bfloat16 logits" % name)
+    if pred.dtype == torch.int64:
+        if pred.shape != target.shape:
+            raise ValueError("%s: pred %s and target %s differ in shape" % (name, tuple(pred.shape), tuple(target.shape)))
+        if return_labels:
+            raise ValueError("%s: return_labels needs logits as pred (a label map is its own argmax)" % name)
+    elif pred.dtype in (torch.float32, torch.bfloat16):
+        want = (target.shape[0], num_classes) + tuple(target.shape[1:])
+        if tuple(pred.shape) != want:
+            raise ValueError("%s: logits must have the shape (N, num_classes, dims) = %s for a target %s, got %s"
+                             % (name, want, tuple(target.shape), tuple(pred.shape)))
+    else:
+        raise ValueError("%s: pred must be int64 labels or float32 / bfloat16 logits, got %s" % (name, pred.dtype))
+    if ignore_index is not None and (isinstance(ignore_index, bool) or not isinstance(ignore_index, int)
+                                     or not -2 ** 63 <= ignore_index < 2 ** 63):
+        raise ValueError("%s: ignore_index must be None or an int (of 64 bits), got %r" % (name, ignore_index))
+
+
+def confusion_matrix(pred, target, num_classes, ignore_index=None, reduce_batch=False, out=None, return_labels=False):
+    """The (target, prediction) count matrix of every entry (definitions: "Confusion matrix and voxel overlap" in the module's
+    docstring).  pred: int64 labels (N,dims), or fp32 / bf16 logits (N,K,dims) with K == num_classes whose argmax is taken inside
+    the kernel; target: int64 labels (N,dims).  Returns Confusion, a namedtuple of device tensors:
+
+        matrix       (N,K,K)   int64   [n,t,p] = #{counted v : target = t, pred = p}; rows are the truth
+        pred_only    (N,K)     int64   #{counted v : pred = k, target outside [0, K)}
+        target_only  (N,K)     int64   #{counted v : target = k, pred outside [0, K)}
+        counted      (N,)      int64   voxels not left out by ignore_index
+        labels       (N,dims)  int64   the argmax map, written in the same pass, with return_labels=True (logits only); else None
+
+    reduce_batch=True drops the leading N: every entry adds into the same counters.  out: a Confusion of exactly the shapes the
+    call would return; the call adds into its four count tensors without clearing them and returns it, which accumulates a
+    dataset-level matrix over batches of any size with reduce_batch=True.  num_classes is at most 1024 (8 MB of matrix per entry);
+    overlap_metrics has the scores for more classes without a matrix."""
+    name = "confusion_matrix"
+    _check_confusion(name, pred, target, num_classes, ignore_index, return_labels)
+    if num_classes > ops.CONFUSION_MAX_K:
+        raise ValueError("%s takes at most %d classes (8 MB of matrix per entry), got %d: overlap_metrics has the per-class scores "
+                         "for up to 65535 classes without a matrix" % (name, ops.CONFUSION_MAX_K, num_classes))
+    if out is not None:
+        shapes = ops.confusion_shapes(target.shape[0], num_classes, reduce_batch)
+        if not isinstance(out, Confusion):
+            raise ValueError("%s: out must be a Confusion, got %s" % (name, type(out).__name__))
+        for field, t, s in zip(Confusion._fields, out[:4], shapes):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or tuple(t.shape) != s or not t.is_contiguous() \
+                    or t.device != target.device:
+                raise ValueError("%s: out.%s must be a contiguous int64 tensor of shape %s on the target's device"
+                                 % (name, field, s))
+    _require_gpu(pred, "pred")
+    _require_gpu(target, "target")
+    return ops.confusion_matrix(pred, target, num_classes, ignore_index=ignore_index, reduce_batch=bool(reduce_batch), out=out,
+                                return_labels=bool(return_labels))
+
+
+def overlap_metrics(pred, target, num_classes, ignore_index=None, reduce_batch=False, return_labels=False):
+    """Per-class voxel overlap scores of every entry without building the matrix (definitions: "Confusion matrix and voxel
+    overlap" in the module's docstring).  pred, target, ignore_index, reduce_batch and return_labels as for confusion_matrix;
+    num_classes up to 65535.  Returns OverlapMetrics, a namedtuple of device tensors:
+
+        overlap      (N,K,3)   int64   |A|, |B|, |A n B| over the counted voxels
+        counted      (N,)      int64   voxels not left out by ignore_index
+        dice, iou, precision, recall, specificity   (N,K) fp32 each; NaN when the denominator is 0
+        labels       (N,dims)  int64   the argmax map with return_labels=True (logits only); else None
+
+    With ignore_index=None, overlap and dice equal those of surface_distance_metrics bit for bit."""
+    _check_confusion("overlap_metrics", pred, target, num_classes, ignore_index, return_labels)
+    _require_gpu(pred, "pred")
+    _require_gpu(target, "target")
+    return ops.overlap_metrics(pred, target, num_classes, ignore_index=ignore_index, reduce_batch=bool(reduce_batch),
+                               return_labels=bool(return_labels))
+
+
+def overlap_scores(matrix):
+    """The scores of overlap_metrics from finished count matrices (..., K, K) int64, rows = truth: for example an accumulated
+    Confusion.matrix.  The matrix is taken as complete: |A_k| is its column sum, |B_k| its row sum and counted its total (what
+    pred_only and target_only hold is not in it).  Returns OverlapScores with the leading shape: overlap (...,K,3) int64, counted
+    (...) int64 and dice, iou, precision, recall, specificity (...,K) fp32, through the same finish kernel."""
+    if not isinstance(matrix, torch.Tensor) or matrix.dim() < 2 or matrix.shape[-1] != matrix.shape[-2]:
+        raise ValueError("overlap_scores expects count matrices (..., K, K)")
+    if matrix.dtype != torch.int64:
+        raise ValueError("overlap_scores: the matrix must be int64, got %s" % matrix.dtype)
+    if matrix.numel() == 0:
+        raise ValueError("overlap_scores: empty matrix %s" % (tuple(matrix.shape),))
+    _check_num_classes("overlap_scores", int(matrix.shape[-1]))
+    _require_gpu(matrix, "matrix")
+    return ops.overlap_scores(matrix)

@@ -2688,6 +2688,107 @@ def betti_error(pred, target, num_classes, connectivity=1):
     return BettiError(error, error.sum(dim=2), betti, euler)
 
 
+# ---- confusion matrix and per-class overlap scores, also from logits (csrc/seg_confusion.hip) -----------------------------------
+
+Confusion = collections.namedtuple("Confusion", ["matrix", "pred_only", "target_only", "counted", "labels"])
+OverlapMetrics = collections.namedtuple("OverlapMetrics", ["overlap", "counted", "dice", "iou", "precision", "recall", "specificity",
+                                                          "labels"])
+OverlapScores = collections.namedtuple("OverlapScores", ["overlap", "counted", "dice", "iou", "precision", "recall", "specificity"])
+# advchain_confusion_limit(0..4) of the source (tests/test_confusion_cpu.py holds the two sides together)
+CONFUSION_TILE = 1024            # voxels a workgroup takes at a time: kTile
+CONFUSION_MAX_BLOCKS = 128       # workgroups per entry; from there on a workgroup walks several tiles: kMaxBlocks
+CONFUSION_LDS_MAX_K = 127        # the matrix is counted in LDS up to this many classes ((K + 1)^2 words: 64 KB), in global memory above
+CONFUSION_MAX_K = 1024           # classes of a matrix (8 MB per entry)
+OVERLAP_LDS_MAX_K = 2048         # the 3 K counters of overlap_metrics are in LDS up to this many classes, in global memory above
+_PRED_KINDS = {torch.int64: 0, torch.float32: 1, torch.bfloat16: 2}
+
+
+def confusion_shapes(N, K, reduce_batch):
+    """The shapes of Confusion's matrix, pred_only, target_only and counted."""
+    lead = () if reduce_batch else (N,)
+    return lead + (K, K), lead + (K,), lead + (K,), lead
+
+
+def _confusion_inputs(name, pred, target, num_classes, return_labels):
+    """(pred contiguous, its kind, target contiguous, N, K, spatial shape, dims array, labels or None)."""
+    pred = pred.detach() if isinstance(pred, torch.Tensor) else pred
+    target = _dev_labels(target.detach() if isinstance(target, torch.Tensor) else target, "target")
+    _require_device(pred, "pred")
+    if pred.dtype not in _PRED_KINDS:
+        raise ValueError("%s: pred must be int64 labels or float32 / bfloat16 logits, got %s" % (name, pred.dtype))
+    _same_device(pred, target)
+    kind, K = _PRED_KINDS[pred.dtype], int(num_classes)
+    N, sp = target.shape[0], tuple(target.shape[1:])
+    want = tuple(target.shape) if kind == 0 else (N, K) + sp
+    if tuple(pred.shape) != want:
+        raise ValueError("%s: pred must have the shape %s for a target %s, got %s" % (name, want, tuple(target.shape), tuple(pred.shape)))
+    if return_labels and kind == 0:
+        raise ValueError("%s: return_labels needs logits as pred (a label map is its own argmax)" % name)
+    pred = pred if pred.is_contiguous() else pred.contiguous()
+    labels = torch.empty(target.shape, device=target.device, dtype=torch.int64) if return_labels else None
+    return pred, kind, target, N, K, sp, _lib.dims_array(sp), labels
+
+
+def _confusion_flags(ignore_index, reduce_batch, accumulate=False):
+    return (0 if ignore_index is None else 1, 0 if ignore_index is None else int(ignore_index),
+            (1 if reduce_batch else 0) | (2 if accumulate else 0))
+
+
+@_on_tensor_device
+def confusion_matrix(pred, target, num_classes, ignore_index=None, reduce_batch=False, out=None, return_labels=False):
+    """pred: (N,dims) int64 labels or (N,K,dims) fp32 / bf16 logits; target (N,dims) int64 -> Confusion of int64 device tensors:
+    matrix (N,K,K) with rows = truth, pred_only (N,K), target_only (N,K), counted (N,), and labels (N,dims), the argmax map, with
+    return_labels (include/advchain_hip.h: advchain_confusion).  out: a Confusion of the same shapes to add into.  No gradient."""
+    pred, kind, target, N, K, sp, dims, labels = _confusion_inputs("confusion_matrix", pred, target, num_classes, return_labels)
+    if out is None:
+        counts = [torch.empty(s, device=target.device, dtype=torch.int64) for s in confusion_shapes(N, K, reduce_batch)]
+    else:
+        counts = list(out[:4])
+        for t, s in zip(counts, confusion_shapes(N, K, reduce_batch)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or tuple(t.shape) != s or not t.is_contiguous():
+                raise ValueError("confusion_matrix: out must hold contiguous int64 tensors of the shapes %s"
+                                 % (confusion_shapes(N, K, reduce_batch),))
+        _same_device(target, *counts)
+    has_ignore, ignore, flags = _confusion_flags(ignore_index, reduce_batch, out is not None)
+    _lib.check(_lib.load().advchain_confusion(_ptr(pred), kind, _ptr(target), _ptr(labels), *[_ptr(t) for t in counts], N, K, len(sp),
+                                              dims, has_ignore, ignore, flags, _stream()), "confusion")
+    return Confusion(counts[0], counts[1], counts[2], counts[3], labels)
+
+
+@_on_tensor_device
+def overlap_metrics(pred, target, num_classes, ignore_index=None, reduce_batch=False, return_labels=False):
+    """pred and target as for confusion_matrix -> OverlapMetrics: overlap (N,K,3) int64 = |A|, |B|, |A n B|, counted (N,) int64,
+    dice / iou / precision / recall / specificity (N,K) fp32 and labels (include/advchain_hip.h: advchain_overlap).  No matrix is
+    built.  No gradient."""
+    pred, kind, target, N, K, sp, dims, labels = _confusion_inputs("overlap_metrics", pred, target, num_classes, return_labels)
+    lead, dev = (() if reduce_batch else (N,)), target.device
+    overlap = torch.empty(lead + (K, 3), device=dev, dtype=torch.int64)
+    counted = torch.empty(lead, device=dev, dtype=torch.int64)
+    scores = [torch.empty(lead + (K,), device=dev, dtype=torch.float32) for _ in range(5)]
+    has_ignore, ignore, flags = _confusion_flags(ignore_index, reduce_batch)
+    _lib.check(_lib.load().advchain_overlap(_ptr(pred), kind, _ptr(target), _ptr(labels), _ptr(overlap), _ptr(counted),
+                                            *[_ptr(t) for t in scores], N, K, len(sp), dims, has_ignore, ignore, flags, _stream()),
+               "overlap")
+    return OverlapMetrics(overlap, counted, *scores, labels)
+
+
+@_on_tensor_device
+def overlap_scores(matrix):
+    """(...,K,K) int64 count matrices, rows = truth, taken as complete -> OverlapScores with the leading shape: overlap (...,K,3)
+    int64, counted (...) int64 and the five fp32 scores (...,K) (include/advchain_hip.h: advchain_overlap_scores).  No gradient."""
+    matrix = _dev_labels(matrix.detach() if isinstance(matrix, torch.Tensor) else matrix, "matrix")
+    lead, K = tuple(matrix.shape[:-2]), matrix.shape[-1]
+    R = 1
+    for s in lead:
+        R *= s
+    overlap = torch.empty(lead + (K, 3), device=matrix.device, dtype=torch.int64)
+    counted = torch.empty(lead, device=matrix.device, dtype=torch.int64)
+    scores = [torch.empty(lead + (K,), device=matrix.device, dtype=torch.float32) for _ in range(5)]
+    _lib.check(_lib.load().advchain_overlap_scores(_ptr(matrix), _ptr(overlap), _ptr(counted), *[_ptr(t) for t in scores], R, K,
+                                                   _stream()), "overlap_scores")
+    return OverlapScores(overlap, counted, *scores)
+
+
 # ---- erosion, dilation, opening and closing with a Euclidean ball (csrc/seg_morph.hip) -----------------------------------------
 
 # The tiles of the morphology kernels by number of spatial axes; None: the axis is not tiled (k_morph_axis stages whole lines).

@@ -1025,6 +1025,46 @@ int64_t advchain_betti_workspace(int64_t N, int ndim, const int64_t* dims); /* 4
 int advchain_betti(const int64_t* pred, const int64_t* target, int64_t* betti, int64_t* euler, int64_t* error, void* workspace,
                    int64_t N, int64_t K, int ndim, const int64_t* dims, int connectivity, void* stream);
 
+/* ---- confusion matrix and per-class overlap scores, also from logits, 2D and 3D (seg_confusion.hip) ---------------------------
+ * Not in the reference.  target (N, dims) int64, dims = (H, W) or (D, H, W).  `pred_kind` says what pred is: 0 an int64 label map
+ * (N, dims); 1 fp32 or 2 bf16 logits or probabilities (N, K, dims), whose argmax over the class axis is the prediction: the first
+ * maximal class wins, a NaN is larger than everything (the first NaN wins), a row of -inf gives class 0 -- torch.argmax on the
+ * CPU; bf16 is widened to fp32, exactly.  A_k = {v : pred[v] == k}, B_k = {v : target[v] == k} for every k in [0, K); a label
+ * outside [0, K) is in no class and is never used as an address.  With has_ignore = 1 a voxel whose TARGET equals ignore_index is
+ * left out of every count (has_ignore = 0: nothing is left out, whatever ignore_index holds).  labels_out (N, dims) int64 or NULL:
+ * the argmax map, written in the same pass (logits only).  `flags`: 1 reduce_batch -- the outputs lose their leading N and every
+ * entry adds into the same counters; 2 accumulate (advchain_confusion only) -- the counters are not cleared first, the call adds
+ * into what they hold.  Outputs, 8-byte aligned; none needs clearing without flag 2:
+ *   advchain_confusion       matrix (N,K,K) int64       [n,t,p] = #{counted v : target = t, pred = p}: rows are the truth
+ *                            pred_only (N,K) int64      #{counted v : pred = k, target outside [0, K)}
+ *                            target_only (N,K) int64    #{counted v : target = k, pred outside [0, K)}
+ *                            counted (N) int64          voxels not left out by ignore_index
+ *                            K in 1 .. 1024 (8 MB of matrix per entry).
+ *   advchain_overlap         overlap (N,K,3) int64      |A|, |B|, |A n B| over the counted voxels; counted (N) int64;
+ *                            dice, iou, precision, recall, specificity (N,K) fp32: with TP = |A n B|, FP = |A| - TP,
+ *                            FN = |B| - TP, TN = counted - TP - FP - FN: 2 TP / (|A| + |B|), TP / (|A| + |B| - TP), TP / |A|,
+ *                            TP / |B|, TN / (TN + FP), each one fp64 division rounded to fp32 once, NaN when the denominator
+ *                            is 0.  No matrix is built: 3 K counters per entry, K in 1 .. 65535.
+ *   advchain_overlap_scores  the same overlap, counted and quotients from R finished matrices (R,K,K) int64 taken as complete:
+ *                            |A_k| the column sum, |B_k| the row sum, TP the diagonal, counted the total.
+ * One streaming pass: a lane owns 4 consecutive voxels (16-byte loads where pointers and sizes allow, scalar otherwise: the
+ * results do not depend on alignment), a workgroup walks tiles of 1024 voxels of one entry, at most 128 workgroups an entry (more
+ * only where a workgroup would otherwise see 2^31 voxels or more).  A wave groups equal keys so that one lane adds a group's
+ * count; the adds go to 32-bit counters in LDS (the matrix up to K = 127, overlap up to K = 2048), flushed once with 64-bit
+ * global adds, or straight to the global counters above.  Integer atomics only, no memset, no workspace, no host read-back: the
+ * same bits on every run, capturable on one stream.  advchain_confusion_limit(what): 0 the voxels of a tile, 1 the cap on
+ * workgroups per entry, 2 the largest K of the LDS matrix, 3 the largest K of the matrix, 4 the largest K of the LDS overlap
+ * counters; -1 otherwise.  Host only.                                                                                          */
+int64_t advchain_confusion_limit(int what);
+int advchain_confusion(const void* pred, int pred_kind, const int64_t* target, int64_t* labels_out, int64_t* matrix,
+                       int64_t* pred_only, int64_t* target_only, int64_t* counted, int64_t N, int64_t K, int ndim,
+                       const int64_t* dims, int has_ignore, int64_t ignore_index, int flags, void* stream);
+int advchain_overlap(const void* pred, int pred_kind, const int64_t* target, int64_t* labels_out, int64_t* overlap,
+                     int64_t* counted, float* dice, float* iou, float* precision, float* recall, float* specificity, int64_t N,
+                     int64_t K, int ndim, const int64_t* dims, int has_ignore, int64_t ignore_index, int flags, void* stream);
+int advchain_overlap_scores(const int64_t* matrix, int64_t* overlap, int64_t* counted, float* dice, float* iou, float* precision,
+                            float* recall, float* specificity, int64_t R, int64_t K, void* stream);
+
 /* ---- erosion, dilation, opening and closing of label maps with a Euclidean ball, 2D and 3D (seg_morph.hip) ---------------------
  * Not in the reference.  labels (N, dims) int64, dims = (H, W) or (D, H, W); K classes; `background` any integer.  A class voxel
  * carries a label k in [0, K) other than `background`; S_k is the set of voxels of an entry with label k.  A label outside [0, K)
